@@ -14,14 +14,20 @@ N(0,1) text contexts and noise).  Multi-GPU = batch sharding: per-GPU work is fi
 the text contexts + global noise are broadcast from rank 0 and the images all-gathered inside the
 timed region (RCCL), nothing crosses GPUs inside a step.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps, writes the last timed step's images when `--dump-outputs DIR` is given
+(DIR/images.npy, float32 [batch, size, size, 3] holding the uint8 values; a fixed seeded sample of them, DIR/images_sample.npy,
+when they would exceed 64 MB) and prints the line.  Rank 0 prints ONE JSON line with the contract fields; with `--full` it adds
+  ms_denoise_loop / ms_vae_decode   the two halves of a job timed separately, and launches_per_step
   roofline      the dominant kernel (implicit-GEMM conv/dense on MFMA): algorithmic FLOP per launch
                 / its average launch duration measured here with HIP events on the launch stream;
                 `traffic` = L2-miss bytes per launch from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) that THIS
                 run makes as child processes over tools/pmc_step.py before it touches the GPU itself (N = 1 only;
                 --quoted-traffic, or a box without rocprofv3, falls back to the newest file under profiles/ and says so)
+  roofline_by_kernel, eager_ms_per_unet_step_by_entry_point   per kernel class / entry point of one eager step
+  psnr_db_vs_oracle_golden   the final latent of one 512x512 x 25 job against the committed fp32-oracle latent
   cpu_baseline  the oracle (fp32 CPU restatement of the reference path; Keras itself is not
                 installable here) timed on this box's host cores on a bounded sample
+--no-roofline, --quoted-traffic and --no-cpu-baseline trim a --full run; a plain run does none of these.
 """
 from __future__ import annotations
 
@@ -54,6 +60,11 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beyond the headline: job halves, roofline (rocprofv3 child passes), per-kernel rates, "
+                         "PSNR against the oracle golden, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the images of the last timed step to DIR/images.npy (float32)")
     ap.add_argument("--batch-per-gpu", type=int, default=1)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--denoise-steps", type=int, default=25)
@@ -76,7 +87,10 @@ def parse_args(argv=None):
     ap.add_argument("--stub-local", action="store_true",
                     help="replace the GPU pipeline by a trivial per-sample generator (launcher / sharding self-test; the "
                          "line is marked stub and is not a measurement)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 LIVE_TRAFFIC = None   # summary of this run's own PMC passes (live_traffic), read by kernel_roofline
@@ -398,12 +412,13 @@ def main(argv=None):
         # the driver's plain `python bench.py --gpus N`: become the launcher BEFORE anything touches a GPU
         sys.exit(launch_ranks(args.gpus, sys.argv[1:] if argv is None else argv))
 
-    if (args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.backend == "nccl" and not args.stub_local
-            and not args.no_roofline and not args.quoted_traffic):
+    roofline_here = (args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.backend == "nccl"
+                     and not args.stub_local and not args.no_roofline)
+    if roofline_here and not args.quoted_traffic:
         global LIVE_TRAFFIC, LIVE_INGRAPH   # (children first: nothing in this process has initialised the GPU yet)
         LIVE_TRAFFIC = live_traffic(args)
         LIVE_INGRAPH = in_graph_trace(args)
-    elif (args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.backend == "nccl" and not args.stub_local and not args.no_roofline):
+    elif roofline_here:
         LIVE_INGRAPH = in_graph_trace(args)   # (--quoted-traffic: the counters are quoted from profiles/, the in-graph trace is still this run's)
 
     import torch
@@ -491,7 +506,7 @@ def main(argv=None):
         if args.controlnet:  # zero-convs are NOT zero (bias_scale > 0 also draws non-trivial biases), else the path is vacuous
             load_synthetic_shared(sd.control_net, rank, sdir, bias_scale=0.05)
             load_synthetic_shared(sd.hint_net, rank, sdir, bias_scale=0.05)
-        if rank != 0 or args.no_cpu_baseline:
+        if rank != 0 or args.no_cpu_baseline or not args.full:
             unet_arrays = vae_arrays = None
         log(f"[rank {rank}] weights {'generated + packed' if rank == 0 or sdir is None else 'mapped from rank 0 (' + sdir + ')'} in {time.time() - t0:.1f}s")
         out_shape = (gb, size, size, 3)
@@ -538,6 +553,8 @@ def main(argv=None):
     if not stub:
         check_job_flags()
     assert tuple(img.shape) == out_shape and img.dtype == torch.uint8 and (rank != 0 or img.device.type == "cpu")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, img)
 
     images = gb * args.steps
     value = images / elapsed
@@ -576,7 +593,7 @@ def main(argv=None):
         out["config"]["cond_uncond"] = "two HIP streams" if sd._engine(b, 77, 77, nsteps, 7.5, 0.7, args.controlnet).dual else "one fused batch"
         out["tflops_per_gpu"] = round(tflop_per_image * b * args.steps / elapsed, 2)
 
-    if rank == 0 and not stub:
+    if rank == 0 and not stub and args.full:
         rank0_extras(out, args, sd, world, b, nsteps, size, ctx, unc, noise, hints, unet_arrays, vae_arrays)
     if rank == 0:
         if args.sync_phases and phase.wall_ms:   # (profiling runs: host wall time per phase, device drained at each end)
@@ -701,6 +718,23 @@ def to_host(img):
             acc = _host_out["flags"] = torch.zeros_like(flags)
         acc.bitwise_or_(flags)
     return buf
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: what the timed path handed its caller in its last step - the gathered uint8 images on the host - as
+    out_dir/images.npy in float32 (the same values).  Above 64 MB, a fixed seeded sample of the flattened images instead
+    (out_dir/images_sample.npy: the same positions for the same shape, run after run)."""
+    x = np.asarray(img.cpu() if hasattr(img, "cpu") else img).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    if x.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "images.npy"), x)
+        return
+    flat = x.reshape(-1)
+    idx = np.sort(np.random.default_rng(0).choice(flat.size, size=DUMP_LIMIT_BYTES // 4, replace=False))
+    np.save(os.path.join(out_dir, "images_sample.npy"), flat[idx])
 
 
 def check_job_flags():

@@ -270,18 +270,24 @@ def test_weight_tables_match_reference_digests():
     assert h.hexdigest() == g["UNET_KEY_MAPPING"]["sha256"]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/stable_diffusion/ckpt_loader.py"), reason="reference not present")
 def test_weight_tables_equal_reference_tables():
-    import importlib.util
+    """The generated tables against the reference loader's own CKPT_MAPPING / UNET_KEY_MAPPING, as recorded from it
+    (tools/make_ref_live_goldens.py -> tests/golden/g13_ref_live.json: row counts and digests of every table it holds)."""
+    import sys
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from make_ref_live_goldens import key_mapping_digest, table_rows_digest
 
     from minsdtf_amd import weights as W
 
-    spec = importlib.util.spec_from_file_location("ref_ckpt", "/root/reference/stable_diffusion/ckpt_loader.py")
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    for kind in m.CKPT_MAPPING:   # (the CLIP text tables are built in text_encoder.py's constructors: test_loaders_cpu.py)
-        assert [(s.key, s.perm) for s in W.table(kind)] == [tuple(x) for x in m.CKPT_MAPPING[kind]]
-    assert {s.key: s.alt_key for s in W.table("civitai_model")} == m.UNET_KEY_MAPPING
+    g = gold("g13_ref_live.json")
+    assert set(g["ckpt_mapping"]) >= {"civitai_model", "decoder", "encoder", "controlnet", "hintnet"}
+    for kind, rec in g["ckpt_mapping"].items():   # (the CLIP text tables are built in text_encoder.py's constructors: test_loaders_cpu.py)
+        rows = [(s.key, s.perm) for s in W.table(kind)]
+        assert len(rows) == rec["count"], kind
+        assert table_rows_digest(rows) == rec["sha256"], kind
+    alt = {s.key: s.alt_key for s in W.table("civitai_model")}
+    assert len(alt) == g["unet_key_mapping"]["count"] and key_mapping_digest(alt) == g["unet_key_mapping"]["sha256"]
 
 
 def test_synthetic_checkpoint_roundtrip(tmp_path):

@@ -98,29 +98,28 @@ def test_pipeline_string_prompt_path(tmp_path):
     assert sd.encode_text("a cat", p).shape == (1, 77, 8)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/stable_diffusion/clip_tokenizer.py"), reason="reference not present")
 def test_tokenizer_and_weighting_equal_reference_live():
-    """Random strings / prompts through the reference's code (imported under the keras stub) and through ours."""
+    """Seeded random strings / prompts through ours against what the reference's SimpleTokenizer, parse_prompt_attention and
+    get_weighted_text_embeddings returned for them, recorded from it (tools/make_ref_live_goldens.py -> tests/golden/g13_ref_live.json,
+    g13_ref_live_text.npz; the name is from when the reference ran here)."""
     import make_goldens as mg
-
-    mg.install_keras_stub()
-    sys.path.insert(0, mg.REF)
-    import stable_diffusion.clip_tokenizer as ref_tok
-    import stable_diffusion.long_prompt_weighting as ref_lpw
+    import make_ref_live_goldens as rl
 
     from minsdtf_amd.text import SimpleTokenizer, get_weighted_text_embeddings, parse_prompt_attention
 
-    a, b = ref_tok.SimpleTokenizer(BPE), SimpleTokenizer(BPE)
-    rng = np.random.default_rng(5)
-    words = ["photo", "graph", "astronaut", "riding", "horse", "moon", "the", "cat's", "Hat", "42", "café", "!!", "...", "(", ")", "[", "]",
-             ":1.3)", "\\(", "&amp;", "beautiful", "masterpiece", ",", "\t", "  "]
-    for _ in range(200):
-        s = " ".join(rng.choice(words, size=rng.integers(1, 40)))
-        assert a.encode(s) == b.encode(s), s
-        assert ref_lpw.parse_prompt_attention(s) == parse_prompt_attention(s), s
-    for _ in range(25):
-        s = " ".join(rng.choice(words, size=rng.integers(1, 120)))
-        kw = dict(no_boseos_middle=bool(rng.integers(0, 2)), pad_token_id=a.end_of_text)
-        x = ref_lpw.get_weighted_text_embeddings(a, mg.FakeClipEmbedding(), mg.FakeTextEncoder(), s, **kw)
-        y = get_weighted_text_embeddings(b, mg.FakeClipEmbedding(), mg.FakeTextEncoder(), s, **kw)
+    g = json.load(open(os.path.join(GOLD, "g13_ref_live.json")))
+    arrays = np.load(os.path.join(GOLD, "g13_ref_live_text.npz"))
+    short, long = rl.random_prompts()
+    assert [c["prompt"] for c in g["prompts"]] == short and [(c["prompt"], c["no_boseos_middle"]) for c in g["weighted"]] == long
+    b = SimpleTokenizer(BPE)
+    for c in g["prompts"]:
+        s = c["prompt"]
+        assert b.encode(s) == c["tokens"], s
+        assert json.loads(json.dumps(parse_prompt_attention(s))) == c["parsed"], s
+    for i, c in enumerate(g["weighted"]):
+        assert c["pad_token_id"] == b.end_of_text
+        y = get_weighted_text_embeddings(b, mg.FakeClipEmbedding(), mg.FakeTextEncoder(), c["prompt"], no_boseos_middle=c["no_boseos_middle"],
+                                         pad_token_id=b.end_of_text)
+        x = arrays[f"weighted_{i}"]
+        assert np.asarray(y).dtype == x.dtype, c["prompt"]
         np.testing.assert_array_equal(x, y)

@@ -43,35 +43,35 @@ if [ "$WHAT" = mfma ]; then
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = headline ]; then
     pmc "" || exit $?
-    MSD_BENCH_KEEP_TRACE=$OUT/${TAG}_graph $T 500 python bench.py > $OUT/${TAG}_bench_n1.json 2> $OUT/bench_n1.err || exit 1
+    MSD_BENCH_KEEP_TRACE=$OUT/${TAG}_graph $T 500 python bench.py --full > $OUT/${TAG}_bench_n1.json 2> $OUT/bench_n1.err || exit 1
     echo "bench n1 done"; head -c 330 $OUT/${TAG}_bench_n1.json; echo
-    $T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline > $OUT/prof_bench.log 2>&1 || exit 2
+    $T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-roofline > $OUT/prof_bench.log 2>&1 || exit 2
     ST=$(ls $OUT/prof/*/*kernel_stats.csv 2>/dev/null | head -1)
     [ -n "$ST" ] && cp $ST $OUT/${TAG}_bench_kernel_stats.csv
     rm -rf $OUT/prof
     echo "rocprof stats done"
-    $T 300 rocprofv3 --kernel-trace --marker-trace --output-format csv -d $OUT/prof_phase -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --sync-phases > $OUT/prof_phase.log 2>&1 || exit 6
-    python tools/trace_summary.py $OUT/prof_phase $OUT/${TAG}_phase_summary.md "round ${TAG#r} (commit $COMMIT), python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --sync-phases" > /dev/null 2> $OUT/phase_sum.err || echo "phase summary failed (see phase_sum.err)"
+    $T 300 rocprofv3 --kernel-trace --marker-trace --output-format csv -d $OUT/prof_phase -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --sync-phases > $OUT/prof_phase.log 2>&1 || exit 6
+    python tools/trace_summary.py $OUT/prof_phase $OUT/${TAG}_phase_summary.md "round ${TAG#r} (commit $COMMIT), python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-roofline --sync-phases" > /dev/null 2> $OUT/phase_sum.err || echo "phase summary failed (see phase_sum.err)"
     rm -rf $OUT/prof_phase
     echo "phase trace done"
-    $T 200 python bench.py --batch-per-gpu 2 --steps 3 --no-cpu-baseline --no-roofline > $OUT/${TAG}_bench_b2.json 2>> $OUT/bench_cfg.err
+    $T 200 python bench.py --full --batch-per-gpu 2 --steps 3 --no-cpu-baseline --no-roofline > $OUT/${TAG}_bench_b2.json 2>> $OUT/bench_cfg.err
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = b4 ]; then      # C3's per-GPU shape: batch 4 (fused cond+uncond batch 8)
     pmc _b4 --batch 4 || exit $?
-    MSD_BENCH_KEEP_TRACE=$OUT/${TAG}_graph $T 400 python bench.py --batch-per-gpu 4 --steps 3 --no-cpu-baseline --quoted-traffic > $OUT/${TAG}_bench_b4.json 2>> $OUT/bench_cfg.err
+    MSD_BENCH_KEEP_TRACE=$OUT/${TAG}_graph $T 400 python bench.py --full --batch-per-gpu 4 --steps 3 --no-cpu-baseline --quoted-traffic > $OUT/${TAG}_bench_b4.json 2>> $OUT/bench_cfg.err
     echo "b4 done"
     # the serving choice for the GroupNorm form (MSD_GN_ROWS=4096: DESIGN.md 4.3), its own file
-    MSD_GN_ROWS=4096 $T 300 python bench.py --batch-per-gpu 4 --steps 3 --no-cpu-baseline --no-roofline > $OUT/${TAG}_bench_b4_gn_rows4096.json 2>> $OUT/bench_cfg.err
+    MSD_GN_ROWS=4096 $T 300 python bench.py --full --batch-per-gpu 4 --steps 3 --no-cpu-baseline --no-roofline > $OUT/${TAG}_bench_b4_gn_rows4096.json 2>> $OUT/bench_cfg.err
     echo "b4 gn_rows 4096 done"
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = 768 ]; then     # C4: 768x768, 50 steps
     pmc _768 --size 768 || exit $?
-    MSD_BENCH_KEEP_TRACE=$OUT/${TAG}_graph $T 600 python bench.py --size 768 --denoise-steps 50 --steps 2 --no-cpu-baseline --quoted-traffic > $OUT/${TAG}_bench_768.json 2>> $OUT/bench_cfg.err
+    MSD_BENCH_KEEP_TRACE=$OUT/${TAG}_graph $T 600 python bench.py --full --size 768 --denoise-steps 50 --steps 2 --no-cpu-baseline --quoted-traffic > $OUT/${TAG}_bench_768.json 2>> $OUT/bench_cfg.err
     echo "768 done"
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = controlnet ]; then   # C5's per-GPU shape: ControlNet, batch 1
     pmc _controlnet --controlnet || exit $?
-    MSD_BENCH_KEEP_TRACE=$OUT/${TAG}_graph $T 400 python bench.py --controlnet --steps 3 --no-cpu-baseline --quoted-traffic > $OUT/${TAG}_bench_controlnet.json 2>> $OUT/bench_cfg.err
+    MSD_BENCH_KEEP_TRACE=$OUT/${TAG}_graph $T 400 python bench.py --full --controlnet --steps 3 --no-cpu-baseline --quoted-traffic > $OUT/${TAG}_bench_controlnet.json 2>> $OUT/bench_cfg.err
     echo "controlnet done"
 fi
 echo "configs done"
