@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MSD_ABI_VERSION 11
+#define MSD_ABI_VERSION 12
 
 #define MSD_OK 0
 #define MSD_E_ARG (-1)      /* bad / inconsistent argument */
@@ -393,6 +393,37 @@ typedef struct MsdCfgStep {
 } MsdCfgStep;
 
 MSD_API int msd_cfg_step(const MsdCfgStep* p, msd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * msd_sampler_step (ABI 12) — classifier-free guidance + guidance rescale + a multistep / ancestral sampler step, fp32, one
+ * launch: msd_cfg_step's guidance, rescale, step counter (advance 0 / 1 / 2) and inpaint blend, with a general linear update
+ * that carries the previous evaluation's denoised estimate (minsdtf_amd/samplers.py: DPM++ 2M, DPM++ 2M SDE, Euler ancestral).
+ *   eps, latent, step_ptr, batch, n, num_steps, guidance, guidance_rescale, advance, inpaint_*: as msd_cfg_step.
+ *   coef:          fp32 [steps][8] = {alpha_i, sigma_i, c_x, c_D, c_P, c_z, 0, 0}:  e = CFG(+rescale) of eps,
+ *                  D = (x - sigma_i e) / alpha_i,  x' = c_x x + c_D D + c_P P + c_z z,  then P = D.
+ *                  The inpaint blend (inpaint_mask != NULL) re-noises inpaint_init with the row's alpha_i / sigma_i.
+ *   denoised_prev: fp32 [batch][n] = P, required: read only where the row's c_P != 0 (the first executed row has c_P = 0, so
+ *                  the buffer needs no initial value), written with D on every step.
+ *   step_noise:    fp32 [steps][batch][n] = the per-step N(0,1) draws z, or NULL (then c_z is ignored).
+ * Argument errors (a NULL eps / latent / coef / denoised_prev, bad dims, advance outside 0..2 or without step_ptr, an
+ * inpaint_mask without inpaint_init / inpaint_noise) return MSD_E_ARG without launching.
+ */
+typedef struct MsdSamplerStep {
+    const float* eps;
+    float* latent;
+    const float* coef;
+    int32_t* step_ptr;
+    int32_t batch, n, num_steps;
+    float guidance, guidance_rescale;
+    int32_t advance;
+    const float* inpaint_init;
+    const float* inpaint_noise;
+    const float* inpaint_mask;
+    const float* step_noise;
+    float* denoised_prev;
+} MsdSamplerStep;
+
+MSD_API int msd_sampler_step(const MsdSamplerStep* p, msd_stream_t stream);
 
 /* msd_add_bf16 — out = a + b elementwise on bf16. n % 8 == 0. */
 MSD_API int msd_add_bf16(const void* a, const void* b, void* out, int64_t n, msd_stream_t stream);

@@ -15,7 +15,7 @@ import weakref
 LIB_NAME = "libminsdtf_hip.so"
 # $MSD_HIP_LIB: another build of the same library (A/B runs of two kernel versions on one box); default = the in-tree build
 LIB_PATH = os.environ.get("MSD_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_QUICK_GELU = 0, 1, 2, 3
 OUT_BF16, OUT_F32, OUT_U8 = 0, 1, 2
@@ -91,6 +91,16 @@ class MsdCfgStep(C.Structure):
     ]
 
 
+class MsdSamplerStep(C.Structure):
+    _fields_ = [
+        ("eps", C.c_void_p), ("latent", C.c_void_p), ("coef", C.c_void_p), ("step_ptr", C.c_void_p),
+        ("batch", C.c_int32), ("n", C.c_int32), ("num_steps", C.c_int32), ("guidance", C.c_float),
+        ("guidance_rescale", C.c_float), ("advance", C.c_int32),
+        ("inpaint_init", C.c_void_p), ("inpaint_noise", C.c_void_p), ("inpaint_mask", C.c_void_p),
+        ("step_noise", C.c_void_p), ("denoised_prev", C.c_void_p),   # ABI 12: multistep / ancestral samplers
+    ]
+
+
 # every symbol include/minsdtf_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "msd_abi_version": (C.c_int, []),
@@ -112,6 +122,7 @@ SYMBOLS = {
     "msd_embedding_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p]),
     "msd_cfg_step": (C.c_int, [C.POINTER(MsdCfgStep), C.c_void_p]),
+    "msd_sampler_step": (C.c_int, [C.POINTER(MsdSamplerStep), C.c_void_p]),
     "msd_add_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_add_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -16,22 +16,31 @@ struct CfgArgs {
     const float* step_noise; const float* noise_coef;
 };
 
+// msd_sampler_step's arguments: msd_cfg_step's, plus the previous evaluation's denoised estimate P (fp32 [batch][n], read where
+// the row's c_P != 0, written every step); the row is 8 wide and carries the noise coefficient itself (noise_coef unused)
+struct SamplerArgs : CfgArgs {
+    float* dprev;
+};
+
 // One 1024-thread workgroup per sample.  eps (uncond / cond) is read ONCE into registers (up to NPT elements per
 // thread; larger latents take the re-reading loop) and the four moments go through one block reduction with the
 // same summation order as four separate ones (wave butterfly, then the 16 wave sums in wave order).
-template <int NPT>
-__global__ __launch_bounds__(1024) void cfg_step_kernel(const float* hot_eps, float* hot_latent, const float* hot_coef, int32_t* hot_step_ptr, int hot_batch, int hot_n,
-                                                       int hot_num_steps, float hot_guidance, const CfgArgs p) {
-    // (leading scalars: kernarg preload — the step index -> coefficient loads and the data loads start without the kernarg round trip)
+// MULTI = false: msd_cfg_step (rows {signal, noise, A, B}: x' = A x0 + B eps + noise_coef z).  MULTI = true: msd_sampler_step
+// (rows {alpha, sigma, c_x, c_D, c_P, c_z, 0, 0}: D = (x - sigma e) / alpha, x' = c_x x + c_D D + c_P P + c_z z, then P = D).
+// Both kernels below are this one body; the guidance / rescale moments, the register forms and the ticket are shared.
+template <int NPT, bool MULTI, typename Args>
+__device__ __forceinline__ void cfg_step_body(const float* hot_eps, float* hot_latent, const float* hot_coef, int32_t* hot_step_ptr, int hot_batch,
+                                              int hot_n, int hot_num_steps, float hot_guidance, const Args p) {
     __shared__ double red[16][4];
     const int b = blockIdx.x, t = threadIdx.x;
     const int step_raw = hot_step_ptr ? *hot_step_ptr : 0;
     int step = step_raw;
     if (step > hot_num_steps - 1) step = hot_num_steps - 1;
     if (step < 0) step = 0;
-    const float sr = hot_coef[step * 4 + 0], nr = hot_coef[step * 4 + 1];
-    const float ca = hot_coef[step * 4 + 2], cb = hot_coef[step * 4 + 3];   // x' = ca * x0 + cb * eps (+ cz * z)
-    const float cz = p.step_noise ? p.noise_coef[step] : 0.0f;
+    constexpr int W = MULTI ? 8 : 4;   // coefficient row width
+    const float sr = hot_coef[step * W + 0], nr = hot_coef[step * W + 1];
+    const float ca = hot_coef[step * W + 2], cb = hot_coef[step * W + 3];   // x' = ca * x0 + cb * eps (+ cz * z); MULTI: c_x, c_D
+    const float cz = MULTI ? hot_coef[step * W + 5] : (p.step_noise ? p.noise_coef[step] : 0.0f);
     const float* z = p.step_noise ? p.step_noise + ((size_t)step * hot_batch + b) * hot_n : nullptr;
     float* lat = hot_latent + (size_t)b * hot_n;
     const bool cfg = hot_guidance > 0.0f;
@@ -41,7 +50,8 @@ __global__ __launch_bounds__(1024) void cfg_step_kernel(const float* hot_eps, fl
     // its sample: as 4-byte accesses that was 48 wave-instructions per wave x 16 waves through one address unit, most of the
     // launch's 19.8 us at 64x64 (round 5)
     // (KEEP_L: the latent is prefetched with eps only where the registers allow it: 1024 threads = 128 registers per lane; at NPT = 36
-    //  three arrays spill, so the latent is read in the update pass instead)
+    //  three arrays spill, so the latent is read in the update pass instead.  MULTI's P and z are always read in the update pass:
+    //  two more prefetched arrays spill at NPT = 16 as well)
     constexpr bool KEEP_L = NPT <= 16;
     float ru[NPT > 0 ? NPT : 1], rc[NPT > 0 ? NPT : 1], rl[(NPT > 0 && KEEP_L) ? NPT : 1];
     if (NPT > 0) {   // everything this thread touches, issued up front
@@ -111,20 +121,66 @@ __global__ __launch_bounds__(1024) void cfg_step_kernel(const float* hot_eps, fl
         }
         return x;
     };
-    if (NPT > 0) {
+    if constexpr (!MULTI) {
+        if (NPT > 0) {
 #pragma unroll
-        for (int k = 0; k < NPT / 4; ++k) {
-            const int i = 4 * (t + k * 1024);
-            if (i < hot_n) {
-                float4 l;
-                if constexpr (KEEP_L) l = make_float4(rl[4 * k], rl[4 * k + 1], rl[4 * k + 2], rl[4 * k + 3]);
-                else l = *reinterpret_cast<const float4*>(lat + i);
-                *reinterpret_cast<float4*>(lat + i) = make_float4(value(i, ru[4 * k], rc[4 * k], l.x), value(i + 1, ru[4 * k + 1], rc[4 * k + 1], l.y),
-                                                                  value(i + 2, ru[4 * k + 2], rc[4 * k + 2], l.z), value(i + 3, ru[4 * k + 3], rc[4 * k + 3], l.w));
+            for (int k = 0; k < NPT / 4; ++k) {
+                const int i = 4 * (t + k * 1024);
+                if (i < hot_n) {
+                    float4 l;
+                    if constexpr (KEEP_L) l = make_float4(rl[4 * k], rl[4 * k + 1], rl[4 * k + 2], rl[4 * k + 3]);
+                    else l = *reinterpret_cast<const float4*>(lat + i);
+                    *reinterpret_cast<float4*>(lat + i) = make_float4(value(i, ru[4 * k], rc[4 * k], l.x), value(i + 1, ru[4 * k + 1], rc[4 * k + 1], l.y),
+                                                                      value(i + 2, ru[4 * k + 2], rc[4 * k + 2], l.z), value(i + 3, ru[4 * k + 3], rc[4 * k + 3], l.w));
+                }
             }
+        } else {
+            for (int i = t; i < hot_n; i += 1024) lat[i] = value(i, u[i], c[i], lat[i]);
         }
     } else {
-        for (int i = t; i < hot_n; i += 1024) lat[i] = value(i, u[i], c[i], lat[i]);
+        const float cp = hot_coef[step * W + 4];
+        const bool read_p = cp != 0.0f;   // (the first executed row has c_P = 0: P is not read, whatever the buffer holds)
+        float* dp = p.dprev + (size_t)b * hot_n;   // this sample's P
+        // x' = c_x x + c_D D + c_P P + c_z z (+ the inpaint blend); d receives D, the next row's P
+        auto value_multi = [&](int i, float cu, float cc, float l, float pv, float zv, float& d) {
+            const float e = cfg ? (cu + hot_guidance * (cc - cu)) * factor : cu;
+            d = (l - nr * e) / sr;
+            float x = ca * l + cb * d;
+            if (read_p) x += cp * pv;
+            if (z) x += cz * zv;
+            if (p.ip_mask) {
+                const float m = p.ip_mask[i];
+                const float org = sr * p.ip_init[i] + nr * p.ip_noise[(size_t)b * hot_n + i];
+                x = org * (1.0f - m) + x * m;
+            }
+            return x;
+        };
+        if (NPT > 0) {
+#pragma unroll
+            for (int k = 0; k < NPT / 4; ++k) {
+                const int i = 4 * (t + k * 1024);
+                if (i < hot_n) {
+                    float4 l, pv, zv;
+                    if constexpr (KEEP_L) l = make_float4(rl[4 * k], rl[4 * k + 1], rl[4 * k + 2], rl[4 * k + 3]);
+                    else l = *reinterpret_cast<const float4*>(lat + i);
+                    pv = read_p ? *reinterpret_cast<const float4*>(dp + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    zv = z ? *reinterpret_cast<const float4*>(z + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    float4 x, d;
+                    x.x = value_multi(i, ru[4 * k], rc[4 * k], l.x, pv.x, zv.x, d.x);
+                    x.y = value_multi(i + 1, ru[4 * k + 1], rc[4 * k + 1], l.y, pv.y, zv.y, d.y);
+                    x.z = value_multi(i + 2, ru[4 * k + 2], rc[4 * k + 2], l.z, pv.z, zv.z, d.z);
+                    x.w = value_multi(i + 3, ru[4 * k + 3], rc[4 * k + 3], l.w, pv.w, zv.w, d.w);
+                    *reinterpret_cast<float4*>(lat + i) = x;
+                    *reinterpret_cast<float4*>(dp + i) = d;
+                }
+            }
+        } else {
+            for (int i = t; i < hot_n; i += 1024) {
+                float d;
+                lat[i] = value_multi(i, u[i], c[i], lat[i], read_p ? dp[i] : 0.0f, z ? z[i] : 0.0f, d);
+                dp[i] = d;
+            }
+        }
     }
     if (p.advance_in_kernel && t == 0) {
         // every workgroup read *step_ptr at its start and takes its ticket here, at its end: the one that draws the last
@@ -135,6 +191,19 @@ __global__ __launch_bounds__(1024) void cfg_step_kernel(const float* hot_eps, fl
             __hip_atomic_store(hot_step_ptr, step_raw + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+
+template <int NPT>
+__global__ __launch_bounds__(1024) void cfg_step_kernel(const float* hot_eps, float* hot_latent, const float* hot_coef, int32_t* hot_step_ptr, int hot_batch, int hot_n,
+                                                       int hot_num_steps, float hot_guidance, const CfgArgs p) {
+    // (leading scalars: kernarg preload — the step index -> coefficient loads and the data loads start without the kernarg round trip)
+    cfg_step_body<NPT, false>(hot_eps, hot_latent, hot_coef, hot_step_ptr, hot_batch, hot_n, hot_num_steps, hot_guidance, p);
+}
+
+template <int NPT>
+__global__ __launch_bounds__(1024) void sampler_step_kernel(const float* hot_eps, float* hot_latent, const float* hot_coef, int32_t* hot_step_ptr, int hot_batch,
+                                                           int hot_n, int hot_num_steps, float hot_guidance, const SamplerArgs p) {
+    cfg_step_body<NPT, true>(hot_eps, hot_latent, hot_coef, hot_step_ptr, hot_batch, hot_n, hot_num_steps, hot_guidance, p);
 }
 
 __global__ void step_advance_kernel(int32_t* step_ptr) { *step_ptr = *step_ptr + 1; }
@@ -157,6 +226,34 @@ extern "C" int msd_cfg_step(const MsdCfgStep* q, msd_stream_t stream_) {
     if (vec4 && q->n <= 16 * 1024) hipLaunchKernelGGL(cfg_step_kernel<16>, dim3(q->batch), dim3(1024), 0, stream, a.eps, a.latent, a.coef, a.step_ptr, a.batch, a.n, a.num_steps, a.guidance, a);        // <= 64x64 latents
     else if (vec4 && q->n <= 36 * 1024) hipLaunchKernelGGL(cfg_step_kernel<36>, dim3(q->batch), dim3(1024), 0, stream, a.eps, a.latent, a.coef, a.step_ptr, a.batch, a.n, a.num_steps, a.guidance, a);   // 96x96
     else hipLaunchKernelGGL(cfg_step_kernel<0>, dim3(q->batch), dim3(1024), 0, stream, a.eps, a.latent, a.coef, a.step_ptr, a.batch, a.n, a.num_steps, a.guidance, a);
+    MSD_CHECK_LAUNCH();
+    if (q->advance == 1) {
+        hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, stream, q->step_ptr);
+        MSD_CHECK_LAUNCH();
+    }
+    return MSD_OK;
+}
+
+extern "C" int msd_sampler_step(const MsdSamplerStep* q, msd_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!q || !q->eps || !q->latent || !q->coef || !q->denoised_prev) MSD_FAIL(MSD_E_ARG, "sampler_step: null pointer");
+    if (q->batch <= 0 || q->n <= 0 || q->num_steps <= 0) MSD_FAIL(MSD_E_ARG, "sampler_step: bad dims");
+    if (q->advance && !q->step_ptr) MSD_FAIL(MSD_E_ARG, "sampler_step: advance needs step_ptr");
+    if (q->advance < 0 || q->advance > 2) MSD_FAIL(MSD_E_ARG, "sampler_step: advance takes 0, 1 or 2");
+    if (q->inpaint_mask && (!q->inpaint_init || !q->inpaint_noise)) MSD_FAIL(MSD_E_ARG, "sampler_step: inpaint_mask needs inpaint_init and inpaint_noise");
+    // (the register forms use 16-byte accesses to eps, the latent, P and z)
+    const bool vec4 = (q->n % 4) == 0 && q->n >= 4 && msd_aligned16(q->eps) && msd_aligned16(q->latent) && msd_aligned16(q->denoised_prev) &&
+                      (!q->step_noise || msd_aligned16(q->step_noise));
+    SamplerArgs a;
+    a.eps = q->eps; a.latent = q->latent; a.coef = q->coef; a.step_ptr = q->step_ptr;
+    a.advance_in_kernel = q->advance == 2 ? 1 : 0;
+    a.batch = q->batch; a.n = q->n; a.num_steps = q->num_steps; a.guidance = q->guidance; a.rescale = q->guidance_rescale;
+    a.ip_init = q->inpaint_init; a.ip_noise = q->inpaint_noise; a.ip_mask = q->inpaint_mask;
+    a.step_noise = q->step_noise; a.noise_coef = nullptr;
+    a.dprev = q->denoised_prev;
+    if (vec4 && q->n <= 16 * 1024) hipLaunchKernelGGL(sampler_step_kernel<16>, dim3(q->batch), dim3(1024), 0, stream, a.eps, a.latent, a.coef, a.step_ptr, a.batch, a.n, a.num_steps, a.guidance, a);
+    else if (vec4 && q->n <= 36 * 1024) hipLaunchKernelGGL(sampler_step_kernel<36>, dim3(q->batch), dim3(1024), 0, stream, a.eps, a.latent, a.coef, a.step_ptr, a.batch, a.n, a.num_steps, a.guidance, a);
+    else hipLaunchKernelGGL(sampler_step_kernel<0>, dim3(q->batch), dim3(1024), 0, stream, a.eps, a.latent, a.coef, a.step_ptr, a.batch, a.n, a.num_steps, a.guidance, a);
     MSD_CHECK_LAUNCH();
     if (q->advance == 1) {
         hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, stream, q->step_ptr);

@@ -178,6 +178,20 @@ def cfg_step(*, eps, latent, coef, step_ptr, batch, n, num_steps, guidance, guid
     return Call(lib.msd_cfg_step, (C.byref(s),), name, keep=s)
 
 
+def sampler_step(*, eps, latent, coef, step_ptr, denoised_prev, batch, n, num_steps, guidance, guidance_rescale, advance=True,
+                 inpaint_init=None, inpaint_noise=None, inpaint_mask=None, step_noise=None, name="sampler_step") -> Call:
+    """msd_sampler_step: coef fp32 [num_steps][8] (minsdtf_amd/samplers.py), denoised_prev fp32 [batch][n] (read where the row's
+    c_P != 0, written every step), step_noise fp32 [num_steps][batch][n] or None."""
+    lib = _lib.load()
+    s = _lib.MsdSamplerStep()
+    s.eps, s.latent, s.coef, s.step_ptr = _p(eps), _p(latent), _p(coef), _p(step_ptr)
+    s.inpaint_init, s.inpaint_noise, s.inpaint_mask = _p(inpaint_init), _p(inpaint_noise), _p(inpaint_mask)
+    s.step_noise, s.denoised_prev = _p(step_noise), _p(denoised_prev)
+    s.batch, s.n, s.num_steps = batch, n, num_steps
+    s.guidance, s.guidance_rescale, s.advance = float(guidance), float(guidance_rescale), int(advance)   # 2: in-kernel ({step, ticket})
+    return Call(lib.msd_sampler_step, (C.byref(s),), name, keep=s)
+
+
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:
     lib = _lib.load()
     return Call(lib.msd_add_bf16, (_p(a), _p(b), _p(out), n), name)

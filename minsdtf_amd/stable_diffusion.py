@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib, engine, ops
+from . import samplers as smp
 from . import weights as wtab
 from .models import (ControlNet, DiffusionModel, HintNet, ImageDecoder, ImageEncoder, TextClipEmbedding, TextEncoder, _BoundPlan,
                      _skip_hw, default_device)
@@ -67,8 +68,14 @@ class DenoiseEngine:
 
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
-                 use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False):
+                 use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
+                 sampler=None):
         unet._require_weights()
+        # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
+        # the 8-wide coefficient rows, the previous denoised estimate and (stochastic samplers) per-step draws on the device
+        self.sampler = smp.parse(sampler)
+        if self.sampler is not None and tcd:
+            raise ValueError("a sampler cannot be combined with the TCD sampler")
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
         self.use_graph = use_graph
@@ -108,7 +115,7 @@ class DenoiseEngine:
         self._sched_key = None       # schedule whose coefficient / time-embedding tables are on the device
         self._step_init: Dict[int, torch.Tensor] = {}
         self.latent = torch.zeros(B, h, w, 4, dtype=torch.float32, device=dev)
-        self.coef = torch.zeros(num_steps, 4, dtype=torch.float32, device=dev)
+        self.coef = torch.zeros(num_steps, smp.ROW if self.sampler is not None else 4, dtype=torch.float32, device=dev)
         self.temb_in = torch.zeros(num_steps, 320, dtype=torch.float32, device=dev)
         total_u = sum(c for _, c in engine.resblock_names(False))
         table_u = prep_t.alloc(num_steps * total_u * 4)
@@ -187,12 +194,22 @@ class DenoiseEngine:
                             "mask": torch.ones(n, dtype=torch.float32, device=dev)}
         ip = self.inpaint or {}
         # TCD sampler: one N(0,1) draw per step and sample, made on the host in the reference's order (prepare())
-        self.step_noise = torch.zeros(num_steps, B, n, dtype=torch.float32, device=dev) if tcd else None
+        stochastic = tcd or (self.sampler is not None and self.sampler.stochastic)
+        self.step_noise = torch.zeros(num_steps, B, n, dtype=torch.float32, device=dev) if stochastic else None
         self.noise_coef = torch.zeros(num_steps, dtype=torch.float32, device=dev) if tcd else None
-        tail.rec(ops.cfg_step, eps=self.eps, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr, batch=B, n=n,
-                 num_steps=num_steps, guidance=guidance, guidance_rescale=guidance_rescale, advance=2,
-                 inpaint_init=ip.get("init"), inpaint_noise=ip.get("noise"), inpaint_mask=ip.get("mask"),
-                 step_noise=self.step_noise, noise_coef=self.noise_coef)
+        self.denoised_prev = None
+        if self.sampler is None:
+            tail.rec(ops.cfg_step, eps=self.eps, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr, batch=B, n=n,
+                     num_steps=num_steps, guidance=guidance, guidance_rescale=guidance_rescale, advance=2,
+                     inpaint_init=ip.get("init"), inpaint_noise=ip.get("noise"), inpaint_mask=ip.get("mask"),
+                     step_noise=self.step_noise, noise_coef=self.noise_coef)
+        else:
+            # (P needs no initial value: the first executed row has c_P = 0 and the kernel does not read it there)
+            self.denoised_prev = torch.zeros(B, n, dtype=torch.float32, device=dev)
+            tail.rec(ops.sampler_step, eps=self.eps, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr,
+                     denoised_prev=self.denoised_prev, batch=B, n=n, num_steps=num_steps, guidance=guidance,
+                     guidance_rescale=guidance_rescale, advance=2, inpaint_init=ip.get("init"), inpaint_noise=ip.get("noise"),
+                     inpaint_mask=ip.get("mask"), step_noise=self.step_noise)
         if self.cn_plan is not None:
             self.cn_plan.finalize()   # (first: the main plan's zero convs record addresses of its feature maps)
             self._join = step.marks["controls"]
@@ -311,11 +328,13 @@ class DenoiseEngine:
             callback(i + 1)
 
     def prepare(self, contexts: Dict[str, np.ndarray], noise: np.ndarray, scheduler: Scheduler, timesteps,
-                start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None) -> None:
+                start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None) -> None:
         """Upload the per-call inputs and run the preparation plan.  Every array may be a host array or a (device) tensor.
         inpaint = (init_latent (1,h,w,4), noise (B,h,w,4), latent mask (h,w) or (h,w,1)) for an engine built with
         inpaint=True; step_noise = (B, num_steps, h*w*4) TCD draws made by the caller (sharded runs: the slice of the
-        draws for the global batch) instead of the draws made here."""
+        draws for the global batch) instead of the draws made here.  An engine built with a sampler takes its
+        samplers.Schedule as `sampler` (the coefficient rows are built here for `start_index`) and, for the stochastic samplers,
+        its draws as `step_noise` (B, num_steps, ...) (drawn here from numpy's global stream when None)."""
         if self.inpaint is not None:
             init, ip_noise, mask = inpaint
             self.inpaint["init"].copy_(_f32_tensor(init).reshape(-1))
@@ -335,11 +354,20 @@ class DenoiseEngine:
         # the schedule's tables: uploaded when the schedule changes, not per call (pageable host -> device copies make the
         # host wait for the stream, which keeps it from queueing this job behind the previous one's last kernels)
         # (keyed by the table's VALUES: a scheduler with other betas / final alpha / eta on the same timesteps is another schedule)
-        coef = scheduler.coefficient_table()
-        sched_key = (tuple(int(t) for t in scheduler.timesteps), bool(getattr(scheduler, "active_tcd", False)), coef.tobytes())
+        if self.sampler is not None:
+            if sampler is None or sampler.spec.name != self.sampler.name or sampler.num_steps != self.num_steps:
+                raise ValueError(f"this engine runs the {self.sampler.name} sampler over {self.num_steps} steps: pass its Schedule")
+            # (the rows depend on the start index: the first executed row never reads P)
+            coef = smp.coefficient_table(sampler, int(start_index))
+            taus = [float(t) for t in sampler.timesteps]   # fractional for Karras: the time embedding is taken at the float t
+            sched_key = ("sampler", sampler.spec.name, sampler.timesteps.tobytes(), int(start_index), coef.tobytes())
+        else:
+            coef = scheduler.coefficient_table()
+            taus = [int(t) for t in scheduler.timesteps]
+            sched_key = (tuple(int(t) for t in scheduler.timesteps), bool(getattr(scheduler, "active_tcd", False)), coef.tobytes())
         if self._sched_key != sched_key:
             self.coef.copy_(torch.from_numpy(coef))
-            temb = np.concatenate([get_timestep_embedding(int(t), 1) for t in scheduler.timesteps], axis=0)
+            temb = np.concatenate([get_timestep_embedding(t, 1) for t in taus], axis=0)
             self.temb_in.copy_(torch.from_numpy(np.ascontiguousarray(temb, dtype=np.float32)))
             self.prep_t.run(torch.cuda.current_stream().cuda_stream)
             self._sched_key = sched_key
@@ -347,7 +375,11 @@ class DenoiseEngine:
         if init is None:
             init = self._step_init[int(start_index)] = torch.tensor([int(start_index), 0], dtype=torch.int32, device=self.step_ptr.device)
         self.step_ptr.copy_(init)   # {first step, ticket 0}: device -> device
-        if self.step_noise is not None:
+        if self.step_noise is not None and self.sampler is not None:
+            if step_noise is None:
+                step_noise = smp.draw_step_noise(self.B, self.num_steps, self.h, self.w)
+            self.step_noise.copy_(_f32_tensor(step_noise).reshape(self.B, self.num_steps, -1).transpose(0, 1))
+        elif self.step_noise is not None:
             # scheduler.py:301 draws np.random.randn(*latent.shape) once per executed step except the last
             self.noise_coef.copy_(torch.from_numpy(scheduler.noise_coefficients()))
             if step_noise is not None:
@@ -642,14 +674,18 @@ class StableDiffusionBase:
     def generate_image(self, encoded_text, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        diffusion_noise=None, seed=None, negative_embedding=None, control_net_image=None, inpaint_mask=None,
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
-                       callback=None, host_loop=False, return_latent=False):
-        """Reference :317-486.  With ``self.shard_batch = True`` under an initialised torch.distributed process group
-        `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
+                       callback=None, host_loop=False, return_latent=False, sampler=None):
+        """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
+        "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
+        With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
         rank denoises + decodes its contiguous slice and every rank returns the whole gathered batch (minsdtf_amd/dist.py).
         Default (False): the reference's meaning, this process runs all `batch_size` samples."""
         if diffusion_noise is not None and seed is not None:
             raise ValueError("`diffusion_noise` and `seed` should not both be passed to `generate_image`. `seed` is only "
                              "used to generate diffusion noise when it's not already user-specified.")
+        spec = smp.parse(sampler)   # (ValueError for an unknown name)
+        if spec is not None and self.active_tcd:
+            raise ValueError(f"sampler={sampler!r} on a TCD pipeline (active_tcd=True): the TCD sampler is the only one it runs")
         B = batch_size
         context = self._batch_of(encoded_text, B, 2)
         unconditional_context = self._negative_context(negative_prompt, negative_embedding, B)
@@ -677,6 +713,13 @@ class StableDiffusionBase:
         inpainting = latent_mask is not None and encoded is not None
         blend_pixels = pixel_mask is not None and picture01 is not None
         start_index = num_steps - run_steps  # position of the first executed timestep in the descending schedule
+        sched = sampler_z = None
+        if spec is not None:
+            sched = smp.schedule(spec, self.scheduler, num_steps)
+            if encoded is not None:   # (k-diffusion's entry point: the first executed evaluation's own alpha / sigma)
+                start_latent = sched.entry_latent(start_index, encoded, noise)
+            if spec.stochastic:   # the per-step draws of the GLOBAL batch, sample-major
+                sampler_z = smp.draw_step_noise(B, num_steps, noise.shape[1], noise.shape[2], seed)
         hint = self._hint_batch(control_net_image, B)
         g, phi = float(unconditional_guidance_scale), float(guidance_rescale)
 
@@ -687,6 +730,12 @@ class StableDiffusionBase:
                 decoded = picture * (1.0 - mask) + decoded * mask
             return np.clip(decoded * 255.0, 0, 255).astype("uint8")
 
+        if host_loop and spec is not None:
+            latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
+                                             sampler_z, (encoded, noise, latent_mask[0]) if inpainting else None)
+            if return_latent:
+                return np.asarray(latent, dtype=np.float32)
+            return finish(self.image_decoder.predict_on_batch(latent))
         if host_loop:
             latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending,
                                      (encoded, noise, latent_mask[0]) if inpainting else None)
@@ -714,6 +763,8 @@ class StableDiffusionBase:
             for i in range(start_index, num_steps - 1):
                 zs[i] = np.random.randn(*noise.shape).astype(np.float32).reshape(B, -1)
             per_sample["tcd"] = np.ascontiguousarray(zs.transpose(1, 0, 2))
+        if sampler_z is not None:
+            per_sample["sampler_z"] = sampler_z.reshape(B, num_steps, -1)
         dev = getattr(self, "device", None) or self.diffusion_model.device
         names = list(per_sample) + list(shared)
 
@@ -724,8 +775,13 @@ class StableDiffusionBase:
             hint_b = a.get("hint")
             ip = (a["encoded"], a["noise"], a["mask"]) if inpainting else None
             tcd_z = a.get("tcd")
-            eng = self._engine(b, c.shape[1], u.shape[1], num_steps, g, phi, hint_b is not None, ip is not None)
-            eng.prepare(eng.contexts(u, c), z, self.scheduler, self.scheduler.timesteps, start_index, hint_b, ip, step_noise=tcd_z)
+            if spec is None:
+                eng = self._engine(b, c.shape[1], u.shape[1], num_steps, g, phi, hint_b is not None, ip is not None)
+                eng.prepare(eng.contexts(u, c), z, self.scheduler, self.scheduler.timesteps, start_index, hint_b, ip, step_noise=tcd_z)
+            else:
+                eng = self._engine(b, c.shape[1], u.shape[1], num_steps, g, phi, hint_b is not None, ip is not None, sampler=spec.name)
+                eng.prepare(eng.contexts(u, c), z, self.scheduler, self.scheduler.timesteps, start_index, hint_b, ip,
+                            step_noise=a.get("sampler_z"), sampler=sched)
             eng.run_steps(run_steps, callback)
             if return_latent:
                 return eng.latent
@@ -746,12 +802,12 @@ class StableDiffusionBase:
             engine.check_gn_sync(flags.cpu(), device=dev, group_wide=sharded)
         return host
 
-    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False) -> DenoiseEngine:
+    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None) -> DenoiseEngine:
         # the engine's plans (and captured hipGraphs) hold raw addresses of the packed weights: a set_weights() /
         # load_synthetic() / LoRA reload on any of the models it was built from must retire it
         wver = (self.diffusion_model.weights_version,) + ((self.control_net.weights_version, self.hint_net.weights_version)
                                                            if control else ())
-        key = (B, tc, tu, steps, g, phi, control, self.denoise_streams, inpaint, self.active_tcd, wver, engine.GN_EPOCH)
+        key = (B, tc, tu, steps, g, phi, control, self.denoise_streams, inpaint, self.active_tcd, wver, engine.GN_EPOCH, sampler)
         eng = self._engines.get(key)
         if eng is None:
             # one resident engine (its arenas are the big allocations): the old one goes BEFORE the new one is built, so that a
@@ -767,7 +823,7 @@ class StableDiffusionBase:
             eng = DenoiseEngine(self.diffusion_model, B, tc, tu, steps, g, phi,
                                 control_net=self.control_net if control else None,
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
-                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd)
+                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=sampler)
             self._engines = {key: eng}  # one resident engine: its arenas are the big allocations
         return eng
 
@@ -781,24 +837,7 @@ class StableDiffusionBase:
         for _index, timestep in list(enumerate(timesteps))[::-1]:
             latent_prev = latent
             t_emb = get_timestep_embedding(timestep, batch_size)
-            if g > 0.0:
-                if hint is not None:
-                    uc = self.control_net.predict_on_batch([latent, t_emb, unconditional_context, hint])
-                    u = self.diffusion_model.predict_on_batch([latent, t_emb, unconditional_context] + list(uc))
-                    cc = self.control_net.predict_on_batch([latent, t_emb, context, hint])
-                    c = self.diffusion_model.predict_on_batch([latent, t_emb, context] + list(cc))
-                else:
-                    u = self.diffusion_model.predict_on_batch([latent, t_emb, unconditional_context])
-                    c = self.diffusion_model.predict_on_batch([latent, t_emb, context])
-                latent = u + g * (c - u)
-                if phi > 0.0:
-                    latent = rescale_noise_cfg(latent, c, guidance_rescale=phi)
-            else:
-                if hint is not None:
-                    cc = self.control_net.predict_on_batch([latent, t_emb, context, hint])
-                    latent = self.diffusion_model.predict_on_batch([latent, t_emb, context] + list(cc))
-                else:
-                    latent = self.diffusion_model.predict_on_batch([latent, t_emb, context])
+            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint)
             latent = self.scheduler.step(latent, timestep, latent_prev)
             if inpaint is not None:   # reference :469-475
                 init_latent, noise, latent_mask = inpaint
@@ -809,6 +848,47 @@ class StableDiffusionBase:
             if callback is not None:
                 callback(iteration)
         return latent
+
+    def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint):
+        """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467)."""
+        if g > 0.0:
+            if hint is not None:
+                uc = self.control_net.predict_on_batch([latent, t_emb, unconditional_context, hint])
+                u = self.diffusion_model.predict_on_batch([latent, t_emb, unconditional_context] + list(uc))
+                cc = self.control_net.predict_on_batch([latent, t_emb, context, hint])
+                c = self.diffusion_model.predict_on_batch([latent, t_emb, context] + list(cc))
+            else:
+                u = self.diffusion_model.predict_on_batch([latent, t_emb, unconditional_context])
+                c = self.diffusion_model.predict_on_batch([latent, t_emb, context])
+            e = u + g * (c - u)
+            if phi > 0.0:
+                e = rescale_noise_cfg(e, c, guidance_rescale=phi)
+            return e
+        if hint is not None:
+            cc = self.control_net.predict_on_batch([latent, t_emb, context, hint])
+            return self.diffusion_model.predict_on_batch([latent, t_emb, context] + list(cc))
+        return self.diffusion_model.predict_on_batch([latent, t_emb, context])
+
+    def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
+                           inpaint=None):
+        """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`."""
+        batch_size = latent.shape[0]
+        hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
+        tab = smp.rows(sched, start)
+        x = np.asarray(latent, dtype=np.float64)
+        prev = None
+        for iteration, i in enumerate(range(start, sched.num_steps), start=1):
+            t_emb = get_timestep_embedding(float(sched.timesteps[i]), batch_size)
+            e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint)
+            z = step_noise[:, i] if step_noise is not None else None
+            x, prev = smp.host_step(tab[i], x, e, prev, z)
+            if inpaint is not None:   # the row's own alpha / sigma, as in the device kernel
+                init_latent, noise, latent_mask = inpaint
+                origin = tab[i, 0] * np.repeat(init_latent, batch_size, axis=0) + tab[i, 1] * np.asarray(noise, dtype=np.float64)
+                x = origin * (1.0 - latent_mask[None]) + x * latent_mask[None]
+            if callback is not None:
+                callback(iteration)
+        return x
 
 
 class StableDiffusion(StableDiffusionBase):
