@@ -425,6 +425,47 @@ typedef struct MsdSamplerStep {
 
 MSD_API int msd_sampler_step(const MsdSamplerStep* p, msd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * msd_lora_merge — LoRA switch at run time: rewrites packed weight matrices IN PLACE (same tensors, same layouts), so launch
+ * plans and captured graphs that hold their addresses stay valid (minsdtf_amd/lora.py; DESIGN.md "LoRA switch").  One launch
+ * over `num_jobs` job descriptors; per job, for every logical element (n, k) of an N x K matrix:
+ *   v   = master[n][k] + sum_j up[n][j] * down[j][k]      fp32, j = 0 .. rank-1 in order, fused multiply-add; rank 0: v = master
+ *   v   = (v * rowscale[n]) * colscale[k]               each factor optional (NULL), in this order, no contraction
+ *   out = bf16 (round to nearest even) or fp32 of v
+ * stored at destination row r = (rowmap ? rowmap[n] : n) + row_off and column c = col_off + k of an out_rows x out_cols matrix:
+ *   layout 0: rows, out[r * ld + c];  1: chunk-major [out_cols/64][out_rows][64] (bf16 only);
+ *   layout 2: transposed rows out[c * out_rows + r] (fp32 only: the direct-conv form of a Dense);
+ * and, when out_frag != NULL, into the fragment-major copy of the same bf16 matrix (MsdConvGemm.w_layout = 2, packing.fragment_major;
+ * out_rows % 16 == 0, out_cols % 64 == 0); when colsum != NULL (bf16, the job spans whole destination rows) colsum[r] = fp32 of the
+ * fp64 sum of the row's ROUNDED values (the .lncs vector of a LayerNorm fold).  Rows whose rowmap entry falls outside
+ * [0, out_rows) are not written.  Deterministic: every element and every row sum has one fixed evaluation order.
+ * `jobs` is the host array (validated here: argument errors return MSD_E_ARG before anything is launched); `jobs_dev` is a device
+ * copy of the same entries, which the kernel reads.  first_block = sum over the earlier jobs of ceil(n / 8).  rank <= 512.
+ */
+typedef struct MsdLoraJob {
+    const float* master;     /* [n][master_ld] fp32 */
+    const float* up;         /* [n][rank] fp32 (NULL when rank == 0) */
+    const float* down;       /* [rank][k] fp32 (NULL when rank == 0) */
+    const float* rowscale;   /* [n] or NULL */
+    const float* colscale;   /* [k] or NULL */
+    const int32_t* rowmap;   /* [n] or NULL */
+    void* out;
+    void* out_frag;          /* bf16 fragment-major copy, or NULL */
+    float* colsum;           /* [out_rows] fp32, or NULL */
+    int32_t n, k, rank, master_ld;
+    int32_t layout, out_dtype, ld;
+    int32_t out_rows, out_cols, row_off, col_off;
+    int32_t first_block;
+} MsdLoraJob;
+
+typedef struct MsdLoraMerge {
+    const MsdLoraJob* jobs;      /* host array */
+    const MsdLoraJob* jobs_dev;  /* device copy */
+    int32_t num_jobs;
+} MsdLoraMerge;
+
+MSD_API int msd_lora_merge(const MsdLoraMerge* p, msd_stream_t stream);
+
 /* msd_add_bf16 — out = a + b elementwise on bf16. n % 8 == 0. */
 MSD_API int msd_add_bf16(const void* a, const void* b, void* out, int64_t n, msd_stream_t stream);
 /* msd_add_f32_bf16 — out = bf16(a + b), a / out bf16, b fp32, summed in fp32 (may run in place, out == a).  The ControlNet

@@ -101,6 +101,23 @@ class MsdSamplerStep(C.Structure):
     ]
 
 
+class MsdLoraJob(C.Structure):
+    _fields_ = [
+        ("master", C.c_void_p), ("up", C.c_void_p), ("down", C.c_void_p), ("rowscale", C.c_void_p), ("colscale", C.c_void_p),
+        ("rowmap", C.c_void_p), ("out", C.c_void_p), ("out_frag", C.c_void_p), ("colsum", C.c_void_p),
+        ("n", C.c_int32), ("k", C.c_int32), ("rank", C.c_int32), ("master_ld", C.c_int32),
+        ("layout", C.c_int32), ("out_dtype", C.c_int32), ("ld", C.c_int32),
+        ("out_rows", C.c_int32), ("out_cols", C.c_int32), ("row_off", C.c_int32), ("col_off", C.c_int32),
+        ("first_block", C.c_int32),
+    ]
+
+
+class MsdLoraMerge(C.Structure):
+    _fields_ = [("jobs", C.c_void_p), ("jobs_dev", C.c_void_p), ("num_jobs", C.c_int32)]
+
+
+LORA_ROWS_PER_BLOCK = 8   # csrc/lora.hip LR_ROWS: MsdLoraJob.first_block counts workgroups of this many rows
+
 # every symbol include/minsdtf_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "msd_abi_version": (C.c_int, []),
@@ -123,6 +140,7 @@ SYMBOLS = {
                                     C.c_int32, C.c_void_p, C.c_void_p]),
     "msd_cfg_step": (C.c_int, [C.POINTER(MsdCfgStep), C.c_void_p]),
     "msd_sampler_step": (C.c_int, [C.POINTER(MsdSamplerStep), C.c_void_p]),
+    "msd_lora_merge": (C.c_int, [C.POINTER(MsdLoraMerge), C.c_void_p]),
     "msd_add_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_add_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

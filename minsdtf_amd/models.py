@@ -82,6 +82,10 @@ class HipModel:
         # bumped by every set_weights(): launch plans hold raw device addresses of the packed weights, so whatever caches
         # a plan built on this model (its own _plans, StableDiffusion._engines) keys on it
         self.weights_version = 0
+        # LoRA switch (lora.py): off unless the owner asks for it before the weights are set; then set_weights also keeps the fp32
+        # masters the merge starts from
+        self.lora_switch = False
+        self._lora = None
 
     def _table_kw(self) -> dict:
         return {}
@@ -105,15 +109,46 @@ class HipModel:
             if tuple(a.shape) != tuple(s.shape):
                 raise ValueError(f"{self.name}: {s.name} has shape {a.shape}, expected {s.shape}")
             named[(s.name, s.kind)] = a
+        self._lora = None
+        self._ffproj_stash = {} if getattr(self, "lora_switch", False) else None
         W = packing.PackedWeights(self._pack(named))
         if engine.W_CHUNK_MAJOR:
             # the bf16 matrices the MFMA kernels read (msd_conv_gemm, msd_cross_attention_q: keys *.w / *.lnw) are stored
             # chunk-major; W records which ones, and the emitters pass that per-key layout to the op (Emitter.conv)
             for k in [k for k, t in W.items() if t.dtype == torch.bfloat16 and t.dim() == 2 and k.endswith((".w", ".lnw"))]:
                 W.to_chunk_major(k)
+        if self._ffproj_stash is not None:   # (lora_switch)
+            from . import lora
+
+            self._lora = lora.MergeBase(self, named, W, self._ffproj_stash)
+        self._ffproj_stash = None
         self._W = W
         self.weights_version += 1
         self._plans.clear()
+
+    @property
+    def lora_version(self) -> int:
+        """Bumped by every LoRA switch of these packed weights (shared with the models that share_weights them); the addresses do
+        not change, so weights_version does not."""
+        base = getattr(self, "_lora", None)
+        return 0 if base is None else base.version
+
+    def validate_loras(self, factor_sets) -> None:
+        """Raise (RuntimeError without the switch, ValueError for a factor that does not fit) before any device write."""
+        if getattr(self, "_lora", None) is None:
+            raise RuntimeError(f"{self.name}: LoRA switching needs weights set with lora_switch=True "
+                               "(StableDiffusion(lora_switch=True)); weights adopted through load_packed cannot be switched")
+        self._lora.validate(factor_sets, self.name)
+
+    def set_loras(self, factor_sets) -> bool:
+        """Merge [(lora.Factors, scale), ...] into the packed weights in place (replacing the active set; [] = the base), stream-
+        ordered on the current stream, then synchronise.  Returns whether any packed tensor was rewritten."""
+        self.validate_loras(factor_sets)
+        written = self._lora.apply(self._W, factor_sets)
+        if written:
+            self._lora.version += 1
+        torch.cuda.synchronize(self.device)
+        return bool(written)
 
     def share_weights(self, other: "HipModel") -> None:
         """Use `other`'s packed device weights (same network kind, e.g. one checkpoint served at two image sizes):
@@ -123,6 +158,7 @@ class HipModel:
         if other.device != self.device:   # the plans hold raw device addresses
             raise ValueError(f"{self.name}: share_weights across devices ({other.device} -> {self.device})")
         self._W = other._W
+        self._lora = getattr(other, "_lora", None)   # (one packed image, one master: the sharing models switch together)
         self.weights_version += 1
         self._plans.clear()
 
@@ -136,11 +172,15 @@ class HipModel:
         """The packed device weights of this model -> `path` (packing.save_packed; `meta`: whatever identifies the
         checkpoint, compared by load_packed)."""
         self._require_weights()
+        base = getattr(self, "_lora", None)
+        if base is not None and base.active:   # merged weights are not the checkpoint's: never adopted as the base
+            meta = dict(meta, lora_version=base.version)
         packing.save_packed(self._W, path, dict(meta, kind=self.kind, table_kw=self._table_kw()))
 
     def load_packed(self, path: str, **meta) -> None:
         """Adopt weights another process packed (save_packed): no generation, no packing pass, one upload."""
         self._W = packing.load_packed(path, self.device, dict(meta, kind=self.kind, table_kw=self._table_kw()))
+        self._lora = None
         self.weights_version += 1
         self._plans.clear()
 
@@ -237,6 +277,8 @@ class HipModel:
                 continue
             w2d, wpd = np.asarray(w2, np.float64), np.asarray(wp, np.float64).reshape(wp.shape[-2], wp.shape[-1])
             wcat = np.concatenate([w2d @ wpd, wpd], axis=0)                       # (4C + C, C) as (in, out)
+            if getattr(self, "_ffproj_stash", None) is not None:   # the LoRA merge's master of the top block (lora.MergeBase)
+                self._ffproj_stash[att] = wcat[: w2d.shape[0]]
             W[att + ".ffproj.w"] = packing.pack_dense(wcat.astype(np.float32), d)
             W[att + ".ffproj.b"] = packing.dev_f32((np.asarray(b2, np.float64) @ wpd + np.asarray(bp, np.float64)).astype(np.float32), d)
         # ResBlock conv2 + conv_shortcut (diffusion_model.py:34-38,50) as one contraction: W = [conv2 taps | shortcut], b = b2 + bs
@@ -334,8 +376,9 @@ class DiffusionModel(HipModel):
     kind = "civitai_model"
 
     def __init__(self, img_height=512, img_width=512, apply_control_net=False, name=None, ckpt_path=None, lora_dict=None,
-                 device=None):
+                 device=None, lora_switch=False):
         super().__init__(name or "diffusion_model", device)
+        self.lora_switch = lora_switch
         if img_height % 64 or img_width % 64:
             raise ValueError("img_height / img_width must be multiples of 64 (three stride-2 levels after the /8 VAE)")
         self.h, self.w = img_height // 8, img_width // 8
@@ -627,13 +670,14 @@ class TextEncoder(HipModel):
     kind = "text_encoder"
 
     def __init__(self, max_length=77, embed_dim=768, num_heads=12, num_layers=12, clip_skip=-2, name=None, ckpt_path=None,
-                 lora_dict=None, device=None):
+                 lora_dict=None, device=None, lora_switch=False):
         if (embed_dim, num_heads, num_layers) != (wtab.CLIP_DIM, wtab.CLIP_HEADS, wtab.CLIP_LAYERS):
             raise ValueError("only the SD1.5 CLIP ViT-L/14 text model geometry is built (768, 12 heads, 12 layers)")
         if not -num_layers <= clip_skip <= -1:
             raise ValueError("clip_skip must be in [-num_layers, -1]")
         self.clip_skip, self.max_length = clip_skip, max_length
         super().__init__(name or "text_encoder", device)
+        self.lora_switch = lora_switch
         self._maybe_load(ckpt_path, lora_dict)
 
     def _table_kw(self):

@@ -228,3 +228,41 @@ def replicate(*, src, dst, nbytes, copies, name="replicate") -> Call:
 def memset_zero(*, ptr, nbytes, name="memset") -> Call:
     lib = _lib.load()
     return Call(lib.msd_memset_zero, (_p(ptr), nbytes), name)
+
+
+LORA_LAYOUT_ROWS, LORA_LAYOUT_CHUNK, LORA_LAYOUT_T = 0, 1, 2   # MsdLoraJob.layout
+
+
+def lora_job(*, master, out, n, k, out_rows, out_cols, up=None, down=None, rank=0, master_ld=None, rowscale=None, colscale=None,
+             rowmap=None, out_frag=None, colsum=None, layout=LORA_LAYOUT_ROWS, out_dtype=OUT_BF16, ld=None, row_off=0,
+             col_off=0) -> _lib.MsdLoraJob:
+    """One msd_lora_merge job descriptor (include/minsdtf_hip.h); first_block is filled by lora_merge."""
+    j = _lib.MsdLoraJob()
+    j.master, j.up, j.down = _p(master), _p(up), _p(down)
+    j.rowscale, j.colscale, j.rowmap = _p(rowscale), _p(colscale), _p(rowmap)
+    j.out, j.out_frag, j.colsum = _p(out), _p(out_frag), _p(colsum)
+    j.n, j.k, j.rank = int(n), int(k), int(rank)
+    j.master_ld = int(k if master_ld is None else master_ld)
+    j.layout, j.out_dtype = int(layout), int(out_dtype)
+    j.ld = int(out_cols if ld is None else ld)
+    j.out_rows, j.out_cols, j.row_off, j.col_off = int(out_rows), int(out_cols), int(row_off), int(col_off)
+    return j
+
+
+def lora_merge(jobs, device, name="lora_merge") -> Call:
+    """One grouped msd_lora_merge launch over `jobs` (lora_job records): the host array is validated by the library, a device
+    copy (kept alive by the returned Call) is what the kernel reads."""
+    import torch
+
+    lib = _lib.load()
+    arr = (_lib.MsdLoraJob * len(jobs))()
+    first = 0
+    for i, j in enumerate(jobs):
+        arr[i] = j
+        arr[i].first_block = first
+        first += (j.n + _lib.LORA_ROWS_PER_BLOCK - 1) // _lib.LORA_ROWS_PER_BLOCK
+    host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8) if jobs else torch.zeros(0, dtype=torch.uint8)
+    dev = host.to(device) if jobs else None
+    s = _lib.MsdLoraMerge()
+    s.jobs, s.jobs_dev, s.num_jobs = C.addressof(arr), _p(dev), len(jobs)
+    return Call(lib.msd_lora_merge, (C.byref(s),), name, keep=(arr, dev, s))

@@ -27,7 +27,7 @@ its Gradio / Streamlit shells.
 from __future__ import annotations
 
 import os
-from typing import Callable, Dict, Optional
+from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -365,6 +365,8 @@ class DenoiseEngine:
             coef = scheduler.coefficient_table()
             taus = [int(t) for t in scheduler.timesteps]
             sched_key = (tuple(int(t) for t in scheduler.timesteps), bool(getattr(scheduler, "active_tcd", False)), coef.tobytes())
+        # (and by the UNet's LoRA version: the table is the time_emb_proj layers' output, which a LoRA switch changes in place)
+        sched_key = sched_key + (getattr(self.unet, "lora_version", 0),)
         if self._sched_key != sched_key:
             self.coef.copy_(torch.from_numpy(coef))
             temb = np.concatenate([get_timestep_embedding(t, 1) for t in taus], axis=0)
@@ -556,6 +558,7 @@ class StableDiffusionBase:
                 # reference :488-493: start token + 76 end tokens through the embedding and the text encoder
                 ids = np.asarray([[49406] + [49407] * (MAX_PROMPT_LENGTH - 1)], dtype=np.int32)
                 self.unconditional_context = self.encode_tokens(ids)
+                self._computed_uncond = self.unconditional_context   # (a text-encoder LoRA switch recomputes it: set_loras)
             else:
                 raise NotImplementedError(
                     "the unconditional context is CLIP's embedding of the empty prompt; pass text_encoder_ckpt=, or set "
@@ -897,8 +900,13 @@ class StableDiffusion(StableDiffusionBase):
     initialised torch.distributed process group ("More than one GPU")."""
 
     def __init__(self, img_height=512, img_width=512, jit_compile=False, clip_skip=-1, unet_ckpt=None, text_encoder_ckpt=None,
-                 vae_ckpt=None, lora_path=None, controlnet_path=None, active_tcd=False, device=None):
+                 vae_ckpt=None, lora_path=None, controlnet_path=None, active_tcd=False, device=None, lora_switch=False):
         super().__init__(img_height, img_width, jit_compile, active_tcd)
+        # lora_switch (opt in: fp32 masters of the targetable weights stay on the device, ~3.4 GB for the UNet): LoRAs are merged
+        # into the packed weights in place by set_loras() instead of at load time (minsdtf_amd/lora.py)
+        self.lora_switch = bool(lora_switch)
+        self._active_loras: List[Tuple[object, float]] = []
+        self._computed_uncond = None
         self.clip_skip = clip_skip
         self.unet_ckpt = unet_ckpt
         self.text_encoder_ckpt = text_encoder_ckpt
@@ -911,13 +919,61 @@ class StableDiffusion(StableDiffusionBase):
             self.text_encoder_lora_dict, self.unet_lora_dict = wtab.load_weights_from_lora(lora_path)
             self.lora_path = lora_path
         self.device = device if device is not None else default_device()
+        if self.lora_switch and self.lora_path is not None:
+            self._active_loras = [(self.lora_path, 1.0)]   # merged when each model gets its weights (_with_loras)
+
+    # ---- LoRA switch at run time
+    @property
+    def active_loras(self) -> Tuple[Tuple[object, float], ...]:
+        """The LoRAs merged into the weights now: ((source, scale), ...)."""
+        return tuple(self._active_loras)
+
+    def _lora_models(self):
+        """The models a LoRA changes that hold weights now (the ControlNet and the VAE are not LoRA targets)."""
+        out = [self.diffusion_model]
+        if self._text_models_ready():
+            out.append(self.text_encoder)
+        return [m for m in out if m._W is not None]
+
+    def set_loras(self, loras) -> None:
+        """Replace the active LoRA set with `loras` = [(source, scale), ...] (source: a kohya .safetensors / .pt path or a loaded
+        state dict; scale: any float).  Entry i adds scale_i * alpha_i / rank_i * up_i @ down_i to its layers; [] restores the base
+        weights bit for bit.  The packed weights are rewritten in place (same tensors, same layouts), so launch plans and the
+        captured whole-loop graph stay valid.  Stream-ordered on the model's device, then synchronised: a job started afterwards
+        on any stream sees the new weights.  Not allowed from inside a generate_image callback.  Every check (the switch, the
+        files, the shapes) runs before the first device write."""
+        if not self.lora_switch:
+            raise RuntimeError("set_loras needs StableDiffusion(lora_switch=True)")
+        from . import lora
+
+        loras = [(src, float(scale)) for src, scale in loras]
+        sets = [(lora.read_factors(src, self.device), scale) for src, scale in loras]
+        models = self._lora_models()
+        for m in models:
+            m.validate_loras(sets)
+        for m in models:
+            changed = m.set_loras(sets)
+            if changed and m is self._text_encoder and self._computed_uncond is not None \
+                    and self.unconditional_context is self._computed_uncond:
+                self.unconditional_context = self._computed_uncond = None
+        self._active_loras = loras
+
+    def _with_loras(self, model):
+        """A model created after set_loras (the properties build them lazily) gets the active set merged at once."""
+        if self.lora_switch and self._active_loras and model._W is not None:
+            from . import lora
+
+            model.set_loras([(lora.read_factors(src, self.device), scale) for src, scale in self._active_loras])
+        return model
 
     @property
     def diffusion_model(self):
         if self._diffusion_model is None:
             self._diffusion_model = DiffusionModel(self.img_height, self.img_width, ckpt_path=self.unet_ckpt,
                                                    apply_control_net=self.controlnet_path is not None,
-                                                   lora_dict=self.unet_lora_dict, device=self.device)
+                                                   lora_dict=None if self.lora_switch else self.unet_lora_dict, device=self.device,
+                                                   lora_switch=self.lora_switch)
+            self._with_loras(self._diffusion_model)
             if self.jit_compile:
                 self._diffusion_model.compile(jit_compile=True)
         return self._diffusion_model
@@ -944,7 +1000,9 @@ class StableDiffusion(StableDiffusionBase):
         """Reference :672-683."""
         if self._text_encoder is None:
             self._text_encoder = TextEncoder(MAX_PROMPT_LENGTH, clip_skip=self.clip_skip, ckpt_path=self.text_encoder_ckpt,
-                                             lora_dict=self.text_encoder_lora_dict, device=self.device)
+                                             lora_dict=None if self.lora_switch else self.text_encoder_lora_dict, device=self.device,
+                                             lora_switch=self.lora_switch)
+            self._with_loras(self._text_encoder)
             if self.jit_compile:
                 self._text_encoder.compile(jit_compile=True)
         return self._text_encoder
