@@ -835,7 +835,7 @@ __global__ __launch_bounds__(512) void conv_bighalo_kernel(CG_HOT_PARAMS, const 
 #endif
 }
 
-// ---- configurations: (BM, BN, WGM, WGN, IH, JH, NB, code); selected by tile_m = 5000 + BM, tile_n = BN, stages = code --------------
+// ---- configurations: (BM, BN, WGM, WGN, IH, JH, NB, code); selected by tile_m = 5000 + BM, tile_n = BN, stages = code (= minsdtf_amd/tuning.py BIG_TILES / BIG_TILES_HALO_IMAGE: tests/test_host_cpu.py test_form_lists_match_the_built_kernels)
 #ifndef MSD_BIG_CFGS
 #define MSD_BIG_CFGS(X)          \
     X(256, 256, 2, 4, 2, 2, 2, 0) \
@@ -886,21 +886,21 @@ static int msd_conv_big_init() {
     return MSD_OK;
 }
 
-// 16-column blocks per wave of the configuration a (bm, bn, code) request selects, 0 if it is not built
-int msd_conv_big_nj(int bm, int bn, int code) {
-#define X(bm_, bn_, wgm, wgn, ih, jh, nb, code_) if (bm == bm_ && bn == bn_ && code == code_) return bn_ / wgn / 16;
+// 16-column blocks per wave of the configuration a decoded (rows, cols, code) request selects, 0 if it is not built
+int msd_conv_big_nj(const CGForm& f) {
+#define X(bm_, bn_, wgm, wgn, ih, jh, nb, code_) if (f.rows == bm_ && f.cols == bn_ && f.code == code_) return bn_ / wgn / 16;
     MSD_BIG_CFGS(X)
 #undef X
     return 0;
 }
 
 // Launch for an already validated argument block (tiles_m / tiles_n / m_fast / nk_per / nslices set by msd_conv_gemm).
-int msd_conv_big_launch(const CGArgs& a, int bm, int bn, int code, int slices, bool dense, hipStream_t stream) {
+int msd_conv_big_launch(const CGArgs& a, const CGForm& f, int slices, bool dense, hipStream_t stream) {
     int rc = msd_conv_big_init();
     if (rc) return rc;
     const dim3 grid(a.tiles_m * a.tiles_n, slices);
 #define X(bm_, bn_, wgm, wgn, ih, jh, nb, code_)                                                                              \
-    if (bm == bm_ && bn == bn_ && code == code_) {                                                                            \
+    if (f.rows == bm_ && f.cols == bn_ && f.code == code_) {                                                                  \
         if (dense)                                                                                                            \
             hipLaunchKernelGGL((conv_big_kernel<bm_, bn_, wgm, wgn, ih, jh, nb, 1>), grid, dim3(512),                         \
                                big_lds(bm_, bn_, nb), stream, CG_HOT_ARGS(a), a);                                             \
@@ -914,12 +914,12 @@ int msd_conv_big_launch(const CGArgs& a, int bm, int bn, int code, int slices, b
     }
     MSD_BIG_CFGS(X)
 #undef X
-    MSD_FAIL(MSD_E_UNSUPPORTED, "conv_big: no %d x %d configuration with code %d", bm, bn, code);
+    MSD_FAIL(MSD_E_UNSUPPORTED, "conv_big: no %d x %d configuration with code %d", f.rows, f.cols, f.code);
 }
 
 // ---- halo-image variant: host side ------------------------------------------------------------------------------------------------
-int msd_conv_bighalo_nj(int bn, int code) {
-#define X(bn_, wgm, wgn, nbw, code_) if (bn == bn_ && code == code_) return bn_ / wgn / 16;
+int msd_conv_bighalo_nj(const CGForm& f) {
+#define X(bn_, wgm, wgn, nbw, code_) if (f.cols == bn_ && f.code == code_) return bn_ / wgn / 16;
     MSD_BIGHALO_CFGS(X)
 #undef X
     return 0;
@@ -927,17 +927,17 @@ int msd_conv_bighalo_nj(int bn, int code) {
 
 // Launch for an already validated argument block (3x3 / stride 1 / pad 1, h_in and w_in multiples of 16, no shortcut operand; tiles_m =
 // batch x 16x16-pixel tiles, mg_tps / mg_tx set, nk_per in 64-channel CHUNKS: msd_conv_gemm).
-int msd_conv_bighalo_launch(const CGArgs& a, int bn, int code, int slices, hipStream_t stream) {
+int msd_conv_bighalo_launch(const CGArgs& a, const CGForm& f, int slices, hipStream_t stream) {
     int rc = msd_conv_big_init();
     if (rc) return rc;
     const dim3 grid(a.tiles_m * a.tiles_n, slices);
 #define X(bn_, wgm, wgn, nbw, code_)                                                                                          \
-    if (bn == bn_ && code == code_) {                                                                                         \
+    if (f.cols == bn_ && f.code == code_) {                                                                                   \
         hipLaunchKernelGGL((conv_bighalo_kernel<bn_, wgm, wgn, nbw>), grid, dim3(512), bighalo_lds(bn_, nbw), stream,         \
                            CG_HOT_ARGS(a), a);                                                                                \
         return MSD_OK;                                                                                                        \
     }
     MSD_BIGHALO_CFGS(X)
 #undef X
-    MSD_FAIL(MSD_E_UNSUPPORTED, "conv_big: no halo-image configuration 256 x %d with code %d", bn, code);
+    MSD_FAIL(MSD_E_UNSUPPORTED, "conv_big: no halo-image configuration 256 x %d with code %d", f.cols, f.code);
 }

@@ -23,6 +23,7 @@ struct CGArgs {
     int kmajor;            // conv_big.hip: 1 = walk K chunk-major (for every 64-channel chunk its 9 taps: the halo-tile kernel's order, so its bits), 0 = tap-major
     uint32_t w_rs, w_ks;   // weight addressing in bytes: row (output column) stride, K-chunk stride ([N][K]: 2K, 128; chunk-major: 128, 128 N)
 };
+#include "conv_form.h"   // the decoded launch codes (CGForm) and the launchers that take them
 
 // Kernarg preload: the kernels take the fields their prologue needs FIRST as leading scalar arguments (15 dwords) in front of the
 // argument block; built with -mllvm -amdgpu-kernarg-preload-count=16 these arrive in SGPRs with the wave, so tile mapping and loader

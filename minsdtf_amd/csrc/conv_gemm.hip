@@ -300,8 +300,7 @@ static void launch_finalize(const CGArgs& a, int slices, hipStream_t stream) {
     }
 }
 
-// ---- tile configurations of the LDS-DMA kernel ------------------------------------------------
-struct TileCfg { int bm, bn, threads, lds, stages; };
+// ---- tile configurations of the LDS-DMA kernel (= minsdtf_amd/tuning.py TILES: tests/test_host_cpu.py test_form_lists_match_the_built_kernels)
 #define MSD_TILE_CFGS(X) \
     X(0, 128, 128, 2, 4, 3, 3) \
     X(1, 128, 64, 2, 2, 3, 3)  \
@@ -334,26 +333,6 @@ struct TileCfg { int bm, bn, threads, lds, stages; };
 //  — 4 x 64 = 256 workgroups, one per CU, each moving (128 + 160) rows per K step instead of 640 workgroups of 64x128 moving
 //  (64 + 128): the layer is bound by the L2 -> LDS bytes per CU, and this is the fewest for a grid that fills the chip once)
 constexpr int cfg_lds(int bm, int bn, int threads, int st) { return st * (bm + (bn + threads / 8 - 1) / (threads / 8) * (threads / 8)) * 128; }
-static const TileCfg g_cfgs[] = {
-#define X(id, bm, bn, wgm, wgn, st, code) {bm, bn, wgm * wgn * 64, cfg_lds(bm, bn, wgm * wgn * 64, st), code},
-    MSD_TILE_CFGS(X)
-#undef X
-};
-constexpr int NUM_TILE_CFGS = 19;
-
-int msd_conv_halo_launch(const CGArgs& a, int th, int bn, int stages, int variant, int slices, hipStream_t stream);
-int msd_conv_wreg_nj(int bm, int bn, int stages);   // 16-column blocks per wave of a built configuration, 0: not built
-int msd_conv_wreg_launch(const CGArgs& a, int bm, int bn, int stages, int slices, bool dense, hipStream_t stream);
-int msd_conv_big_nj(int bm, int bn, int code);      // conv_big.hip: 16-column blocks per wave of a built configuration, 0: not built
-int msd_conv_big_launch(const CGArgs& a, int bm, int bn, int code, int slices, bool dense, hipStream_t stream);
-int msd_conv_bighalo_nj(int bn, int code);              // conv_big.hip, halo-image variant (tile_m 5256, stages 20 + code)
-int msd_conv_bighalo_launch(const CGArgs& a, int bn, int code, int slices, hipStream_t stream);
-// tile_m ranges of the forms (one predicate each, mirrored by minsdtf_amd/tuning.py form_of): [1000, 3000) halo tiles, [3000, 4000)
-// row panels, [4000, 5000) wreg, [5000, 6000) big; anything from 6000 up is refused
-static inline bool cg_is_wreg(int tile_m) { return tile_m >= 4000 && tile_m < 5000; }
-static inline bool cg_is_big(int tile_m) { return tile_m >= 5000 && tile_m < 6000; }
-bool msd_conv_rowpanel_eligible(const CGArgs& a, int rows, int wg_cols);
-int msd_conv_rowpanel_launch(CGArgs a, int rows, int wg_cols, hipStream_t stream);
 
 static bool g_cg_attr_done = false;
 static int g_conv_dense = 1; // 1 = 1x1 / Dense layers take the DENSE loader (default), 0 = the general loader (A/B runs)
@@ -361,8 +340,7 @@ void msd_set_conv_dense(int v) { g_conv_dense = v; }
 
 int msd_conv_gemm_init() {
     if (g_cg_attr_done) return MSD_OK;
-    hipError_t e;
-    e = hipSuccess;
+    hipError_t e = hipSuccess;
 #define X(id, bm, bn, wgm, wgn, st, code)                                                                           \
     if (e == hipSuccess)                                                                                            \
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_dma_kernel<bm, bn, wgm, wgn, st, false>),  \
@@ -377,21 +355,117 @@ int msd_conv_gemm_init() {
     return MSD_OK;
 }
 
-// tile width the launch will use (same rules as msd_conv_gemm below)
-static int cg_effective_bn(const MsdConvGemm* q) {
-    if (cg_is_wreg(q->tile_m) || cg_is_big(q->tile_m)) return q->tile_n;   // wreg / big form: the request IS the tile (the launch fails if it is not built)
-    int bn = q->tile_m >= 3000 ? 64 : q->tile_n;   // (a row-panel request that is not eligible runs on the 128x64 tile)
+// column tile the launch will use: the one rule behind msd_conv_gemm_ln_slots and cg_resolve_form
+static int cg_run_cols(const CGForm& f, const MsdConvGemm* q) {
+    if (f.family == CG_WREG || cg_is_big(f)) return f.cols;   // wreg / big form: the request IS the tile (the launch fails if it is not built)
+    int bn = (f.family == CG_ROWPANEL || f.family == CG_NONE) ? 64 : f.cols;   // (a row-panel request that is not eligible runs on the 128x64 tile)
     if (bn == 0) bn = (q->N % 128 == 0 || q->N > 1024) ? 128 : 64;
-    if (bn == 80 && q->act == MSD_ACT_GEGLU) bn = 64;
+    if (bn == 80 && q->act == MSD_ACT_GEGLU) bn = 64;   // (80 = 5 fragments: no x|gate pairing -> 64 for GEGLU)
     return bn;
 }
 
 extern "C" int msd_conv_gemm_ln_slots(const MsdConvGemm* q) {
     if (!q || q->N <= 0) MSD_FAIL(MSD_E_ARG, "conv_gemm_ln_slots: bad arguments");
-    if (q->tile_m >= 1000 && q->ksize == 3) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm_ln_slots: 1x1 / dense launches only");
-    const int bn = cg_effective_bn(q);
+    const CGForm f = cg_decode_form(q->tile_m, q->tile_n, q->stages);
+    if (f.family != CG_TILE && q->ksize == 3) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm_ln_slots: 1x1 / dense launches only");
+    const int bn = cg_run_cols(f, q);
     return (q->N + bn - 1) / bn;
 }
+
+// what the halo-tile kernel takes: 3x3 / stride 1 / pad 1 on a same-size output of whole th x 16-pixel tiles (a shortcut operand - stride 1,
+// same-size output, < 4 GB: checked by msd_conv_gemm - is walked behind the slice's main chunks, conv_halo.hip)
+static bool cg_halo_eligible(const MsdConvGemm* q, const CGArgs& a, int th) {
+    return q->ksize == 3 && q->stride == 1 && q->pad == 1 && q->h_out == q->h_in && q->w_out == q->w_in && !q->upsample && (q->w_in % 16) == 0 &&
+           (long long)q->N * a.K * 2 < (1ll << 32) - 4096 &&   // 32-bit weight / activation byte offsets
+           (long long)a.M * (q->c0 > q->c1 ? q->c0 : q->c1) * 2 < (1ll << 32) - 4096 && (th == 8 || th == 16) && (q->h_in % th) == 0;
+}
+
+// Requested form -> the form that runs, and the split-K slices it runs in (a.nk_per, a.nslices, a.kmajor).  The ONLY place where a request is replaced:
+//   a halo request the halo-tile kernel does not take -> the 128-row tile: the tap-major walk, another order of sums than was asked for
+//   a row-panel request that kernel does not take     -> the 128x64 tile (the same bits)
+//   tile / halo columns: 0 -> by N, 80 with GEGLU -> 64; a 16x16-pixel halo tile is 128 wide unless 80 is asked for
+//   GEGLU on an 8-wave tile -> the tile's default entry (GEGLU pairs the fragments of a wave: the 8-wave 64x64 tile has a single one per wave)
+static CGForm cg_resolve_form(const CGForm& f, const MsdConvGemm* q, CGArgs& a, int splitk) {
+    CGForm run = f;
+    if (f.family == CG_HALO && !cg_halo_eligible(q, a, f.th)) run = cg_decode_form(128, f.cols, q->stages);
+    // split-K is over 64-channel chunks (each = 9 K steps) on the chunk-major walk, over K tiles on the tap-major one
+    const int units = run.chunk_major ? a.nkc : a.nk;
+    if (splitk > units) splitk = units;
+    a.nk_per = (units + splitk - 1) / splitk;
+    a.nslices = (units + a.nk_per - 1) / a.nk_per;
+    a.kmajor = (run.family == CG_BIG && run.chunk_major) ? 1 : 0;
+    if (a.kmajor) a.nk_per *= 9;   // (the big form counts K tiles, nine per chunk; its staged-halo variant counts chunks)
+    if (f.family == CG_ROWPANEL && !msd_conv_rowpanel_eligible(a, f.rows, f.cols)) run = cg_decode_form(128, 64, q->stages);
+    if (run.family == CG_TILE || run.family == CG_HALO) run.cols = cg_run_cols(run, q);
+    if (run.family == CG_HALO && run.th == 16 && run.cols != 80) run.cols = 128;
+    if (run.family == CG_TILE && run.rows == 0) run.rows = 128;
+    if (run.family == CG_TILE && run.variant == 1 && q->act == MSD_ACT_GEGLU) run.code = 0;
+    return run;
+}
+
+// ---- the launch tail, shared by the families: tile grid, tiles_m row tiles x N / cols column tiles; tps / tx = tiles per sample / per tile row of the two spatially tiled forms
+static void cg_set_tiles(CGArgs& a, int tiles_m, int cols, int tps = 0, int tx = 0) {
+    a.tiles_m = tiles_m;
+    a.tiles_n = (a.N + cols - 1) / cols;
+    a.m_fast = (a.N > a.M) ? 1 : 0;   // weights are the bigger operand: keep each weight panel on one XCD
+    a.mg_tdiv = udiv_magic_of(a.m_fast ? a.tiles_m : a.tiles_n);
+    a.mg_tps = tps ? udiv_magic_of(tps) : 0;
+    a.mg_tx = tx ? udiv_magic_of(tx) : 0;
+}
+// 1x1 / Dense form: 32-bit byte offsets from the tensor bases (the DENSE kernels carry the LayerNorm-fold consumer and no time-embedding row, the
+// general kernels the reverse); tile = the plain tile kernel: it also honours msd_set_conv_dense and checks the 4 GB bounds of its own loader
+static int cg_dense_form(const MsdConvGemm* q, const CGArgs& a, bool tile, bool* dense) {
+    const bool needs_dense = q->ln_in || q->act == MSD_ACT_GEGLU || q->split_mode;
+    bool d = !q->rowvec && !q->a2 && q->ksize == 1 && q->stride == 1 && !q->upsample && q->h_out == q->h_in && q->w_out == q->w_in;
+    if (tile)
+        d = d && (g_conv_dense || needs_dense) && (long long)a.M * (q->c0 > q->c1 ? q->c0 : q->c1) * 2 < (1ll << 32) - 4096 &&
+            (long long)a.N * a.K * 2 < (1ll << 32) - 4096;
+    if (needs_dense && !d)
+        MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: the LayerNorm fold, GEGLU and the q|k|v^T split run on the 1x1 / Dense form only%s",
+                 tile ? " (ksize 1, stride 1, no upsampling, no rowvec, no shortcut operand)" : "");
+    *dense = d;
+    return MSD_OK;
+}
+static int cg_hot_check(const CGArgs& a) {
+    if (!cg_hot_ok(a)) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: tile / K-tile / channel counts beyond the packed launch arguments (K tiles, channels < 65536; row tiles < 2^23; column tiles < 256)");
+    return MSD_OK;
+}
+static int cg_launched(int rc, const CGArgs& a, int slices, hipStream_t stream) {   // behind every family's launch: its status, the launch error, the split-K reduction
+    if (rc) return rc;
+    MSD_CHECK_LAUNCH();
+    if (slices > 1) {
+        launch_finalize(a, slices, stream);
+        MSD_CHECK_LAUNCH();
+    }
+    return MSD_OK;
+}
+
+// id of the MSD_TILE_CFGS entry a tile form selects, -1: no such tile (the first entry of a tile size is its default ring depth; `stages` selects a deeper ring: more
+//  bytes in flight per CU for the weight-streaming small-M layers that run one workgroup per CU)
+static int cg_tile_cfg(const CGForm& f) {
+    int cfg = -1;
+#define X(id, bm, bn, wgm, wgn, st, code_) if (f.rows == bm && f.cols == bn && (cfg < 0 || f.code == code_)) cfg = id;
+    MSD_TILE_CFGS(X)
+#undef X
+    return cfg;
+}
+static void cg_tile_launch(int cfg, const CGArgs& a, bool dense, int slices, hipStream_t stream) {
+    const dim3 grid(a.tiles_m * a.tiles_n, slices);
+    switch (cfg) {
+#define X(id, bm_, bn_, wgm, wgn, st, code)                                                                             \
+    case id:                                                                                                            \
+        if (dense)                                                                                                      \
+            hipLaunchKernelGGL((conv_gemm_dma_kernel<bm_, bn_, wgm, wgn, st, true>), grid, dim3(wgm * wgn * 64),        \
+                               cfg_lds(bm_, bn_, wgm * wgn * 64, st), stream, CG_HOT_ARGS(a), a);                       \
+        else                                                                                                            \
+            hipLaunchKernelGGL((conv_gemm_dma_kernel<bm_, bn_, wgm, wgn, st, false>), grid, dim3(wgm * wgn * 64),       \
+                               cfg_lds(bm_, bn_, wgm * wgn * 64, st), stream, CG_HOT_ARGS(a), a);                       \
+        break;
+        MSD_TILE_CFGS(X)
+#undef X
+    }
+}
+
 
 extern "C" int msd_conv_gemm(const MsdConvGemm* q, msd_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
@@ -489,24 +563,20 @@ extern "C" int msd_conv_gemm(const MsdConvGemm* q, msd_stream_t stream_) {
     // (again, with the shortcut channels in K: the weight loader's 32-bit byte offsets are n * K * 2 + ...)
     if ((long long)a.N * a.K * 2 >= (1ll << 32) - 4096) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: an operand of 4 GB or more");
     if (q->w_layout < 0 || q->w_layout > 2) MSD_FAIL(MSD_E_ARG, "conv_gemm: w_layout %d", q->w_layout);
-    if (q->tile_m >= 6000 || q->tile_m < 0) MSD_FAIL(MSD_E_ARG, "conv_gemm: tile_m %d names no kernel form", q->tile_m);
-    const bool wreg = cg_is_wreg(q->tile_m), big = cg_is_big(q->tile_m);
-    // big form, stages code + 10: chunk-major K walk (the halo-tile kernel's order and numerics class)
-    // stages code + 20: the same walk on a staged 18 x 18-pixel halo per chunk (3x3 / stride 1 / pad 1 on whole 16 x 16-pixel tiles)
-    const bool big_hi = big && q->stages >= 20;
-    const bool big_km = big && q->stages >= 10 && !big_hi;
-    const int big_code = big_hi ? q->stages - 20 : (big_km ? q->stages - 10 : q->stages);
+    const CGForm f = cg_decode_form(q->tile_m, q->tile_n, q->stages);
+    if (!f.valid) MSD_FAIL(MSD_E_ARG, "conv_gemm: tile_m %d names no kernel form", q->tile_m);
+    const bool wreg = f.family == CG_WREG, big = cg_is_big(f), bighalo = f.family == CG_BIGHALO;
     if (big) {
-        if ((big_km || big_hi) && (q->ksize != 3 || (q->a2 && !big_hi)))
+        if (f.chunk_major && (q->ksize != 3 || (q->a2 && !bighalo)))
             MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: the chunk-major walk of the big-tile form is for 3x3 convs (with a shortcut operand: on the staged-halo variant only)");
-        if (big_hi) {
-            if (q->tile_m != 5256 || !msd_conv_bighalo_nj(q->tile_n, big_code))
-                MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: no halo-image big-tile configuration %d x %d code %d", q->tile_m - 5000, q->tile_n, big_code);
+        if (bighalo) {
+            if (f.rows != 256 || !msd_conv_bighalo_nj(f))
+                MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: no halo-image big-tile configuration %d x %d code %d", f.rows, f.cols, f.code);
             const int up = q->upsample ? 2 : 1;
             if (q->stride != 1 || q->pad != 1 || q->h_out != up * q->h_in || q->w_out != up * q->w_in || (q->h_out % 16) || (q->w_out % 16))
                 MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: the halo-image big-tile form runs 3x3 / stride 1 / pad 1 convs on output images of whole 16 x 16-pixel tiles (%d x %d)", q->h_out, q->w_out);
-        } else if (!msd_conv_big_nj(q->tile_m - 5000, q->tile_n, big_code))
-            MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: no big-tile configuration %d x %d code %d", q->tile_m - 5000, q->tile_n, big_code);
+        } else if (!msd_conv_big_nj(f))
+            MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: no big-tile configuration %d x %d code %d", f.rows, f.cols, f.code);
         if (q->ln_out) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: the big-tile form has no LayerNorm-producer epilogue (ln_out)");
         // its general loader forms pixel * row bytes with a 24-bit multiply
         if ((long long)q->batch * q->h_in * q->w_in >= (1ll << 24) || (long long)(q->c0 > q->c1 ? q->c0 : q->c1) * 2 >= (1ll << 24))
@@ -522,8 +592,8 @@ extern "C" int msd_conv_gemm(const MsdConvGemm* q, msd_stream_t stream_) {
     if (wreg != (q->w_layout == 2))
         MSD_FAIL(MSD_E_ARG, "conv_gemm: tile_m %d with w_layout %d (the fragment-major weight image, w_layout 2, is read by the wreg form, tile_m 4000 + rows, and by nothing else)",
                  q->tile_m, q->w_layout);
-    if (wreg && ((q->N % 16) || !msd_conv_wreg_nj(q->tile_m - 4000, q->tile_n, q->stages)))
-        MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: no wreg configuration %d x %d stages %d (N %% 16 must be 0: N = %d)", q->tile_m - 4000, q->tile_n, q->stages, q->N);
+    if (wreg && ((q->N % 16) || !msd_conv_wreg_nj(f)))
+        MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: no wreg configuration %d x %d stages %d (N %% 16 must be 0: N = %d)", f.rows, f.cols, f.code, q->N);
     a.w_rs = q->w_layout ? 128u : (uint32_t)a.K * 2u;
     a.w_ks = q->w_layout ? (uint32_t)a.N * 128u : 128u;
     a.ln_in = q->ln_in; a.ln_colsum = q->ln_colsum; a.ln_out = q->ln_out;
@@ -535,7 +605,7 @@ extern "C" int msd_conv_gemm(const MsdConvGemm* q, msd_stream_t stream_) {
         if (!msd_aligned16(q->ln_colsum) || (((uintptr_t)q->ln_in) & 7u)) MSD_FAIL(MSD_E_ALIGN, "conv_gemm: ln_in / ln_colsum alignment");
     }
     if (q->ln_out) {
-        if (q->split_mode || q->out_dtype != MSD_OUT_BF16 || q->act != MSD_ACT_NONE || q->ksize != 1 || (q->tile_m >= 1000 && q->tile_m < 3000) || big ||
+        if (q->split_mode || q->out_dtype != MSD_OUT_BF16 || q->act != MSD_ACT_NONE || q->ksize != 1 || f.family == CG_HALO || big ||
             (((uintptr_t)q->ln_out) & 7u))
             MSD_FAIL(MSD_E_ARG, "conv_gemm: ln_out needs a plain 1x1 launch with a bf16 output and no activation");
         if (q->ln_out_slots != msd_conv_gemm_ln_slots(q))
@@ -543,31 +613,10 @@ extern "C" int msd_conv_gemm(const MsdConvGemm* q, msd_stream_t stream_) {
                      msd_conv_gemm_ln_slots(q));
     }
 
-    int splitk = q->splitk < 1 ? 1 : q->splitk;
+    const int splitk = q->splitk < 1 ? 1 : q->splitk;
     if ((q->ln_in || q->ln_out) && splitk > 1) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: the LayerNorm fold is plain-K only (splitk=%d)", splitk);
-    // halo variant (tile_m = 1000 + pixels per tile: 1128 = 8x16, 1256 = 16x16): spatially blocked 3x3
-    int halo_th = 0;
-    if (q->tile_m >= 1000 && q->tile_m < 3000) {
-        const int th = (q->tile_m % 1000) / 16;   // 1128 / 1256: 8x16 / 16x16 pixels; 2128: 8x16 on 8 waves
-        // (a shortcut operand - stride 1, same-size output, < 4 GB: checked above - is walked behind the slice's main chunks, conv_halo.hip)
-        const bool ok = q->ksize == 3 && q->stride == 1 && q->pad == 1 && q->h_out == q->h_in &&
-                        q->w_out == q->w_in && !q->upsample && (q->w_in % 16) == 0 &&
-                        (long long)q->N * a.K * 2 < (1ll << 32) - 4096 &&   // 32-bit weight / activation byte offsets
-                        (long long)a.M * (q->c0 > q->c1 ? q->c0 : q->c1) * 2 < (1ll << 32) - 4096 &&
-                        (th == 8 || th == 16) && (q->h_in % th) == 0;
-        if (ok) halo_th = th;
-    }
-    a.kmajor = big_km ? 1 : 0;
-    if (halo_th || big_km || big_hi) {  // split-K is over 64-channel chunks (each = 9 K steps)
-        if (splitk > a.nkc) splitk = a.nkc;
-        a.nk_per = (a.nkc + splitk - 1) / splitk;
-    } else {
-        if (splitk > a.nk) splitk = a.nk;
-        a.nk_per = (a.nk + splitk - 1) / splitk;
-    }
-    const int slices = (halo_th || big_km || big_hi) ? (a.nkc + a.nk_per - 1) / a.nk_per : (a.nk + a.nk_per - 1) / a.nk_per;
-    a.nslices = slices;
-    if (big_km) a.nk_per *= 9;   // (the big form counts K tiles, nine per chunk)
+    const CGForm run = cg_resolve_form(f, q, a, splitk);
+    const int slices = a.nslices;
     if (slices > 1) {
         if (q->split_mode || q->act == MSD_ACT_GEGLU) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: split-K needs plain mode");
         if ((long long)a.M * a.N / 4 >= (1ll << 31)) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: split-K output too large");
@@ -575,137 +624,40 @@ extern "C" int msd_conv_gemm(const MsdConvGemm* q, msd_stream_t stream_) {
             MSD_FAIL(MSD_E_WORKSPACE, "conv_gemm: split-K workspace too small (%lld < %lld floats)",
                      (long long)q->workspace_floats, (long long)slices * a.M * a.N);
     }
-    // tile configuration: explicit (tile_m, tile_n) or the size heuristic
-    int bm = q->tile_m, bn = cg_effective_bn(q);   // (80 = 5 fragments: no x|gate pairing -> 64 for GEGLU)
-    if (bm == 0 || bm >= 1000) bm = 128;   // a halo request that is not eligible falls back to 128-row tiles
-    if (halo_th) {
-        if (halo_th == 16 && bn != 80) bn = 128;
-        a.tiles_n = (a.N + bn - 1) / bn;
-        a.tiles_m = a.batch * (a.h_in / halo_th) * (a.w_in / 16);
-        a.m_fast = (a.N > a.M) ? 1 : 0;
-        a.mg_tdiv = udiv_magic_of(a.m_fast ? a.tiles_m : a.tiles_n);
-        a.mg_tps = udiv_magic_of((a.h_in / halo_th) * (a.w_in / 16));
-        a.mg_tx = udiv_magic_of(a.w_in / 16);
-        rc = msd_conv_halo_launch(a, halo_th, bn, q->stages, q->tile_m >= 2000 ? 1 : 0, slices, stream);
-        if (rc) return rc;
-        MSD_CHECK_LAUNCH();
-        if (slices > 1) {
-            launch_finalize(a, slices, stream);
-            MSD_CHECK_LAUNCH();
-        }
-        return MSD_OK;
-    }
-    // row-panel Dense kernel (tile_m = 3000 + rows per workgroup, tile_n = columns per workgroup): conv_rowpanel.hip
-    if (q->tile_m >= 3000 && q->tile_m < 4000 && msd_conv_rowpanel_eligible(a, q->tile_m - 3000, q->tile_n)) {
-        rc = msd_conv_rowpanel_launch(a, q->tile_m - 3000, q->tile_n, stream);
-        if (rc) return rc;
-        MSD_CHECK_LAUNCH();
-        return MSD_OK;
-    }
-    if (wreg) {   // weights global -> VGPR in fragment order, activations through the LDS ring: conv_wreg.hip
-        const int wbm = q->tile_m - 4000, wbn = q->tile_n;
-        if (q->act == MSD_ACT_GEGLU && (msd_conv_wreg_nj(wbm, wbn, q->stages) % 2)) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: GEGLU needs x | gate fragment pairs per wave");
-        a.tiles_m = (a.M + wbm - 1) / wbm;
-        a.tiles_n = (a.N + wbn - 1) / wbn;
-        a.m_fast = (a.N > a.M) ? 1 : 0;
-        a.mg_tdiv = udiv_magic_of(a.m_fast ? a.tiles_m : a.tiles_n);
-        a.mg_tps = a.mg_tx = 0;
-        const bool needs_dense = q->ln_in || q->act == MSD_ACT_GEGLU || q->split_mode;
-        const bool dense = !q->rowvec && !q->a2 && q->ksize == 1 && q->stride == 1 && !q->upsample && q->h_out == q->h_in && q->w_out == q->w_in;
-        if (needs_dense && !dense)
-            MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: the LayerNorm fold, GEGLU and the q|k|v^T split run on the 1x1 / Dense form only");
-        if (!cg_hot_ok(a)) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: tile / K-tile / channel counts beyond the packed launch arguments (K tiles, channels < 65536; row tiles < 2^23; column tiles < 256)");
-        rc = msd_conv_wreg_launch(a, wbm, wbn, q->stages, slices, dense, stream);
-        if (rc) return rc;
-        MSD_CHECK_LAUNCH();
-        if (slices > 1) {
-            launch_finalize(a, slices, stream);
-            MSD_CHECK_LAUNCH();
-        }
-        return MSD_OK;
-    }
-    if (big_hi) {   // the big form on a staged halo: conv_big.hip (conv_bighalo_kernel); nk_per stays in chunks
-        a.tiles_m = a.batch * (a.h_out / 16) * (a.w_out / 16);
-        a.tiles_n = (a.N + q->tile_n - 1) / q->tile_n;
-        a.m_fast = (a.N > a.M) ? 1 : 0;
-        a.mg_tdiv = udiv_magic_of(a.m_fast ? a.tiles_m : a.tiles_n);
-        a.mg_tps = udiv_magic_of((a.h_out / 16) * (a.w_out / 16));
-        a.mg_tx = udiv_magic_of(a.w_out / 16);
-        if (!cg_hot_ok(a)) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: tile / K-tile / channel counts beyond the packed launch arguments (K tiles, channels < 65536; row tiles < 2^23; column tiles < 256)");
-        rc = msd_conv_bighalo_launch(a, q->tile_n, big_code, slices, stream);
-        if (rc) return rc;
-        MSD_CHECK_LAUNCH();
-        if (slices > 1) {
-            launch_finalize(a, slices, stream);
-            MSD_CHECK_LAUNCH();
-        }
-        return MSD_OK;
-    }
-    if (big) {   // 256-row macro tiles, staggered half-workgroups: conv_big.hip
-        const int bbm = q->tile_m - 5000, bbn = q->tile_n;
-        if (q->act == MSD_ACT_GEGLU && (msd_conv_big_nj(bbm, bbn, big_code) % 2)) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: GEGLU needs x | gate fragment pairs per wave");
-        a.tiles_m = (a.M + bbm - 1) / bbm;
-        a.tiles_n = (a.N + bbn - 1) / bbn;
-        a.m_fast = (a.N > a.M) ? 1 : 0;
-        a.mg_tdiv = udiv_magic_of(a.m_fast ? a.tiles_m : a.tiles_n);
-        a.mg_tps = a.mg_tx = 0;
-        const bool needs_dense = q->ln_in || q->act == MSD_ACT_GEGLU || q->split_mode;
-        const bool dense = !q->rowvec && !q->a2 && q->ksize == 1 && q->stride == 1 && !q->upsample && q->h_out == q->h_in && q->w_out == q->w_in;
-        if (needs_dense && !dense)
-            MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: the LayerNorm fold, GEGLU and the q|k|v^T split run on the 1x1 / Dense form only");
-        if (!cg_hot_ok(a)) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: tile / K-tile / channel counts beyond the packed launch arguments (K tiles, channels < 65536; row tiles < 2^23; column tiles < 256)");
-        rc = msd_conv_big_launch(a, bbm, bbn, big_code, slices, dense, stream);
-        if (rc) return rc;
-        MSD_CHECK_LAUNCH();
-        if (slices > 1) {
-            launch_finalize(a, slices, stream);
-            MSD_CHECK_LAUNCH();
-        }
-        return MSD_OK;
-    }
-    int cfg = -1;
-    // (GEGLU pairs the fragments of a wave: the 8-wave 64x64 tile has a single one per wave)
-    const int stages_req = (q->act == MSD_ACT_GEGLU && q->stages >= 10 && q->stages < 20) ? 0 : q->stages;
-    for (int i = 0; i < NUM_TILE_CFGS; ++i)
-        if (g_cfgs[i].bm == bm && g_cfgs[i].bn == bn && (cfg < 0 || g_cfgs[i].stages == stages_req)) cfg = i;
-    // (the first entry of a tile size is its default ring depth; `stages` selects a deeper ring: more
-    //  bytes in flight per CU for the weight-streaming small-M layers that run one workgroup per CU)
-    if (cfg < 0)
-        MSD_FAIL(MSD_E_ARG, "conv_gemm: unsupported tile %dx%d (have 128x128 128x64 64x64 64x128 256x128)", bm, bn);
-    const int tiles_m = (a.M + bm - 1) / bm;
-    a.tiles_n = (a.N + bn - 1) / bn;
-    a.tiles_m = tiles_m;
-    a.m_fast = (a.N > a.M) ? 1 : 0;   // weights are the bigger operand: keep each weight panel on one XCD
-    a.mg_tdiv = udiv_magic_of(a.m_fast ? a.tiles_m : a.tiles_n);
-    a.mg_tps = a.mg_tx = 0;
-    dim3 grid(tiles_m * a.tiles_n, slices);
-    if (!cg_hot_ok(a)) MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: tile / K-tile / channel counts beyond the packed launch arguments (K tiles, channels < 65536; row tiles < 2^23; column tiles < 256)");
-    // 1x1 / Dense form: 32-bit byte offsets from the tensor bases
-    // (the DENSE kernel carries the LayerNorm-fold consumer and no time-embedding row, the general kernel the reverse)
-    const bool needs_dense = q->ln_in || q->act == MSD_ACT_GEGLU || q->split_mode;
-    const bool dense = (g_conv_dense || needs_dense) && !q->rowvec && !q->a2 && q->ksize == 1 && q->stride == 1 && !q->upsample && q->h_out == q->h_in && q->w_out == q->w_in &&
-                       (long long)a.M * (q->c0 > q->c1 ? q->c0 : q->c1) * 2 < (1ll << 32) - 4096 &&
-                       (long long)a.N * a.K * 2 < (1ll << 32) - 4096;
-    if (needs_dense && !dense)
-        MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: the LayerNorm fold, GEGLU and the q|k|v^T split run on the 1x1 / Dense form only (ksize 1, "
-                                    "stride 1, no upsampling, no rowvec, no shortcut operand)");
-    switch (cfg) {
-#define X(id, bm_, bn_, wgm, wgn, st, code)                                                                             \
-    case id:                                                                                                            \
-        if (dense)                                                                                                      \
-            hipLaunchKernelGGL((conv_gemm_dma_kernel<bm_, bn_, wgm, wgn, st, true>), grid, dim3(wgm * wgn * 64),        \
-                               cfg_lds(bm_, bn_, wgm * wgn * 64, st), stream, CG_HOT_ARGS(a), a);                       \
-        else                                                                                                            \
-            hipLaunchKernelGGL((conv_gemm_dma_kernel<bm_, bn_, wgm, wgn, st, false>), grid, dim3(wgm * wgn * 64),       \
-                               cfg_lds(bm_, bn_, wgm * wgn * 64, st), stream, CG_HOT_ARGS(a), a);                       \
+    bool dense = false;
+    switch (run.family) {
+    case CG_HALO: {   // spatially blocked 3x3, th x 16-pixel tiles: conv_halo.hip
+        const int ty = a.h_in / run.th, tx = a.w_in / 16;
+        cg_set_tiles(a, a.batch * ty * tx, run.cols, ty * tx, tx);
+        rc = msd_conv_halo_launch(a, run, slices, stream);
         break;
-        MSD_TILE_CFGS(X)
-#undef X
     }
-    MSD_CHECK_LAUNCH();
-    if (slices > 1) {
-        launch_finalize(a, slices, stream);
-        MSD_CHECK_LAUNCH();
+    case CG_ROWPANEL:   // rows per workgroup x columns per workgroup: conv_rowpanel.hip
+        rc = msd_conv_rowpanel_launch(a, run.rows, run.cols, stream);
+        break;
+    case CG_WREG:   // weights global -> VGPR in fragment order, activations through the LDS ring: conv_wreg.hip
+    case CG_BIG:    // 256-row macro tiles, staggered half-workgroups: conv_big.hip
+        if (q->act == MSD_ACT_GEGLU && ((wreg ? msd_conv_wreg_nj(run) : msd_conv_big_nj(run)) % 2))
+            MSD_FAIL(MSD_E_UNSUPPORTED, "conv_gemm: GEGLU needs x | gate fragment pairs per wave");
+        cg_set_tiles(a, (a.M + run.rows - 1) / run.rows, run.cols);
+        if ((rc = cg_dense_form(q, a, false, &dense)) || (rc = cg_hot_check(a))) return rc;
+        rc = wreg ? msd_conv_wreg_launch(a, run, slices, dense, stream) : msd_conv_big_launch(a, run, slices, dense, stream);
+        break;
+    case CG_BIGHALO: {   // the big form on a staged halo of 16 x 16-pixel tiles: conv_big.hip (conv_bighalo_kernel); nk_per stays in chunks
+        const int ty = a.h_out / 16, tx = a.w_out / 16;
+        cg_set_tiles(a, a.batch * ty * tx, run.cols, ty * tx, tx);
+        if ((rc = cg_hot_check(a))) return rc;
+        rc = msd_conv_bighalo_launch(a, run, slices, stream);
+        break;
     }
-    return MSD_OK;
+    default: {   // CG_TILE
+        const int cfg = cg_tile_cfg(run);
+        if (cfg < 0)
+            MSD_FAIL(MSD_E_ARG, "conv_gemm: unsupported tile %dx%d (have 128x128 128x64 64x64 64x128 256x128)", run.rows, run.cols);
+        cg_set_tiles(a, (a.M + run.rows - 1) / run.rows, run.cols);
+        if ((rc = cg_hot_check(a)) || (rc = cg_dense_form(q, a, true, &dense))) return rc;
+        cg_tile_launch(cfg, a, dense, slices, stream);
+    }
+    }
+    return cg_launched(rc, a, slices, stream);
 }

@@ -536,7 +536,7 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv3x3_halo_kernel(HAL
 // Variant 1 (tile_m 2128): the same tile on 8 waves — two waves per SIMD even when the launch puts a
 // single workgroup on a CU, so one wave's LDS-DMA issue stalls and LDS latency hide under the other's MFMAs.
 // `stages` 30 + depth: 3 taps (one filter row) per K step with a ring of `depth` rows (8x16 tiles x 64 / 80 channels: the
-// ring holds depth x 3 weight tiles).
+// ring holds depth x 3 weight tiles). (= minsdtf_amd/tuning.py HALO_TILES: tests/test_host_cpu.py test_form_lists_match_the_built_kernels)
 #define MSD_HALO_CFGS(X)      \
     X(8, 64, 2, 2, 3, 0, 1, 0)   \
     X(8, 128, 2, 4, 3, 0, 1, 0)  \
@@ -566,9 +566,14 @@ __global__ __launch_bounds__((WGM * WGN + NL) * 64) void conv3x3_halo_kernel(HAL
     X(16, 80, 4, 1, 153, 0, 1, 0) \
     X(16, 80, 4, 1, 155, 0, 1, 0)
 
+// a `stages` code of the table = 30 / 60 / 90 / 150 + ring depth (the plain form's code is its depth); from 90 up the K loop is rotated (PFX)
+constexpr int halo_depth(int code) { return code % 30; }
+constexpr int halo_rotated(int code) { return code >= 90 ? 1 : 0; }
+#define HALO_KERNEL(th, bn, wgm, wgn, st, taps, nl, xsc) conv3x3_halo_kernel<th, bn, wgm, wgn, halo_depth(st), taps, nl, halo_rotated(st), xsc>
+
 template <int TH, int BN, int WGM, int WGN, int SC, int TAPS, int NL, bool XSC = false>
 static constexpr int halo_lds() {
-    constexpr int S = SC % 30;   // (SC = stages code: 30 + depth for the 3-taps-per-step form, 60 + depth: the same with 2 loader waves)
+    constexpr int S = halo_depth(SC);
     constexpr int NT = (NL ? NL : WGM * WGN) * 64, RPP = NT / 8, HROWS = (TH + 2) * 18, HR = (HROWS + RPP - 1) / RPP;
     constexpr int BNP = (BN + RPP - 1) / RPP * RPP;
     constexpr int base = 2 * HR * RPP * 128 + S * TAPS * BNP * 128;
@@ -583,10 +588,10 @@ int msd_conv_halo_init() {
     hipError_t e = hipSuccess;
 #define X(th, bn, wgm, wgn, st, var, taps, nl)                                                                         \
     if (e == hipSuccess)                                                                                              \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<th, bn, wgm, wgn, st % 30, taps, nl, (st >= 90), false>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, halo_lds<th, bn, wgm, wgn, st, taps, nl>());                           \
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&HALO_KERNEL(th, bn, wgm, wgn, st, taps, nl, false)),   \
+                                hipFuncAttributeMaxDynamicSharedMemorySize, halo_lds<th, bn, wgm, wgn, st, taps, nl>());       \
     if (e == hipSuccess)                                                                                              \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_halo_kernel<th, bn, wgm, wgn, st % 30, taps, nl, (st >= 90), true>), \
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&HALO_KERNEL(th, bn, wgm, wgn, st, taps, nl, true)),    \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, halo_lds<th, bn, wgm, wgn, st, taps, nl, true>());
     MSD_HALO_CFGS(X)
 #undef X
@@ -595,35 +600,35 @@ int msd_conv_halo_init() {
     return MSD_OK;
 }
 
+static bool halo_built(int th, int bn, int stages, int variant) {
+#define X(th_, bn_, wgm, wgn, st, var, taps, nl) if (th == th_ && bn == bn_ && stages == st && variant == var) return true;
+    MSD_HALO_CFGS(X)
+#undef X
+    return false;
+}
+
 // Launch for an already validated argument block; returns MSD_E_UNSUPPORTED if (th, bn) is not built.
-int msd_conv_halo_launch(const CGArgs& a, int th, int bn, int stages, int variant, int slices, hipStream_t stream) {
+int msd_conv_halo_launch(const CGArgs& a, const CGForm& f, int slices, hipStream_t stream) {
     int rc = msd_conv_halo_init();
     if (rc) return rc;
     if (a.tiles_m <= 0 || a.tiles_m >= (1 << 23) || a.tiles_n <= 0 || a.tiles_n >= 256)
         MSD_FAIL(MSD_E_UNSUPPORTED, "conv_halo: tile counts beyond the packed launch arguments (row tiles < 2^23, column tiles < 256)");
+    int th = f.th, bn = f.cols, stages = f.code, variant = f.variant;
     const int tiles = a.batch * (a.h_in / th) * (a.w_in / 16) * a.tiles_n;
     dim3 grid(tiles, slices);
-    // `stages` picks the ring depth if that variant is built, otherwise the tile's default (3)
-    bool have = false;
-#define X(th_, bn_, wgm, wgn, st, var, taps, nl) have = have || (th == th_ && bn == bn_ && stages == st && variant == var);
-    MSD_HALO_CFGS(X)
-#undef X
-    if (!have) {   // unknown ring depth -> the tile's default; unknown 8-wave variant -> the 4-wave tile
+    // unknown ring depth -> the tile's default (3); unknown 8-wave variant -> the 4-wave tile
+    if (!halo_built(th, bn, stages, variant)) {
         stages = 3;
-        have = false;
-#define X(th_, bn_, wgm, wgn, st, var, taps, nl) have = have || (th == th_ && bn == bn_ && stages == st && variant == var);
-        MSD_HALO_CFGS(X)
-#undef X
-        if (!have) variant = 0;
+        if (!halo_built(th, bn, stages, variant)) variant = 0;
     }
 #define X(th_, bn_, wgm, wgn, st, var, taps, nl)                                                                          \
     if (th == th_ && bn == bn_ && stages == st && variant == var) {                                                       \
         if (a.nk > a.nk_main)   /* a shortcut operand: the instance with the extra steps */                              \
-            hipLaunchKernelGGL((conv3x3_halo_kernel<th_, bn_, wgm, wgn, st % 30, taps, nl, (st >= 90), true>), grid, dim3((wgm * wgn + nl) * 64), \
-                               (halo_lds<th_, bn_, wgm, wgn, st, taps, nl, true>()), stream, HALO_HOT_ARGS(a), a);                          \
+            hipLaunchKernelGGL((HALO_KERNEL(th_, bn_, wgm, wgn, st, taps, nl, true)), grid, dim3((wgm * wgn + nl) * 64),  \
+                               (halo_lds<th_, bn_, wgm, wgn, st, taps, nl, true>()), stream, HALO_HOT_ARGS(a), a);        \
         else                                                                                                              \
-            hipLaunchKernelGGL((conv3x3_halo_kernel<th_, bn_, wgm, wgn, st % 30, taps, nl, (st >= 90), false>), grid, dim3((wgm * wgn + nl) * 64), \
-                               (halo_lds<th_, bn_, wgm, wgn, st, taps, nl>()), stream, HALO_HOT_ARGS(a), a);                                \
+            hipLaunchKernelGGL((HALO_KERNEL(th_, bn_, wgm, wgn, st, taps, nl, false)), grid, dim3((wgm * wgn + nl) * 64), \
+                               (halo_lds<th_, bn_, wgm, wgn, st, taps, nl>()), stream, HALO_HOT_ARGS(a), a);              \
         return MSD_OK;                                                                                                    \
     }
     MSD_HALO_CFGS(X)

@@ -268,7 +268,7 @@ __global__ __launch_bounds__(NW * 64) void conv_wreg_kernel(CG_HOT_PARAMS, const
 }
 
 // ---- configurations: (BM, NJ, NW, S, KT, WGM); selected by tile_m = 4000 + BM, tile_n = (NW / WGM) x NJ x 16,
-//      stages = S (+ 10 for 8 waves) (+ 20 for two K tiles per stage) ------------------------------------------------------------
+//      stages = S (+ 10 for 8 waves) (+ 20 for two K tiles per stage) (= minsdtf_amd/tuning.py WREG_TILES: tests/test_host_cpu.py test_form_lists_match_the_built_kernels)
 #define MSD_WREG_CFGS(X) \
     X(128, 2, 4, 3, 1, 1)  \
     X(128, 2, 4, 4, 1, 1)  \
@@ -319,21 +319,21 @@ int msd_conv_wreg_init() {
     return MSD_OK;
 }
 
-// 16-column blocks per wave of the configuration a (bm, bn, stages) request selects, 0 if it is not built
-int msd_conv_wreg_nj(int bm, int bn, int stages) {
-#define X(bm_, nj, nw, st, kt, wgm) if (bm == bm_ && bn == (nw / wgm) * nj * 16 && stages == wreg_code(nw, st, kt)) return nj;
+// 16-column blocks per wave of the configuration a decoded (rows, cols, code) request selects, 0 if it is not built
+int msd_conv_wreg_nj(const CGForm& f) {
+#define X(bm_, nj, nw, st, kt, wgm) if (f.rows == bm_ && f.cols == (nw / wgm) * nj * 16 && f.code == wreg_code(nw, st, kt)) return nj;
     MSD_WREG_CFGS(X)
 #undef X
     return 0;
 }
 
 // Launch for an already validated argument block (tiles_m / tiles_n / m_fast / nk_per / nslices set by msd_conv_gemm).
-int msd_conv_wreg_launch(const CGArgs& a, int bm, int bn, int stages, int slices, bool dense, hipStream_t stream) {
+int msd_conv_wreg_launch(const CGArgs& a, const CGForm& f, int slices, bool dense, hipStream_t stream) {
     int rc = msd_conv_wreg_init();
     if (rc) return rc;
     const dim3 grid(a.tiles_m * a.tiles_n, slices);
 #define X(bm_, nj, nw, st, kt, wgm)                                                                                    \
-    if (bm == bm_ && bn == (nw / wgm) * nj * 16 && stages == wreg_code(nw, st, kt)) {                                  \
+    if (f.rows == bm_ && f.cols == (nw / wgm) * nj * 16 && f.code == wreg_code(nw, st, kt)) {                          \
         if (dense)                                                                                                     \
             hipLaunchKernelGGL((conv_wreg_kernel<bm_, nj, nw, st, true, kt, wgm>), grid, dim3(nw * 64), wreg_lds(bm_, nj, nw, st, kt, wgm), stream, CG_HOT_ARGS(a), a); \
         else                                                                                                           \
@@ -342,5 +342,5 @@ int msd_conv_wreg_launch(const CGArgs& a, int bm, int bn, int stages, int slices
     }
     MSD_WREG_CFGS(X)
 #undef X
-    MSD_FAIL(MSD_E_UNSUPPORTED, "conv_wreg: no %d x %d configuration with stages %d", bm, bn, stages);
+    MSD_FAIL(MSD_E_UNSUPPORTED, "conv_wreg: no %d x %d configuration with stages %d", f.rows, f.cols, f.code);
 }

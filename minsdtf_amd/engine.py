@@ -438,7 +438,7 @@ class Emitter:
             wn = wkey or name
             kw.update(w=self.W[wn + ".lnw"], bias=self.W[wn + ".lnb"], ln_in=ln_in[0], ln_in_slots=ln_in[1],
                       ln_colsum=self.W[wn + ".lncs"], ln_eps=EPS, w_layout=self.w_layout(wn + ".lnw"))
-        if tuning.is_wreg(tile_m):   # wreg form (csrc/conv_wreg.hip): reads the fragment-major image of the same matrix
+        if tuning.form_of(tile_m, tile_n, stages).family == "wreg":   # wreg form (csrc/conv_wreg.hip): reads the fragment-major image of the same matrix
             wk = (wkey or name) + (".lnw" if ln_in is not None else ".w")
             frag = getattr(self.W, "fragment_major", None)
             if frag is not None:

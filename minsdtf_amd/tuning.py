@@ -12,14 +12,15 @@ from __future__ import annotations
 import json
 import os
 import re
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "conv_tuning.json")
 _table: Optional[Dict[str, list]] = None
 _families: Optional[Dict[str, Dict[int, list]]] = None   # batch-agnostic key -> {batch: entry}
 
-# (tile_m, tile_n, stages): stages 0 = the tile's default ring depth.  tile_m 1128 / 1256 = halo-tile
-# 3x3 kernel with 8x16 / 16x16 pixel tiles.
+# The configurations the library builds, as (tile_m, tile_n, stages) - form_of() below reads the codes: copies of the X-macro tables of csrc/conv_gemm.hip,
+# conv_halo.hip, conv_wreg.hip and conv_big.hip, kept equal to them by tests/test_host_cpu.py test_form_lists_match_the_built_kernels.
+# stages 0 = the tile's default ring depth.  tile_m 1128 / 1256 = halo-tile 3x3 kernel with 8x16 / 16x16 pixel tiles.
 TILES = ((128, 128, 0), (128, 64, 0), (64, 64, 0), (64, 128, 0), (256, 128, 0),
          (128, 128, 4), (64, 64, 8), (64, 128, 5), (128, 64, 5), (128, 80, 0), (128, 80, 4),
          (64, 64, 14), (128, 64, 13), (64, 128, 13),   # stages 10 + depth: the tile on 8 waves
@@ -55,21 +56,40 @@ BIG_MIN_ROWS = 4096   # rows (M) below which the tuner does not try the big form
 HALO_IMAGE_MIN_ROWS = 256   # ... its halo-image variant (one 16 x 16-pixel tile per sample at the 16x16 level, split-K over chunks)
 
 
-def is_halo(tile_m: int) -> bool:
-    return 1000 <= tile_m < 3000
+# What (tile_m, tile_n, stages) name: the fields of csrc/conv_form.h CGForm (see there) and a short name for reports.  family: "tile" | "halo" |
+# "rowpanel" | "wreg" | "big" | "bighalo"; variant of a wreg form: + 1 = 8 waves, + 2 = two K tiles per stage
+Form = NamedTuple("Form", [("family", str), ("rows", int), ("cols", int), ("code", int), ("chunk_major", bool), ("variant", int), ("th", int), ("name", str)])
 
 
-def is_rowpanel(tile_m: int) -> bool:
-    return 3000 <= tile_m < 4000
+def _family(tile_m: int) -> Optional[str]:   # the tile_m ranges of the forms (None: names no kernel form)
+    return next(fam for base, fam in ((6000, None), (5000, "big"), (4000, "wreg"), (3000, "rowpanel"), (1000, "halo"), (tile_m, "tile")) if tile_m >= base)
 
 
-def is_wreg(tile_m: int) -> bool:
-    """The same ranges as csrc/conv_gemm.hip cg_is_wreg / cg_is_big (tile_m >= 6000 is refused there)."""
-    return 4000 <= tile_m < 5000
+def form_of(tile_m: int, tile_n: int, stages: int = 0) -> Form:
+    """THE decoder of the launch codes on this side of the ABI (csrc/conv_form.h cg_decode_form on the other)."""
+    fam, rows, walk = _family(tile_m), tile_m % 1000, 2 if stages >= 20 else 1 if stages >= 10 else 0
+    if fam is None:
+        raise ValueError(f"tile_m {tile_m} names no kernel form")
+    if fam == "big":
+        name = f"staged halo 16x16 x{tile_n}" if walk == 2 else f"big {rows}x{tile_n}" + (" chunk-major" if walk else "")
+        return Form("bighalo" if walk == 2 else fam, rows, tile_n, stages - 10 * walk, walk > 0, 0, 0, name)
+    if fam == "wreg":
+        return Form(fam, rows, tile_n, stages, False, (1 if stages % 20 >= 10 else 0) + (2 if walk == 2 else 0), 0, f"wreg {rows}x{tile_n}" + (" 2K/stage" if walk == 2 else ""))
+    if fam == "rowpanel":
+        return Form(fam, rows, tile_n, stages, False, 0, 0, f"row panel x{tile_n}")
+    if fam == "halo":
+        step = " rotated 1 tap" if stages >= 150 else " rotated 3 taps" if stages >= 90 else " 3 taps + loaders" if stages >= 60 else " 3 taps/step" if stages >= 30 else ""
+        return Form(fam, rows, tile_n, stages, True, tile_m // 2000, rows // 16, f"halo {rows // 16}x16" + (" (8 waves)" if tile_m >= 2000 else "") + f" x{tile_n}{step}")
+    return Form(fam, tile_m, tile_n, stages, False, walk, 0, f"tile {tile_m}x{tile_n}" + ("", " (8 waves)", " (64x64/wave)")[walk])
 
 
-def is_big(tile_m: int) -> bool:
-    return 5000 <= tile_m < 6000
+is_halo, is_rowpanel, is_wreg, is_big = (lambda tile_m, _fam=fam: _family(tile_m) == _fam for fam in ("halo", "rowpanel", "wreg", "big"))   # by tile_m alone
+
+
+def wreg_nj(tile_m: int, tile_n: int, stages: int) -> int:
+    """16-column blocks per wave of a wreg configuration (csrc/conv_wreg.hip): 4 waves over N, or 8 (stages + 10), except the 256-row tile's 2 x 4 grid."""
+    f = form_of(tile_m, tile_n, stages)
+    return tile_n // 16 // (8 if (f.variant & 1 and f.rows != 256) else 4)
 
 
 # (rows per workgroup + 3000, columns per workgroup): row-panel Dense kernel (csrc/conv_rowpanel.hip) for the LayerNorm-
@@ -238,13 +258,13 @@ def lookup(batch, h_in, w_in, cin, N, ksize, stride, upsample, M, nk, allow_spli
             if int(ent[0]) == 256 and M < 1024:   # (the 256-row tile needs >= 1024 rows)
                 ent = [128] + list(ent[1:])
             if is_big(int(ent[0])) and M < BIG_MIN_ROWS:   # (a 256-row macro tile on a small launch: the same class on small tiles)
-                stg = int(ent[3]) if len(ent) > 4 else 0
-                if stg >= 20 and cx:   # (shortcut-folded conv of the chunk-major class: a small launch runs on the halo-tile kernel, the same bits)
+                big = form_of(int(ent[0]), int(ent[1]), int(ent[3]) if len(ent) > 4 else 0)
+                if big.family == "bighalo" and cx:   # (shortcut-folded conv of the chunk-major class: a small launch runs on the halo-tile kernel, the same bits)
                     if w_in % 16 == 0 and h_in % 8 == 0:
                         ent = [1128, 80 if (N % 80 == 0 and M > 4096) else 64, int(ent[2]), 93 if M > 4096 else 0, 0.0]
-                elif stg >= 10 and not upsample and stride == 1 and w_in % 16 == 0 and h_in % 8 == 0:
+                elif big.chunk_major and not upsample and stride == 1 and w_in % 16 == 0 and h_in % 8 == 0:
                     ent = [1128, 80 if N % 80 == 0 else 64, int(ent[2]), 0, 0.0]
-                elif stg >= 10:   # (an upsampling layer of the chunk-major class: the halo-tile kernel does not take it; the big form walks any M)
+                elif big.chunk_major:   # (an upsampling layer of the chunk-major class: the halo-tile kernel does not take it; the big form walks any M)
                     ent = [5256, 128, int(ent[2]), 10, 0.0]
                 else:
                     ent = [128, 128 if N % 128 == 0 else 64, int(ent[2]), 0, 0.0]
@@ -265,15 +285,11 @@ def numerics_class(ksize: int, tile_m: int, tile_n: int, splitk: int, ln_produce
     the column tile (how the moments are grouped into partials).  `ln_producer` = False for the shapes that never do — the
     GEGLU and q|k|v projections, the keys ending in "n": their column tile orders nothing.  The table holds ONE class per
     layer shape for all batch sizes (tools/tune_conv.py)."""
-    if tile_m >= 6000:
-        raise ValueError(f"tile_m {tile_m} names no kernel form")
-    if is_big(tile_m) and stages >= 10:   # big form walking K chunk-major: the halo-tile kernel's sums
-        return (True, splitk, 0)
-    if is_rowpanel(tile_m):   # row-panel Dense kernel: the tile kernel's bits (a launch it cannot take runs on the 128x64 tile)
-        return (False, splitk, 64 if (ksize == 1 and ln_producer) else 0)
-    if is_wreg(tile_m) or is_big(tile_m):   # wreg / big form: the tile kernel's K walk and epilogue, partials per column tile as requested
-        return (False, splitk, tile_n if (ksize == 1 and ln_producer) else 0)
-    return (is_halo(tile_m), splitk, tile_n if (ksize == 1 and ln_producer) else 0)
+    f = form_of(tile_m, tile_n, stages)   # (raises for a tile_m that names no kernel form)
+    # row-panel Dense kernel: the tile kernel's bits (a launch it cannot take runs on the 128x64 tile); wreg / big form: the tile kernel's
+    # K walk and epilogue, partials per column tile as requested; big form walking K chunk-major: the halo-tile kernel's sums
+    cols = 64 if f.family == "rowpanel" else 0 if f.family in ("big", "bighalo") and f.chunk_major else tile_n
+    return (f.chunk_major, splitk, cols if (ksize == 1 and ln_producer) else 0)
 
 
 def key_is_ln_producer(key: str) -> bool:

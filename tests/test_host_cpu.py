@@ -376,7 +376,7 @@ def test_tuning_table_pins_one_numerics_class_per_layer():
     assert not bad, bad
     # the shortcut-folded 3x3 convs of the 16x16 / 32x32 / 64x64 levels: chunk-major (halo-tile kernel or staged-halo big form) at EVERY batch
     sc = {k: e for k, e in table.items() if re.search(r"x(16x16|32x32|64x64)x\d+->\d+k3s1u0\+x", k)}
-    assert len(sc) >= 36 and all(tuning.is_halo(int(e[0])) or (tuning.is_big(int(e[0])) and int(e[3]) >= 20) for e in sc.values()), sc
+    assert len(sc) >= 36 and all(tuning.form_of(int(e[0]), int(e[1]), int(e[3])).family in ("halo", "bighalo") for e in sc.values()), sc
     # an unmeasured batch lands in the same class as the measured ones; an unknown layer falls back per SAMPLE
     a = tuning.lookup(2, 8, 8, 1280, 1280, 3, 1, False, 128, 180, True)
     b = tuning.lookup(6, 8, 8, 1280, 1280, 3, 1, False, 384, 180, True)
@@ -603,18 +603,18 @@ def _config_is_built(cfg, shape):
     batch, h_in, w_in, cin, N, ks, stride, ups, M, nk, allow_split, cx = shape
     hl, wl = (2 * h_in, 2 * w_in) if ups else (h_in, w_in)
     key = (bm, bn, stg)
+    form = t.form_of(bm, bn, stg)
     if t.is_halo(bm):
-        return key in t.HALO_TILES and ks == 3 and stride == 1 and not ups and w_in % 16 == 0 and h_in % ((bm % 1000) // 16) == 0   # (round 6: with a shortcut operand too)
+        return key in t.HALO_TILES and ks == 3 and stride == 1 and not ups and w_in % 16 == 0 and h_in % form.th == 0   # (round 6: with a shortcut operand too)
     if t.is_rowpanel(bm):
         return ks == 1 and stride == 1 and not ups and not cx and cin in t.ROWPANEL_ROWS and bm in t.ROWPANEL_ROWS[cin] and bn in t.ROWPANEL_COLS and N % bn == 0 and N % 32 == 0
     if t.is_wreg(bm):
-        waves_n = 4 if (stg % 20 < 10 or bm == 4256) else 8
-        return key in t.WREG_TILES and N % 16 == 0 and not (bn > 64 and N <= 64) and (allow_split or (bn // 16 // waves_n) % 2 == 0)
+        return key in t.WREG_TILES and N % 16 == 0 and not (bn > 64 and N <= 64) and (allow_split or t.wreg_nj(bm, bn, stg) % 2 == 0)
     if t.is_big(bm):
         ok = not (bn == 160 and (N % 160 or not allow_split)) and not (bn > 128 and N <= 128) and not (ks == 1 and allow_split and cin == N and not cx)
-        if stg >= 20:
+        if form.family == "bighalo":
             return ok and key in t.BIG_TILES_HALO_IMAGE and ks == 3 and stride == 1 and not (cx and ups) and hl % 16 == 0 and wl % 16 == 0 and M >= t.HALO_IMAGE_MIN_ROWS
-        if stg >= 10:
+        if form.chunk_major:
             return ok and key in t.BIG_TILES_CHUNK_MAJOR and ks == 3 and stride == 1 and not cx
         return ok and key in t.BIG_TILES
     if key not in t.TILES:
@@ -704,3 +704,73 @@ def test_effective_cpus_respects_affinity_and_quota(tmp_path, monkeypatch):
         assert host.fit_torch_threads() == min(before, host.effective_cpus())
     finally:
         torch.set_num_threads(before)
+
+
+def _x_rows(source, macro):
+    """The X(...) rows of one X-macro table of a HIP source, as tuples of ints."""
+    text = open(os.path.join(ROOT, "minsdtf_amd", "csrc", source)).read()
+    m = re.search(r"#define " + macro + r"\(X\)[ \t]*\\\n((?:[ \t]*X\([^)]*\)[ \t]*\\?\n)+)", text)
+    assert m, (source, macro)
+    return [tuple(int(v) for v in row.split(",")) for row in re.findall(r"X\(([^)]*)\)", m.group(1))]
+
+
+def test_form_lists_match_the_built_kernels():
+    """tuning.TILES / HALO_TILES / WREG_TILES / BIG_TILES / BIG_TILES_HALO_IMAGE are hand-kept copies of the X-macro tables the
+    library instantiates its kernels from: this test is what keeps the two sides equal."""
+    from minsdtf_amd import tuning as t
+
+    tiles, first = set(), set()
+    for (_id, bm, bn, _wgm, _wgn, _st, code) in _x_rows("conv_gemm.hip", "MSD_TILE_CFGS"):
+        tiles.add((bm, bn, code if (bm, bn) in first else 0))   # the first entry of a tile size is its default: stages 0
+        first.add((bm, bn))
+    # halo: depth 3 is every tile's default (stages 0); variant 1 = the tile on 8 waves, tile_m 2000 + pixels
+    halo = {((2000 if var else 1000) + th * 16, bn, 0 if st == 3 else st) for (th, bn, _wgm, _wgn, st, var, _taps, _nl) in _x_rows("conv_halo.hip", "MSD_HALO_CFGS")}
+    src = open(os.path.join(ROOT, "minsdtf_amd", "csrc", "conv_wreg.hip")).read()
+    m = re.search(r"constexpr int wreg_code\(int nw, int s, int kt\) \{ return s \+ \(nw == (\d+) \? (\d+) : 0\) \+ \(kt == (\d+) \? (\d+) : 0\); \}", src)
+    assert m, "conv_wreg.hip: wreg_code is the single definition of the wreg stages code"
+    nw8, add_nw, kt2, add_kt = (int(v) for v in m.groups())
+    wreg = {(4000 + bm, (nw // wgm) * nj * 16, st + (add_nw if nw == nw8 else 0) + (add_kt if kt == kt2 else 0))
+            for (bm, nj, nw, st, kt, wgm) in _x_rows("conv_wreg.hip", "MSD_WREG_CFGS")}
+    big = {(5000 + bm, bn, code) for (bm, bn, _wgm, _wgn, _ih, _jh, _nb, code) in _x_rows("conv_big.hip", "MSD_BIG_CFGS")}
+    bighalo = {(5256, bn, 20 + code) for (bn, _wgm, _wgn, _nbw, code) in _x_rows("conv_big.hip", "MSD_BIGHALO_CFGS")}
+    for name, built, listed, count in (("TILES", tiles, t.TILES, 19), ("HALO_TILES", halo, t.HALO_TILES, 27), ("WREG_TILES", wreg, t.WREG_TILES, 20),
+                                       ("BIG_TILES", big, t.BIG_TILES, 8), ("BIG_TILES_HALO_IMAGE", bighalo, t.BIG_TILES_HALO_IMAGE, 3)):
+        assert len(listed) == len(set(listed)) == len(built) == count, (name, len(listed), len(built))
+        assert set(listed) == built, (name, sorted(set(listed) ^ built))
+    assert {(bm, bn, stg - 10) for (bm, bn, stg) in t.BIG_TILES_CHUNK_MAJOR} <= big, t.BIG_TILES_CHUNK_MAJOR
+
+
+def test_form_of_covers_the_code_space():
+    """tuning.form_of is the one decoder of (tile_m, tile_n, stages) on the Python side: consistent with the is_* predicates on every
+    built configuration and every row of the table, the numerics class of one example per family and walk, the family borders."""
+    from minsdtf_amd import tuning as t
+
+    def family_by_predicates(tm):
+        return "halo" if t.is_halo(tm) else "rowpanel" if t.is_rowpanel(tm) else "wreg" if t.is_wreg(tm) else "big" if t.is_big(tm) else "tile"
+
+    table = json.load(open(os.path.join(ROOT, "minsdtf_amd", "conv_tuning.json")))
+    codes = list(t.TILES + t.HALO_TILES + t.WREG_TILES + t.BIG_TILES + t.BIG_TILES_CHUNK_MAJOR + t.BIG_TILES_HALO_IMAGE)
+    codes += [(int(e[0]), int(e[1]), int(e[3]) if len(e) > 4 else 0) for e in table.values()]
+    assert len(codes) == 82 + len(table) and len(table) >= 306
+    for (tm, tn, stg) in codes:
+        f = t.form_of(tm, tn, stg)
+        assert isinstance(f, t.Form) and f.name and f.cols == tn
+        assert f.family.replace("bighalo", "big") == family_by_predicates(tm), (tm, tn, stg, f)
+        assert (f.family == "bighalo") == (t.is_big(tm) and stg >= 20) and f.chunk_major == (t.is_halo(tm) or (t.is_big(tm) and stg >= 10)), (tm, tn, stg, f)
+    assert t.form_of(5256, 160, 11)[:6] == ("big", 256, 160, 1, True, 0) and t.form_of(5256, 128, 21)[:6] == ("bighalo", 256, 128, 1, True, 0)
+    assert t.form_of(2128, 64, 33)[:7] == ("halo", 128, 64, 33, True, 1, 8) and t.form_of(1256, 80, 5).th == 16
+    assert t.form_of(64, 64, 14).variant == 1 and t.form_of(128, 128, 24).variant == 2 and t.form_of(3128, 96, 0)[:3] == ("rowpanel", 128, 96)
+    assert t.form_of(4128, 128, 13).name == "wreg 128x128" and t.form_of(1128, 80, 93).name == "halo 8x16 x80 rotated 3 taps"
+    # (chunk-major, split-K slices, column tile of the LayerNorm-fold partials): ksize, tile_m, tile_n, splitk, ln_producer, stages
+    for args, cls in (((1, 128, 64, 1, True, 13), (False, 1, 64)), ((3, 128, 128, 4, True, 4), (False, 4, 0)), ((1, 64, 64, 2, False, 0), (False, 2, 0)),
+                      ((3, 1128, 80, 3, True, 93), (True, 3, 0)), ((1, 3128, 160, 1, True, 0), (False, 1, 64)), ((1, 3128, 160, 1, False, 0), (False, 1, 0)),
+                      ((1, 4064, 128, 2, True, 23), (False, 2, 128)), ((3, 4128, 64, 2, True, 3), (False, 2, 0)),
+                      ((1, 5256, 160, 1, True, 1), (False, 1, 160)), ((3, 5256, 128, 1, True, 0), (False, 1, 0)),
+                      ((3, 5256, 256, 2, True, 10), (True, 2, 0)), ((3, 5256, 128, 2, True, 20), (True, 2, 0))):
+        assert t.numerics_class(*args) == cls, (args, t.numerics_class(*args), cls)
+    for tm, fam in ((999, "tile"), (1000, "halo"), (2999, "halo"), (3000, "rowpanel"), (3999, "rowpanel"), (4000, "wreg"), (4999, "wreg"),
+                    (5000, "big"), (5999, "big")):
+        assert t.form_of(tm, 64, 0).family == fam == family_by_predicates(tm), (tm, fam)
+    for call in (lambda: t.form_of(6000, 64, 0), lambda: t.numerics_class(1, 6000, 64, 1)):
+        with pytest.raises(ValueError):
+            call()

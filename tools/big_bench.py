@@ -38,7 +38,7 @@ def main():
             continue
         tm, tn, sk, stg = int(ent[0]), int(ent[1]), int(ent[2]), int(ent[3])
         best_t, res_t, flop = tune_conv.tune_one(s, iters=20, only=lambda t: t == (tm, tn, stg), sks_only=[sk])
-        best_b, res_b, _ = tune_conv.tune_one(s, iters=20, only=lambda t: t[0] >= 5000, sks_only=[sk])
+        best_b, res_b, _ = tune_conv.tune_one(s, iters=20, only=lambda t: tuning.is_big(t[0]), sks_only=[sk])
         if best_b is None:
             continue
         us_t, us_b = best_t[0], best_b[0]

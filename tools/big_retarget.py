@@ -71,7 +71,7 @@ def main():
                 ent = table[key]
                 tm, tn, sk, stg = int(ent[0]), int(ent[1]), int(ent[2]), int(ent[3]) if len(ent) > 4 else 0
                 best_t, _, flop = tune_conv.tune_one(s, iters=args.iters, only=lambda t: t == (tm, tn, stg), sks_only=[sk])
-                best_b, _, _ = tune_conv.tune_one(s, iters=args.iters, only=lambda t: t[0] >= 5000 and t[2] >= 20, sks_only=[sk])
+                best_b, _, _ = tune_conv.tune_one(s, iters=args.iters, only=lambda t: tuning.form_of(*t).family == "bighalo", sks_only=[sk])
                 if best_t is None or best_b is None:
                     plan = None
                     break
@@ -114,7 +114,7 @@ def main():
                     ok_all = False   # (already chunk-major)
                     break
                 best_t, _, flop = tune_conv.tune_one(s, iters=args.iters, only=lambda t: t == (tm, tn, stg), sks_only=[sk])
-                best_b, _, _ = tune_conv.tune_one(s, iters=args.iters, only=lambda t: t[0] >= 5000 and t[2] >= 10, sks_only=[sk])
+                best_b, _, _ = tune_conv.tune_one(s, iters=args.iters, only=lambda t: tuning.is_big(t[0]) and tuning.form_of(*t).chunk_major, sks_only=[sk])
                 if best_t is None or best_b is None:
                     ok_all = False
                     break
@@ -146,13 +146,13 @@ def main():
         if M < (tuning.HALO_IMAGE_MIN_ROWS if args.halo_image else tuning.BIG_MIN_ROWS) or N < 64:
             continue
         tm, tn, sk, stg = int(ent[0]), int(ent[1]), int(ent[2]), int(ent[3]) if len(ent) > 4 else 0
-        if tuning.is_big(tm) and not (args.halo_image and stg < 20):
+        if tuning.is_big(tm) and not (args.halo_image and tuning.form_of(tm, tn, stg).family != "bighalo"):
             continue
         cls = tune_conv.numerics_class(s, tm, tn, sk, stg)
         best_t, _, flop = tune_conv.tune_one(s, iters=args.iters, only=lambda t: t == (tm, tn, stg), sks_only=[sk])
         if best_t is None:
             continue
-        ok = lambda t: t[0] >= 5000 and (t[2] >= 20 or not args.halo_image) and tune_conv.numerics_class(s, t[0], t[1], sk, t[2]) == cls   # noqa: E731
+        ok = lambda t: tuning.is_big(t[0]) and (tuning.form_of(*t).family == "bighalo" or not args.halo_image) and tune_conv.numerics_class(s, t[0], t[1], sk, t[2]) == cls   # noqa: E731
         best_b, res_b, _ = tune_conv.tune_one(s, iters=args.iters, only=ok, sks_only=[sk])
         if best_b is None:
             continue

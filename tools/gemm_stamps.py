@@ -29,7 +29,7 @@ def main():
     from minsdtf_amd import _lib
 
     _lib.LIB_PATH = os.path.join(ROOT, "tools", "_build", "libminsdtf_hip_stamps.so")
-    from minsdtf_amd import ops
+    from minsdtf_amd import ops, tuning
 
     lib = _lib.load()
     lib.msd_init()
@@ -55,8 +55,9 @@ def main():
         res = torch.randn(M, N, device=dev).to(torch.bfloat16)
         out = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
         wsf = torch.empty(max(1, sk * M * N), device=dev, dtype=torch.float32)
-        wreg = 4000 <= tm < 5000   # wreg form: tile 4000 + rows, fragment-major weights
-        big = tm >= 5000           # big form (conv_big.hip): tile 5000 + rows
+        form = tuning.form_of(tm, tn, stg)
+        wreg = form.family == "wreg"                # fragment-major weights
+        big = form.family in ("big", "bighalo")   # conv_big.hip
         if wreg:
             from minsdtf_amd import packing
 
@@ -67,9 +68,8 @@ def main():
         for c in calls:          # the last call's stamps survive; weights rotate so they come from HBM
             c(st.cuda_stream)
         torch.cuda.synchronize()
-        halo = 1000 <= tm < 3000
-        bm = (tm % 1000) if tm >= 1000 else tm
-        nwg = ((M + bm - 1) // bm) * ((N + tn - 1) // tn) * sk
+        halo = form.family == "halo"
+        nwg = ((M + form.rows - 1) // form.rows) * ((N + tn - 1) // tn) * sk
         buf = np.zeros(16 * 8192, np.uint64)
         rc = (lib.msd_debug_stamps_halo if halo else lib.msd_debug_stamps_wreg if wreg else lib.msd_debug_stamps_big if big else lib.msd_debug_stamps)(buf.ctypes.data, buf.size)
         assert rc == 0, rc

@@ -12,24 +12,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def form_name(tm, tn, sk, stg):
-    from minsdtf_amd import tuning as t
-
-    if t.is_halo(tm):
-        kind = {1128: "halo 8x16", 2128: "halo 8x16 (8 waves)", 1256: "halo 16x16"}[tm]
-        extra = " 3 taps/step" if 30 <= stg < 60 else " 3 taps + loaders" if 60 <= stg < 90 else " rotated 3 taps" if 90 <= stg < 150 else " rotated 1 tap" if stg >= 150 else ""
-        s = f"{kind} x{tn}{extra}"
-    elif t.is_rowpanel(tm):
-        s = f"row panel x{tn}"
-    elif t.is_wreg(tm):
-        s = f"wreg {tm - 4000}x{tn}" + (" 2K/stage" if stg >= 20 else "")
-    elif t.is_big(tm):
-        s = (f"staged halo 16x16 x{tn}" if stg >= 20 else f"big {tm - 5000}x{tn} chunk-major" if stg >= 10 else f"big {tm - 5000}x{tn}")
-    else:
-        s = f"tile {tm}x{tn}" + (" (8 waves)" if 10 <= stg < 20 else " (64x64/wave)" if stg >= 20 else "")
-    return s + (f", split-K {sk}" if sk > 1 else "")
-
-
 def kind_of(sh):
     batch, h_in, w_in, cin, N, ks, stride, ups, M, nk, allow_split, cx = sh
     if ks == 3:
@@ -71,7 +53,7 @@ def main():
                     lvl = f"{h_in}x{w_in}"
                 key = (lvl, kind_of(sh))
                 cfg = tuning.lookup(*sh)
-                rows.setdefault(key, {}).setdefault(nb, collections.Counter())[form_name(*cfg)] += 1
+                rows.setdefault(key, {}).setdefault(nb, collections.Counter())[tuning.form_of(cfg[0], cfg[1], cfg[3]).name + (f", split-K {cfg[2]}" if cfg[2] > 1 else "")] += 1
         hdr = " | ".join(f"fused batch {nb} ({nb // 2 if net == 'UNet' else nb} image{'s' if (nb // 2 if net == 'UNet' else nb) > 1 else ''} per GPU)" for nb in nbs)
         print(f"## {net}\n\n| level | layer kind | {hdr} |\n|---|---|" + "---|" * len(nbs))
         for (lvl, kind), per in rows.items():

@@ -102,13 +102,6 @@ def collect_shapes(quick=False):
     return uniq
 
 
-def wreg_nj(bm, bn, stg):
-    """16-column blocks per wave of a wreg configuration (csrc/conv_wreg.hip MSD_WREG_CFGS): 4 waves over N, or 8 (stages code
-    10 + depth), except the 256-row tile whose 8 waves are a 2 x 4 grid."""
-    waves_n = 4 if (stg % 20 < 10 or bm == 4256) else 8
-    return bn // 16 // waves_n
-
-
 def tune_one(shape, iters=10, only=None, sks_only=None):
     from minsdtf_amd import ops, tuning
 
@@ -131,7 +124,7 @@ def tune_one(shape, iters=10, only=None, sks_only=None):
     results = []
     cands = list(tuning.TILES)
     if ks == 3 and stride == 1 and not ups and w_in % 16 == 0:  # halo-tile kernel (tile_m = 1000 + pixels per tile; round 6: with a shortcut operand too)
-        cands += [t for t in tuning.HALO_TILES if h_in % ((t[0] % 1000) // 16) == 0]
+        cands += [t for t in tuning.HALO_TILES if h_in % tuning.form_of(*t).th == 0]
     if ks == 1 and stride == 1 and not ups and not cx and cin in tuning.ROWPANEL_ROWS and N % 32 == 0:   # row-panel Dense kernel
         cands += [(rows, cols, 0) for rows in tuning.ROWPANEL_ROWS[cin] for cols in tuning.ROWPANEL_COLS if N % cols == 0]
     if N % 16 == 0 and not os.environ.get("MSD_TUNE_NO_WREG"):   # wreg form (fragment-major weights straight to registers)
@@ -148,11 +141,13 @@ def tune_one(shape, iters=10, only=None, sks_only=None):
         cands = [t for t in cands if only(t)]
     frag = None
     for (bm, bn, stg) in cands:
-        if 4000 <= bm < 5000 and allow_split is False and wreg_nj(bm, bn, stg) % 2:
+        form = tuning.form_of(bm, bn, stg)
+        wreg, big = form.family == "wreg", form.family in ("big", "bighalo")
+        if wreg and allow_split is False and tuning.wreg_nj(bm, bn, stg) % 2:
             continue   # (the 'n' shapes include GEGLU, which pairs the two blocks of a wave)
-        if bm >= 5000 and allow_split is False and bn == 160:
+        if big and allow_split is False and bn == 160:
             continue   # (5 blocks per wave: no x | gate pairs)
-        if bm < 3000:
+        if form.family in ("tile", "halo"):
             if bm == 256 and M < 1024:
                 continue
             if bn == 128 and N <= 64:
@@ -162,24 +157,23 @@ def tune_one(shape, iters=10, only=None, sks_only=None):
             if bn == 160 and (N % 160 or N < 1280):
                 continue
         sks = [1]
-        if allow_split and (bm < 3000 or bm >= 4000):
+        if allow_split and form.family != "rowpanel":
             # candidates from the PER-SAMPLE shape, so every batch of a layer is measured on the same set of slice counts
-            bme = bm % 1000 if bm >= 1000 else bm
-            tiles = ((M // batch + bme - 1) // bme) * ((N + bn - 1) // bn)
-            kmax = (cin // 64) if (1000 <= bm < 3000 or (bm >= 5000 and stg >= 10)) else nk // 4   # the halo kernel (and the chunk-major big form) split over 64-channel chunks
+            tiles = ((M // batch + form.rows - 1) // form.rows) * ((N + bn - 1) // bn)
+            kmax = (cin // 64) if form.chunk_major else nk // 4   # the halo kernel (and the chunk-major big form) split over 64-channel chunks
             sks += [s for s in (2, 3, 4, 6, 8, 12, 16) if s <= kmax and tiles * s <= 2048 and tiles < 512]
         if sks_only is not None:
             sks = [s for s in sks_only if s == 1 or allow_split]
         for sk in sks:
             wsf = torch.empty(max(1, sk * M * N), device=dev, dtype=torch.float32) if sk > 1 else None
-            if 4000 <= bm < 5000 and frag is None:
+            if wreg and frag is None:
                 from minsdtf_amd import packing
 
                 frag = [packing.fragment_major(w) for w in ws_]
             calls = [ops.conv_gemm(a0=x, w=w, out=out, batch=batch, h_in=h_in, w_in=w_in, c0=cin, N=N, ksize=ks, stride=stride,
                                    upsample=ups, bias=bias, workspace=wsf, workspace_floats=0 if wsf is None else wsf.numel(),
-                                   splitk=sk, tile_m=bm, tile_n=bn, stages=stg, a2=xx, c2=cx, w_layout=2 if 4000 <= bm < 5000 else 0)
-                     for w in (frag if 4000 <= bm < 5000 else ws_)]
+                                   splitk=sk, tile_m=bm, tile_n=bn, stages=stg, a2=xx, c2=cx, w_layout=2 if wreg else 0)
+                     for w in (frag if wreg else ws_)]
             for c in calls[:2]:
                 c(st.cuda_stream)
             torch.cuda.synchronize()

@@ -40,7 +40,7 @@ def main():
         cur = table[key]
         ctm, ctn, csk, cstg = int(cur[0]), int(cur[1]), int(cur[2]), int(cur[3]) if len(cur) > 4 else 0
         t_cur, _, flop = tune_conv.tune_one(s, iters=args.iters, only=lambda t: t == (ctm, ctn, cstg), sks_only=[csk])
-        in_class = lambda t: tuning.is_halo(t[0]) or (tuning.is_big(t[0]) and t[2] >= 20)   # noqa: E731
+        in_class = lambda t: tuning.form_of(*t).family in ("halo", "bighalo")   # noqa: E731
         best, results, _ = tune_conv.tune_one(s, iters=args.iters, only=in_class, sks_only=[sk])
         halo = [r for r in results if tuning.is_halo(r[1])]
         big = [r for r in results if tuning.is_big(r[1])]

@@ -133,7 +133,7 @@ def measure(shape, iters):
     # (i) this library, the table's entry
     bm, bn, sk, stg = tuning.lookup(batch, h_in, w_in, cin, N, ks, stride, ups, M, nk, allow_split, cx)
     wsf = torch.empty(max(1, sk * M * N), device=dev, dtype=torch.float32) if sk > 1 else None
-    wl_ = 2 if 4000 <= bm < 5000 else 1
+    wl_ = 2 if tuning.is_wreg(bm) else 1
     packed = [packing.fragment_major(w) if wl_ == 2 else packing.chunk_major(w) for w in ws_]
     calls = [ops.conv_gemm(a0=x, w=w, out=out, batch=batch, h_in=h_in, w_in=w_in, c0=cin, N=N, ksize=ks, stride=stride, upsample=ups,
                            bias=bias, workspace=wsf, workspace_floats=0 if wsf is None else wsf.numel(), splitk=sk, tile_m=bm,

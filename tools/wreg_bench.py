@@ -13,10 +13,6 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def form(bm):
-    return "wreg" if bm >= 4000 else "rowpanel" if bm >= 3000 else "halo" if bm >= 1000 else "tile"
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fused-batch", type=int, default=2)
@@ -40,7 +36,7 @@ def main():
         allr[key] = [list(r) for r in results]
         per = {}
         for us, bm, bn, sk, stg in results:
-            f = form(bm)
+            f = tuning.form_of(bm, bn, stg).family
             if f not in per:
                 per[f] = (us, bm, bn, sk, stg)
         other = min((v for f, v in per.items() if f != "wreg"), default=None)
@@ -51,8 +47,8 @@ def main():
         if w:
             line += f"   wreg/other {w[0] / other[0]:.2f}  [{flop / w[0] / 1e6:.0f} TF/s]"
         print(line, flush=True)
-        wl = [r for r in results if r[1] >= 4000][:6]
-        print("      wreg: " + "  ".join(f"{bm - 4000}x{bn} s{stg} k{sk}: {us:.1f}" for us, bm, bn, sk, stg in wl), flush=True)
+        wl = [r for r in results if tuning.is_wreg(r[1])][:6]
+        print("      wreg: " + "  ".join(f"{tuning.form_of(bm, bn, stg).rows}x{bn} s{stg} k{sk}: {us:.1f}" for us, bm, bn, sk, stg in wl), flush=True)
     print(f"sum over one step's launches: best non-wreg {tot['best_other'] / 1e3:.3f} ms, best of all forms {tot['best_any'] / 1e3:.3f} ms")
     if args.json:
         with open(args.json, "w") as f:
