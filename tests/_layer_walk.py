@@ -1,0 +1,220 @@
+"""The tensor-less walk of the launch plans, shared by the CPU and GPU tests (and by tools/tune_conv.py): every
+msd_conv_gemm launch the emitters record for a network at a latent size, with what decides its arithmetic and code path.
+
+The walk hooks engine.Plan.rec and leaves tuning.lookup in place, so a record holds the configuration the engine really
+chose (table row, nearest measured batch, or tuning.shape_config), the epilogue it asked for and the weight layout it would
+read.  Nothing is launched; ops.conv_gemm_ln_slots loads the built library (LayerNorm-fold producers ask it for their slot
+count).  Not a conftest: plain helpers, imported by name."""
+import collections
+
+# what one recorded ops.conv_gemm call keeps.  Presence flags are booleans; split = the q|k|v^T / k|v^T epilogue (ns0, ns1 its
+# column counts); ln_in_slots / ln_out_slots = row-moment partials per row read / written (0: none)
+Launch = collections.namedtuple("Launch", [
+    "name", "batch", "h_in", "w_in", "c0", "c1", "N", "ksize", "stride", "upsample", "pad", "pad_end", "c2", "c3",
+    "tile_m", "tile_n", "splitk", "stages", "w_layout",
+    "act", "out_dtype", "bias", "residual", "rowvec", "step_ptr", "ln_in", "ln_in_slots", "ln_out", "ln_out_slots", "split", "ns0", "ns1"])
+
+# a layer signature: the launch without its batch, its configuration and its name
+SIG_FIELDS = ("h_in", "w_in", "c0", "c1", "N", "ksize", "stride", "upsample", "pad", "pad_end", "c2", "c3",
+              "act", "out_dtype", "bias", "residual", "rowvec", "step_ptr", "ln_in", "ln_out", "split", "ns0", "ns1")
+Sig = collections.namedtuple("Sig", SIG_FIELDS)
+
+# (network, fused batch, latent height, latent width).  TUNED: what tools/tune_conv.py measures and BASELINE.md benchmarks, in the tuner's order
+TUNED_WALKS = (("unet", 2, 64, 64), ("vae", 1, 64, 64), ("unet", 4, 64, 64), ("unet", 8, 64, 64), ("unet", 2, 96, 96), ("unet", 1, 64, 64),
+               ("vae", 4, 64, 64), ("vae", 1, 96, 96), ("controlnet", 2, 64, 64), ("vae_enc", 1, 64, 64))
+# ... plus the 96 x 96 UNet at fused batch 1 (nearest-batch / shape_config), fused batches 6 and 10 at 64 x 64 (nearest batch with
+# its is_big / 256-row rewrites) and the 80 x 80 UNet at fused batch 2 (no table row at all: shape_config)
+ALL_WALKS = TUNED_WALKS + (("unet", 1, 96, 96), ("unet", 6, 64, 64), ("unet", 10, 64, 64), ("unet", 2, 80, 80))
+
+
+class _Tensor:
+    """Stands in for a device tensor / buffer while walking the topology."""
+    ptr = 0
+
+    def at(self, off):
+        return self
+
+
+class _AnyWeights(dict):
+    """Every weight "exists" (so the folded layer forms are the ones walked), none is real.  layout / fragment_major as
+    packing.PackedWeights has them: the models keep every MFMA matrix chunk-major and hand the wreg form a fragment-major copy."""
+
+    def __contains__(self, k):
+        return True
+
+    def __missing__(self, k):
+        return _Tensor()
+
+    def layout(self, key):
+        from minsdtf_amd import engine
+
+        return 1 if engine.W_CHUNK_MAJOR else 0
+
+    def fragment_major(self, key):
+        return _Tensor()
+
+
+def _launch(kw):
+    pad = kw.get("pad")
+    pad = (1 if kw.get("ksize", 1) == 3 else 0) if pad is None else pad
+    pad_end = kw.get("pad_end")
+    split = kw.get("split")
+    return Launch(name=kw.get("name", ""), batch=kw["batch"], h_in=kw["h_in"], w_in=kw["w_in"], c0=kw["c0"], c1=kw.get("c1", 0), N=kw["N"],
+                  ksize=kw.get("ksize", 1), stride=kw.get("stride", 1), upsample=bool(kw.get("upsample", False)), pad=pad,
+                  pad_end=pad if pad_end is None else pad_end, c2=kw.get("c2", 0), c3=kw.get("c3", 0),
+                  tile_m=kw.get("tile_m", 0), tile_n=kw.get("tile_n", 0), splitk=kw.get("splitk", 1), stages=kw.get("stages", 0),
+                  w_layout=kw.get("w_layout", 0), act=kw.get("act", 0), out_dtype=kw.get("out_dtype", 0),
+                  bias=kw.get("bias") is not None, residual=kw.get("residual") is not None, rowvec=kw.get("rowvec") is not None,
+                  step_ptr=kw.get("rowvec") is not None, ln_in=kw.get("ln_in") is not None, ln_in_slots=kw.get("ln_in_slots", 0),
+                  ln_out=kw.get("ln_out") is not None, ln_out_slots=kw.get("ln_out_slots", 0), split=split is not None,
+                  ns0=split[0] if split else 0, ns1=split[1] if split else 0)
+
+
+def walk(what, nb, h, w):
+    """Every ops.conv_gemm call the emitters record for `what` ("unet" | "controlnet" | "vae" | "vae_enc") at fused batch nb and
+    latent size h x w, in recording order, as Launch records."""
+    from minsdtf_amd import engine, ops
+    from minsdtf_amd import weights as wtab
+
+    out = []
+    orig = engine.Plan.rec
+
+    def rec(self, fn, **kw):
+        if fn is ops.conv_gemm:
+            out.append(_launch(kw))
+        return orig(self, fn, **kw)
+
+    engine.Plan.rec = rec
+    try:
+        p = engine.Plan("cpu")
+        e = engine.Emitter(p, _AnyWeights())
+        T = _Tensor
+        if what in ("unet", "controlnet"):
+            layers = engine.UNET_ATTN_LAYERS if what == "unet" else engine.ENCODER_ATTN_LAYERS
+            ctx = engine.Act(p.alloc(nb * 77 * 768 * 2), nb, 77, 1, 768)
+            kv = engine.emit_context_kv(e, ctx, layers, p)
+            temb = (T(), 0, 0, engine.temb_columns(what == "controlnet"))
+            if what == "unet":
+                engine.emit_unet(e, T(), nb, nb, h, w, temb, kv, 77, T(), None)
+            else:
+                outs = [p.act(nb, h >> lv, w >> lv, ch) for lv, ch in zip((0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3), wtab.UNET_SKIP_CH + (1280,))]
+                engine.emit_controlnet(e, T(), nb, nb, h, w, temb, kv, 77, p.act(nb, h, w, 320), outs)
+        elif what == "vae":
+            engine.emit_decoder(e, T(), nb, h, w, T(), 0)
+        elif what == "vae_enc":
+            engine.emit_encoder(e, T(), nb, 8 * h, 8 * w, T())
+        else:
+            raise ValueError(what)
+    finally:
+        engine.Plan.rec = orig
+    return out
+
+
+def out_hw(l):
+    hl, wl = (2 * l.h_in, 2 * l.w_in) if l.upsample else (l.h_in, l.w_in)
+    return (hl + l.pad + l.pad_end - l.ksize) // l.stride + 1, (wl + l.pad + l.pad_end - l.ksize) // l.stride + 1
+
+
+def lookup_args(l):
+    """The arguments Emitter.conv handed tuning.lookup for this launch: (batch, h_in, w_in, cin, N, ksize, stride, upsample, M, nk,
+    allow_split, cx)."""
+    from minsdtf_amd import ops
+
+    ho, wo = out_hw(l)
+    cin, cx = l.c0 + l.c1, l.c2 + l.c3
+    return (l.batch, l.h_in, l.w_in, cin, l.N, l.ksize, l.stride, l.upsample, l.batch * ho * wo, l.ksize * l.ksize * (cin // 64) + cx // 64,
+            not (l.split or l.act == ops.ACT_GEGLU), cx)
+
+
+def walk_shapes(nb, h, w, what="unet"):
+    """The tuner's view of a walk: the tuning.lookup arguments of every launch that went through Emitter.conv."""
+    return [lookup_args(l) for l in walk(what, nb, h, w) if l.tile_m or l.tile_n]
+
+
+def shape_key(l):
+    from minsdtf_amd import tuning
+
+    a = lookup_args(l)
+    return tuning.shape_key(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], a[10], a[11])
+
+
+def signature(l):
+    return Sig(*(getattr(l, f) for f in SIG_FIELDS))
+
+
+def sig_id(s):
+    """'64x64x640->320k3s1u0+x960 resid rowvec': the shape key without its batch, the operand boundaries where a tensor is a
+    concat, then the epilogue."""
+    from minsdtf_amd import ops, tuning
+
+    key = tuning.shape_key(0, s.h_in, s.w_in, s.c0 + s.c1, s.N, s.ksize, s.stride, s.upsample, not (s.split or s.act == ops.ACT_GEGLU), s.c2 + s.c3)
+    words = [key.split("x", 1)[1]]
+    if s.c1:
+        words.append(f"in{s.c0}|{s.c1}")
+    if s.c3:
+        words.append(f"sc{s.c2}|{s.c3}")
+    if s.pad != (1 if s.ksize == 3 else 0) or s.pad_end != s.pad:
+        words.append(f"pad{s.pad},{s.pad_end}")
+    words += [n for n, on in (("bias", s.bias), ("resid", s.residual), ("rowvec", s.rowvec), ("ln_in", s.ln_in), ("ln_out", s.ln_out)) if on]
+    if s.split:
+        words.append(f"split{s.ns0}|{s.ns1}")
+    act = {ops.ACT_NONE: None, ops.ACT_SILU: "silu", ops.ACT_GEGLU: "geglu", ops.ACT_QUICK_GELU: "quick_gelu"}[s.act]
+    if act:
+        words.append(act)
+    if s.out_dtype == ops.OUT_F32:
+        words.append("f32")
+    return " ".join(words)
+
+
+# Layer signatures over ALL_WALKS.  tests/test_layer_cases_cpu.py keeps this number equal to what the walk finds, tests/test_layer_shapes_gpu.py
+# asserts that it ran this many cases: a signature the engine starts to record cannot stay untested unnoticed.
+EXPECTED_CASES = 222
+
+_cases = None
+
+
+def cases(walks=ALL_WALKS):
+    """{signature: {batch: [distinct Launch records, names dropped]}} over `walks`, in first-seen order: one GPU test case per key."""
+    global _cases
+    if walks is ALL_WALKS and _cases is not None:
+        return _cases
+    out = collections.OrderedDict()
+    for (what, nb, h, w) in walks:
+        for l in walk(what, nb, h, w):
+            per = out.setdefault(signature(l), {}).setdefault(l.batch, [])
+            l = l._replace(name="")
+            if l not in per:
+                per.append(l)
+    if walks is ALL_WALKS:
+        _cases = out
+    return out
+
+
+def config_is_built(cfg, shape):
+    """The (tile_m, tile_n, stages) of a launch configuration names a kernel the library builds AND that takes this shape (the
+    tuner's candidate filters, tools/tune_conv.py): the wreg / big / staged-halo forms fail the launch otherwise."""
+    from minsdtf_amd import tuning as t
+
+    bm, bn, sk, stg = cfg
+    batch, h_in, w_in, cin, N, ks, stride, ups, M, nk, allow_split, cx = shape
+    hl, wl = (2 * h_in, 2 * w_in) if ups else (h_in, w_in)
+    key = (bm, bn, stg)
+    form = t.form_of(bm, bn, stg)
+    if t.is_halo(bm):
+        return key in t.HALO_TILES and ks == 3 and stride == 1 and not ups and w_in % 16 == 0 and h_in % form.th == 0   # (round 6: with a shortcut operand too)
+    if t.is_rowpanel(bm):
+        return ks == 1 and stride == 1 and not ups and not cx and cin in t.ROWPANEL_ROWS and bm in t.ROWPANEL_ROWS[cin] and bn in t.ROWPANEL_COLS and N % bn == 0 and N % 32 == 0
+    if t.is_wreg(bm):
+        return key in t.WREG_TILES and N % 16 == 0 and not (bn > 64 and N <= 64) and (allow_split or t.wreg_nj(bm, bn, stg) % 2 == 0)
+    if t.is_big(bm):
+        ok = not (bn == 160 and (N % 160 or not allow_split)) and not (bn > 128 and N <= 128) and not (ks == 1 and allow_split and cin == N and not cx)
+        if form.family == "bighalo":
+            return ok and key in t.BIG_TILES_HALO_IMAGE and ks == 3 and stride == 1 and not (cx and ups) and hl % 16 == 0 and wl % 16 == 0 and M >= t.HALO_IMAGE_MIN_ROWS
+        if form.chunk_major:
+            return ok and key in t.BIG_TILES_CHUNK_MAJOR and ks == 3 and stride == 1 and not cx
+        return ok and key in t.BIG_TILES
+    if key not in t.TILES:
+        return False
+    if -(-N // bn) >= 256:   # column tiles travel in 8 bits of a packed launch argument (cg_hot_ok)
+        return False
+    return not (bm == 256 and M < 1024) and not (bn == 128 and N <= 64) and not (bn == 80 and (N % 80 or not allow_split)) and not (bn == 160 and (N % 160 or N < 1280))

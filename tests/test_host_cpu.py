@@ -555,73 +555,7 @@ def test_release_library_refuses_experiment_modes():
         assert b"instrumented build" in lib.msd_last_error()
 
 
-def _walk_shapes(nb, h, w, what="unet"):
-    """Every msd_conv_gemm shape of a network at a latent size, through the emitters (tensor-less weights): the tuner's walk."""
-    from minsdtf_amd import engine, tuning
-
-    rec = []
-    orig = tuning.lookup
-
-    def hook(batch, h_in, w_in, cin, N, ksize, stride, upsample, M, nk, allow_split, cx=0):
-        rec.append((batch, h_in, w_in, cin, N, ksize, stride, bool(upsample), M, nk, bool(allow_split), cx))
-        return tuning.heuristic(M, N, nk, allow_split)
-
-    class AnyW(dict):
-        def __contains__(self, k):
-            return True
-
-        def __missing__(self, k):
-            return None
-
-    class T:
-        ptr = 0
-
-        def at(self, off):
-            return self
-
-    tuning.lookup = hook
-    try:
-        p = engine.Plan("cpu")
-        e = engine.Emitter(p, AnyW())
-        if what == "unet":
-            ctx = engine.Act(p.alloc(nb * 77 * 768 * 2), nb, 77, 1, 768)
-            kv = engine.emit_context_kv(e, ctx, engine.UNET_ATTN_LAYERS, p)
-            engine.emit_unet(e, T(), nb, nb, h, w, (T(), 0, 0, engine.temb_columns(False)), kv, 77, T(), None)
-        else:
-            engine.emit_decoder(e, T(), nb, h, w, T(), 0)
-    finally:
-        tuning.lookup = orig
-    return rec
-
-
-def _config_is_built(cfg, shape):
-    """The (tile_m, tile_n, stages) of a launch configuration names a kernel the library builds AND that takes this shape (the
-    tuner's candidate filters, tools/tune_conv.py): the wreg / big / staged-halo forms fail the launch otherwise."""
-    from minsdtf_amd import tuning as t
-
-    bm, bn, sk, stg = cfg
-    batch, h_in, w_in, cin, N, ks, stride, ups, M, nk, allow_split, cx = shape
-    hl, wl = (2 * h_in, 2 * w_in) if ups else (h_in, w_in)
-    key = (bm, bn, stg)
-    form = t.form_of(bm, bn, stg)
-    if t.is_halo(bm):
-        return key in t.HALO_TILES and ks == 3 and stride == 1 and not ups and w_in % 16 == 0 and h_in % form.th == 0   # (round 6: with a shortcut operand too)
-    if t.is_rowpanel(bm):
-        return ks == 1 and stride == 1 and not ups and not cx and cin in t.ROWPANEL_ROWS and bm in t.ROWPANEL_ROWS[cin] and bn in t.ROWPANEL_COLS and N % bn == 0 and N % 32 == 0
-    if t.is_wreg(bm):
-        return key in t.WREG_TILES and N % 16 == 0 and not (bn > 64 and N <= 64) and (allow_split or t.wreg_nj(bm, bn, stg) % 2 == 0)
-    if t.is_big(bm):
-        ok = not (bn == 160 and (N % 160 or not allow_split)) and not (bn > 128 and N <= 128) and not (ks == 1 and allow_split and cin == N and not cx)
-        if form.family == "bighalo":
-            return ok and key in t.BIG_TILES_HALO_IMAGE and ks == 3 and stride == 1 and not (cx and ups) and hl % 16 == 0 and wl % 16 == 0 and M >= t.HALO_IMAGE_MIN_ROWS
-        if form.chunk_major:
-            return ok and key in t.BIG_TILES_CHUNK_MAJOR and ks == 3 and stride == 1 and not cx
-        return ok and key in t.BIG_TILES
-    if key not in t.TILES:
-        return False
-    if -(-N // bn) >= 256:   # column tiles travel in 8 bits of a packed launch argument (cg_hot_ok)
-        return False
-    return not (bm == 256 and M < 1024) and not (bn == 128 and N <= 64) and not (bn == 80 and (N % 80 or not allow_split)) and not (bn == 160 and (N % 160 or N < 1280))
+from _layer_walk import config_is_built as _config_is_built, walk_shapes as _walk_shapes   # noqa: E402  (the shared tensor-less walk of the emitters)
 
 
 def test_shape_config_reaches_the_fast_forms_at_untuned_sizes():

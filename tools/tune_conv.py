@@ -28,77 +28,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def collect_shapes(quick=False):
-    from minsdtf_amd import engine, tuning
-    from minsdtf_amd import weights as wtab
+    """(batch, h_in, w_in, cin, N, ksize, stride, upsample, allow_split, cx) of every distinct launch of the tuned networks, sizes and
+    batches: the tensor-less walk of the emitters the tests use (tests/_layer_walk.py), so the tuner and the suite cannot drift apart."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import _layer_walk as LW
 
-    rec = []
-    orig = tuning.lookup
-
-    def hook(batch, h_in, w_in, cin, N, ksize, stride, upsample, M, nk, allow_split, cx=0):
-        rec.append((batch, h_in, w_in, cin, N, ksize, stride, bool(upsample), bool(allow_split), cx))
-        return tuning.heuristic(M, N, nk, allow_split)
-
-    tuning.lookup = hook
-    engine.tuning.lookup = hook
-    class _AnyW(dict):   # every weight "exists" (so the folded layer forms are the ones walked), none is real
-        def __contains__(self, k):
-            return True
-
-        def __missing__(self, k):
-            return None
-
-    W = _AnyW()
-
-    class _T:  # stands in for device tensors / buffers while walking the topology
-        ptr = 0
-
-        def at(self, off):
-            return self
-
-    def unet(nb, h, T=77):
-        p = engine.Plan("cpu")
-        e = engine.Emitter(p, W)
-        ctx = engine.Act(p.alloc(nb * T * 768 * 2), nb, T, 1, 768)
-        kv = engine.emit_context_kv(e, ctx, engine.UNET_ATTN_LAYERS, p)
-        cols = engine.temb_columns(False)
-        engine.emit_unet(e, _T(), nb, nb, h, h, (_T(), 0, 0, cols), kv, T, _T(), None)
-
-    def controlnet(nb, h, T=77):
-        p = engine.Plan("cpu")
-        e = engine.Emitter(p, W)
-        ctx = engine.Act(p.alloc(nb * T * 768 * 2), nb, T, 1, 768)
-        kv = engine.emit_context_kv(e, ctx, engine.ENCODER_ATTN_LAYERS, p)
-        cols = engine.temb_columns(True)
-        outs = [p.act(nb, h >> l, h >> l, ch) for l, ch in zip((0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3), wtab.UNET_SKIP_CH + (1280,))]
-        engine.emit_controlnet(e, _T(), nb, nb, h, h, (_T(), 0, 0, cols), kv, T, p.act(nb, h, h, 320), outs)
-
-    def vae(b, h):
-        p = engine.Plan("cpu")
-        e = engine.Emitter(p, W)
-        engine.emit_decoder(e, _T(), b, h, h, _T(), 0)
-
-    def vae_enc(b, h):
-        p = engine.Plan("cpu")
-        e = engine.Emitter(p, W)
-        engine.emit_encoder(e, _T(), b, 8 * h, 8 * h, _T())
-
-    unet(2, 64)
-    vae(1, 64)
-    if not quick:
-        for nb in (4, 8):
-            unet(nb, 64)
-        unet(2, 96)
-        unet(1, 64)
-        vae(4, 64)
-        vae(1, 96)
-        controlnet(2, 64)
-        vae_enc(1, 64)
-    tuning.lookup = orig
-    engine.tuning.lookup = orig
     uniq = []
-    for r in rec:
-        if r not in uniq:
-            uniq.append(r)
+    for (what, nb, h, w) in (LW.TUNED_WALKS[:2] if quick else LW.TUNED_WALKS):
+        for a in LW.walk_shapes(nb, h, w, what):
+            r = a[:8] + (a[10], a[11])
+            if r not in uniq:
+                uniq.append(r)
     return uniq
 
 
