@@ -466,6 +466,45 @@ typedef struct MsdLoraMerge {
 
 MSD_API int msd_lora_merge(const MsdLoraMerge* p, msd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * msd_latent_resample — separable resampling of the fp32 NHWC latent (C = 4) fused with a re-noise: the hand-off between the
+ * two passes of a hires job (minsdtf_amd/hires.py).  An addition to ABI 12: nothing else changed.
+ *
+ *   out[b,y,x,:] = a * sum_j wy[y].w[j] * ( sum_i wx[x].w[i] * in[b, wy[y].idx[j], wx[x].idx[i], :] ) + s * noise[b,y,x,:]
+ *
+ *   in:    fp32 [batch][h_in][w_in][4];   out: fp32 [batch][h_out][w_out][4] (must not overlap in)
+ *   noise: fp32 [batch][h_out][w_out][4], or NULL: the term is skipped and `s` is ignored
+ *   wx:    MsdResampleRow [w_out], wy: MsdResampleRow [h_out] — one row of four taps per output coordinate of the axis, computed
+ *          by the host in float64 and stored as fp32 (hires.taps / hires.pack_rows: the semantics of torch's interpolate with
+ *          align_corners = False for nearest / nearest-exact / bilinear / bicubic).  Indices are already clamped to the source
+ *          (replicate border, clamped per tap); unused taps have weight 0 and any valid index.  (The kernel clamps every index to
+ *          the source once more, so a bad table reads the wrong pixel, never outside `in`.)
+ * Order of the sums (pinned; every product and sum is fp32, FMAs are single-rounded):
+ *   r_j = wx.w[0] * p_j0;  r_j = fma(wx.w[i], p_ji, r_j) for i = 1, 2, 3        (p_ji = the source pixel of taps j, i)
+ *   v   = wy.w[0] * r_0;   v   = fma(wy.w[j], r_j, v)    for j = 1, 2, 3
+ *   out = a * v  without noise;  out = fma(s, noise, a * v)  with it
+ * per channel.  One output pixel is one lane's float4; a sample's bits do not depend on the batch it runs in.
+ * All five pointers 16-byte aligned; batch in 1 .. 65535 (one grid row per sample), sizes in 1 .. 16384 with
+ * h_out >= h_in, w_out >= w_in, fewer than 2^31 output elements.
+ * Argument errors (a NULL struct / in / out / wx / wy, bad sizes, a misaligned pointer, out overlapping in) return
+ * MSD_E_ARG without launching.  Nothing is allocated; the launch is stream-ordered and capturable. */
+typedef struct MsdResampleRow {
+    int32_t idx[4];
+    float w[4];
+} MsdResampleRow;
+
+typedef struct MsdLatentResample {
+    const float* in;
+    float* out;
+    const float* noise;          /* or NULL */
+    const MsdResampleRow* wx;    /* [w_out] */
+    const MsdResampleRow* wy;    /* [h_out] */
+    int32_t batch, h_in, w_in, h_out, w_out;
+    float a, s;
+} MsdLatentResample;
+
+MSD_API int msd_latent_resample(const MsdLatentResample* p, msd_stream_t stream);
+
 /* msd_add_bf16 — out = a + b elementwise on bf16. n % 8 == 0. */
 MSD_API int msd_add_bf16(const void* a, const void* b, void* out, int64_t n, msd_stream_t stream);
 /* msd_add_f32_bf16 — out = bf16(a + b), a / out bf16, b fp32, summed in fp32 (may run in place, out == a).  The ControlNet

@@ -116,6 +116,18 @@ class MsdLoraMerge(C.Structure):
     _fields_ = [("jobs", C.c_void_p), ("jobs_dev", C.c_void_p), ("num_jobs", C.c_int32)]
 
 
+class MsdResampleRow(C.Structure):
+    _fields_ = [("idx", C.c_int32 * 4), ("w", C.c_float * 4)]
+
+
+class MsdLatentResample(C.Structure):
+    _fields_ = [
+        ("in_", C.c_void_p), ("out", C.c_void_p), ("noise", C.c_void_p), ("wx", C.c_void_p), ("wy", C.c_void_p),
+        ("batch", C.c_int32), ("h_in", C.c_int32), ("w_in", C.c_int32), ("h_out", C.c_int32), ("w_out", C.c_int32),
+        ("a", C.c_float), ("s", C.c_float),   # hires hand-off (an addition to ABI 12)
+    ]
+
+
 LORA_ROWS_PER_BLOCK = 8   # csrc/lora.hip LR_ROWS: MsdLoraJob.first_block counts workgroups of this many rows
 
 # every symbol include/minsdtf_hip.h declares: name -> (restype, argtypes)
@@ -141,6 +153,7 @@ SYMBOLS = {
     "msd_cfg_step": (C.c_int, [C.POINTER(MsdCfgStep), C.c_void_p]),
     "msd_sampler_step": (C.c_int, [C.POINTER(MsdSamplerStep), C.c_void_p]),
     "msd_lora_merge": (C.c_int, [C.POINTER(MsdLoraMerge), C.c_void_p]),
+    "msd_latent_resample": (C.c_int, [C.POINTER(MsdLatentResample), C.c_void_p]),
     "msd_add_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_add_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

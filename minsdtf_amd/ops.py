@@ -192,6 +192,17 @@ def sampler_step(*, eps, latent, coef, step_ptr, denoised_prev, batch, n, num_st
     return Call(lib.msd_sampler_step, (C.byref(s),), name, keep=s)
 
 
+def latent_resample(*, x, out, wx, wy, batch, h_in, w_in, h_out, w_out, a=1.0, s=0.0, noise=None, name="latent_resample") -> Call:
+    """msd_latent_resample: out = a * resample(x) + s * noise on the fp32 NHWC latent (C = 4).  wx / wy: the device copies of the
+    per-axis tap rows (hires.pack_rows: int32 [w_out][8] / [h_out][8]); noise fp32 [batch][h_out][w_out][4] or None."""
+    lib = _lib.load()
+    r = _lib.MsdLatentResample()
+    r.in_, r.out, r.noise, r.wx, r.wy = _p(x), _p(out), _p(noise), _p(wx), _p(wy)
+    r.batch, r.h_in, r.w_in, r.h_out, r.w_out = int(batch), int(h_in), int(w_in), int(h_out), int(w_out)
+    r.a, r.s = float(a), float(s)
+    return Call(lib.msd_latent_resample, (C.byref(r),), name, keep=r)
+
+
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:
     lib = _lib.load()
     return Call(lib.msd_add_bf16, (_p(a), _p(b), _p(out), n), name)

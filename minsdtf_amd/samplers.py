@@ -177,11 +177,12 @@ def host_step(row, x, e, prev, z=None):
     return out, d
 
 
-def draw_step_noise(batch: int, num_steps: int, h: int, w: int, seed=None) -> np.ndarray:
+def draw_step_noise(batch: int, num_steps: int, h: int, w: int, seed=None, stream_key: int = 1) -> np.ndarray:
     """The stochastic samplers' N(0,1) draws for the GLOBAL batch, sample-major: (batch, num_steps, h, w, 4) float32, one
-    block per row of the table (executed or not).  With a seed: default_rng([seed, 1]); without: numpy's global stream (as the
-    TCD sampler's).  Sample b's draws are the b-th block whatever the batch size."""
+    block per row of the table (executed or not).  With a seed: default_rng([seed, stream_key]) (1: a job's own loop; 3: the
+    second pass of a hires job; 2 is the hires re-noise draw, hires.draw_noise); without: numpy's global stream (as the TCD
+    sampler's).  Sample b's draws are the b-th block whatever the batch size."""
     shape = (int(batch), int(num_steps), int(h), int(w), 4)
     if seed is None:
         return np.random.randn(*shape).astype(np.float32)
-    return np.random.default_rng([int(seed), 1]).standard_normal(shape).astype(np.float32)
+    return np.random.default_rng([int(seed), int(stream_key)]).standard_normal(shape).astype(np.float32)

@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib, engine, ops
+from . import hires as hires_mod
 from . import samplers as smp
 from . import weights as wtab
 from .models import (ControlNet, DiffusionModel, HintNet, ImageDecoder, ImageEncoder, TextClipEmbedding, TextEncoder, _BoundPlan,
@@ -330,6 +331,8 @@ class DenoiseEngine:
     def prepare(self, contexts: Dict[str, np.ndarray], noise: np.ndarray, scheduler: Scheduler, timesteps,
                 start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None) -> None:
         """Upload the per-call inputs and run the preparation plan.  Every array may be a host array or a (device) tensor.
+        noise = None: the start latent is already in `self.latent` (written there by stream-ordered device work queued before
+        this call: the hand-off of a hires job), nothing is uploaded for it.
         inpaint = (init_latent (1,h,w,4), noise (B,h,w,4), latent mask (h,w) or (h,w,1)) for an engine built with
         inpaint=True; step_noise = (B, num_steps, h*w*4) TCD draws made by the caller (sharded runs: the slice of the
         draws for the global batch) instead of the draws made here.  An engine built with a sampler takes its
@@ -350,7 +353,8 @@ class DenoiseEngine:
             self.inpaint["mask"].copy_(torch.from_numpy(np.ascontiguousarray(np.broadcast_to(m, (self.h, self.w, 4))).reshape(-1)))
         for tag, arr in contexts.items():
             self.ctx_in[tag].copy_(_f32_tensor(arr))
-        self.latent.copy_(_f32_tensor(noise))
+        if noise is not None:
+            self.latent.copy_(_f32_tensor(noise))
         # the schedule's tables: uploaded when the schedule changes, not per call (pageable host -> device copies make the
         # host wait for the stream, which keeps it from queueing this job behind the previous one's last kernels)
         # (keyed by the table's VALUES: a scheduler with other betas / final alpha / eta on the same timesteps is another schedule)
@@ -442,12 +446,13 @@ class StableDiffusionBase:
     # ---- public entry points (reference :84-139)
     def text_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                       embedding=None, negative_embedding=None, seed=None, control_net_image=None, guidance_rescale=0.7,
-                      callback=None, **kw):
+                      callback=None, hires=None, **kw):
+        """``hires``: None, or a hires.HiresSpec / dict for the two-pass hires fix (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
                                    negative_embedding=negative_embedding, control_net_image=control_net_image,
-                                   guidance_rescale=guidance_rescale, callback=callback, **kw)
+                                   guidance_rescale=guidance_rescale, callback=callback, hires=hires, **kw)
 
     def image_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
@@ -677,12 +682,29 @@ class StableDiffusionBase:
     def generate_image(self, encoded_text, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        diffusion_noise=None, seed=None, negative_embedding=None, control_net_image=None, inpaint_mask=None,
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
-                       callback=None, host_loop=False, return_latent=False, sampler=None):
+                       callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
         rank denoises + decodes its contiguous slice and every rank returns the whole gathered batch (minsdtf_amd/dist.py).
-        Default (False): the reference's meaning, this process runs all `batch_size` samples."""
+        Default (False): the reference's meaning, this process runs all `batch_size` samples.
+        ``hires`` (a hires.HiresSpec or a dict of its fields; txt2img only): the two-pass hires fix - `num_steps` steps at the
+        pipeline's own size, then the latent is resampled to the target size and re-noised on the device (msd_latent_resample)
+        and the last int(steps * strength + 0.5) steps of a `steps`-step schedule run at the target size; the result has the
+        target size.  ``hires_noise``: the re-noise draw (B, H2/8, W2/8, 4) (default: default_rng([seed, 2]), or numpy's global
+        stream without a seed).  `callback` counts through both passes."""
+        job = hires_mod.parse(hires, self.img_height, self.img_width, num_steps)   # (ValueError for a bad description)
+        if job is None and hires_noise is not None:
+            raise ValueError("`hires_noise` without `hires`")
+        if job is not None:
+            refused = [n for n, v in (("reference_image", reference_image), ("inpaint_mask", inpaint_mask),
+                                      ("control_net_image", control_net_image)) if v is not None]
+            if host_loop:
+                refused.append("host_loop=True")
+            if self.active_tcd:
+                refused.append("a TCD pipeline (active_tcd=True)")
+            if refused:
+                raise ValueError(f"hires is text-to-image on the device loop only: it cannot be combined with {', '.join(refused)}")
         if diffusion_noise is not None and seed is not None:
             raise ValueError("`diffusion_noise` and `seed` should not both be passed to `generate_image`. `seed` is only "
                              "used to generate diffusion noise when it's not already user-specified.")
@@ -693,6 +715,9 @@ class StableDiffusionBase:
         context = self._batch_of(encoded_text, B, 2)
         unconditional_context = self._negative_context(negative_prompt, negative_embedding, B)
         noise = self._get_initial_diffusion_noise(B, seed) if diffusion_noise is None else self._batch_of(diffusion_noise, B, 3)
+        if job is not None:
+            return self._generate_hires(job, spec, context, unconditional_context, noise, hires_noise, num_steps,
+                                        float(unconditional_guidance_scale), float(guidance_rescale), seed, callback, return_latent)
         self.scheduler.set_timesteps(num_steps)
 
         # image_to_image (reference :410-418,559-568): encode the picture, run only the last int(n*strength+0.5) steps,
@@ -797,6 +822,10 @@ class StableDiffusionBase:
         sharded = world > 1 or (getattr(self, "shard_batch", False) and mdist.collectives_on())
         out = mdist.generate_sharded(local, context, unconditional_context, start_latent, dev,
                                      per_sample=list(per_sample.values()), shared=list(shared.values()), shard=sharded)
+        return self._to_host(out, dev, sharded)
+
+    def _to_host(self, out, dev, sharded):
+        """The job's device result -> host array, behind the cluster-GroupNorm give-up check."""
         flags = engine.gn_sync_flags(dev)   # (None without a cluster-GroupNorm plan on `dev`) queued behind the job, read with its D2H
         host = out.cpu().numpy()
         if flags is not None:   # a cluster GroupNorm that gave up - on ANY rank of a sharded job: raise, never return that image
@@ -805,29 +834,123 @@ class StableDiffusionBase:
             engine.check_gn_sync(flags.cpu(), device=dev, group_wide=sharded)
         return host
 
-    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None) -> DenoiseEngine:
+    # ---- hires fix: two passes with an on-device hand-off (minsdtf_amd/hires.py)
+    def _unet_for(self, height, width) -> DiffusionModel:
+        """The UNet at another image size: a view that shares the base model's packed weights (HipModel.share_weights: no
+        second copy, one LoRA master, so set_loras reaches every size).  Kept per size; shared again when the base's weights
+        were replaced."""
+        base = self.diffusion_model
+        if (height, width) == (self.img_height, self.img_width):
+            return base
+        base._require_weights()
+        views = self.__dict__.setdefault("_unet_views", {})
+        view, seen = views.get((height, width), (None, None))
+        if view is None:
+            view = DiffusionModel(height, width, device=base.device, name=f"{base.name}.{height}x{width}")
+        if seen != base.weights_version:
+            view.share_weights(base)
+            views[(height, width)] = (view, base.weights_version)
+        return view
+
+    def _hires_taps(self, h1, w1, h2, w2, mode, dev):
+        """Device copies of the two tap tables of a hand-off (uploaded once per shape and upscaler)."""
+        cache = self.__dict__.setdefault("_hires_tap_cache", {})
+        key = (h1, w1, h2, w2, mode, str(dev))
+        if key not in cache:
+            cache[key] = tuple(torch.from_numpy(hires_mod.pack_rows(*hires_mod.taps(n_in, n_out, mode))).to(dev)
+                               for n_in, n_out in ((w1, w2), (h1, h2)))
+        return cache[key]
+
+    def _generate_hires(self, job, spec, context, unconditional_context, noise, hires_noise, num_steps, g, phi, seed, callback,
+                        return_latent):
+        """Pass 1 (the txt2img job at the pipeline's own size, no decode) -> one msd_latent_resample launch from the pass-1 engine's
+        latent into the pass-2 engine's, scaled and re-noised with the pass-2 entry rates -> pass 2 at the target size -> decode.
+        Both engines stay resident, so a repeated job constructs nothing and captures nothing."""
+        from . import dist as mdist
+
+        B = noise.shape[0]
+        h1, w1, h2, w2 = self.img_height // 8, self.img_width // 8, job.height // 8, job.width // 8
+        a2, s2, start2, run2 = hires_mod.entry(self.scheduler, spec, job.steps, job.strength)
+        zh = hires_mod.draw_noise(B, h2, w2, seed) if hires_noise is None else self._batch_of(hires_noise, B, 3)
+        if tuple(zh.shape) != (B, h2, w2, 4):
+            raise ValueError(f"hires_noise has shape {tuple(zh.shape)}, the {job.height}x{job.width} latent of batch {B} is {(B, h2, w2, 4)}")
+        per_sample = {"hires_noise": zh}   # name -> array of the GLOBAL batch; insertion order = argument order of `local`
+        sched1 = sched2 = None
+        if spec is not None:
+            sched1, sched2 = smp.schedule(spec, self.scheduler, num_steps), smp.schedule(spec, self.scheduler, job.steps)
+            if spec.stochastic:   # the per-step draws of the global batch, sample-major: pass 1 [seed, 1], pass 2 [seed, 3]
+                per_sample["z1"] = smp.draw_step_noise(B, num_steps, h1, w1, seed).reshape(B, num_steps, -1)
+                per_sample["z2"] = smp.draw_step_noise(B, job.steps, h2, w2, seed, stream_key=3).reshape(B, job.steps, -1)
+        sname = None if spec is None else spec.name
+        dev = getattr(self, "device", None) or self.diffusion_model.device
+        names = list(per_sample)
+        callback2 = None if callback is None else (lambda i: callback(num_steps + i))
+
+        def local(c, u, z, *rest):
+            """This rank's slice: both engines -> pass 1 -> hand-off -> pass 2 -> decode; returns a device tensor."""
+            a = dict(zip(names, rest))
+            b = int(z.shape[0])
+            unet2 = self._unet_for(job.height, job.width)
+            shapes = [dict(steps=num_steps, unet=None), dict(steps=job.steps, unet=unet2)]
+            keys = [self._engine_key(b, c.shape[1], u.shape[1], s["steps"], g, phi, False, sampler=sname, unet=s["unet"]) for s in shapes]
+            eng1, eng2 = (self._engine(b, c.shape[1], u.shape[1], s["steps"], g, phi, False, sampler=sname, unet=s["unet"], job_keys=keys)
+                          for s in shapes)
+            self.scheduler.set_timesteps(num_steps)
+            eng1.prepare(eng1.contexts(u, c), z, self.scheduler, self.scheduler.timesteps, 0, step_noise=a.get("z1"), sampler=sched1)
+            eng1.run_steps(num_steps, callback)
+            wx, wy = self._hires_taps(h1, w1, h2, w2, job.upscaler, eng1.latent.device)
+            zh_dev = _f32_tensor(a["hires_noise"]).to(eng1.latent.device).contiguous()
+            if zh_dev.data_ptr() % 16:   # (a slice of a packed broadcast buffer: the kernel reads 16-byte vectors)
+                zh_dev = zh_dev.clone()
+            ops.latent_resample(x=eng1.latent, out=eng2.latent, wx=wx, wy=wy, batch=b, h_in=h1, w_in=w1, h_out=h2, w_out=w2,
+                                a=a2, s=s2, noise=zh_dev)(torch.cuda.current_stream().cuda_stream)
+            self.scheduler.set_timesteps(job.steps)
+            eng2.prepare(eng2.contexts(u, c), None, self.scheduler, self.scheduler.timesteps, start2, step_noise=a.get("z2"),
+                         sampler=sched2)
+            eng2.run_steps(run2, callback2)
+            if return_latent:
+                return eng2.latent
+            return self.image_decoder.decode_to_uint8(eng2.latent)
+
+        sharded = (mdist.world_size() if getattr(self, "shard_batch", False) else 1) > 1 or \
+            (getattr(self, "shard_batch", False) and mdist.collectives_on())
+        out = mdist.generate_sharded(local, context, unconditional_context, noise, dev, per_sample=list(per_sample.values()),
+                                     shard=sharded)
+        return self._to_host(out, dev, sharded)
+
+    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None) -> tuple:
         # the engine's plans (and captured hipGraphs) hold raw addresses of the packed weights: a set_weights() /
         # load_synthetic() / LoRA reload on any of the models it was built from must retire it
-        wver = (self.diffusion_model.weights_version,) + ((self.control_net.weights_version, self.hint_net.weights_version)
-                                                           if control else ())
+        base = self.diffusion_model
+        unet = base if unet is None else unet
+        wver = (unet.weights_version,) + ((self.control_net.weights_version, self.hint_net.weights_version) if control else ())
         key = (B, tc, tu, steps, g, phi, control, self.denoise_streams, inpaint, self.active_tcd, wver, engine.GN_EPOCH, sampler)
+        return key if unet is base else key + ((unet.h, unet.w),)   # (a hires job's second size: a view of the same weights)
+
+    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None, job_keys=None) -> DenoiseEngine:
+        """The resident engine of this shape, built if need be.  `unet`: the UNet of another size (a hires job's second pass);
+        `job_keys`: the keys of every engine the current job uses (default: this one alone).  The engines' arenas are the big
+        allocations, so whatever the current job does not need goes BEFORE anything is built: a re-recording (another shape,
+        new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than the job's own engines - one for a
+        plain job, two for a hires job."""
+        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, sampler, unet)
+        keep = {key} | set(job_keys or ())
+        if any(k not in keep for k in self._engines):
+            import gc
+
+            for k, old in self._engines.items():
+                if k not in keep:
+                    old.release_graphs()
+            old = None
+            self._engines = {k: e for k, e in self._engines.items() if k in keep}
+            gc.collect()
         eng = self._engines.get(key)
         if eng is None:
-            # one resident engine (its arenas are the big allocations): the old one goes BEFORE the new one is built, so that a
-            # re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for both
-            if self._engines:
-                import gc
-
-                for old in self._engines.values():
-                    old.release_graphs()
-                old = None
-                self._engines = {}
-                gc.collect()
-            eng = DenoiseEngine(self.diffusion_model, B, tc, tu, steps, g, phi,
+            eng = DenoiseEngine(self.diffusion_model if unet is None else unet, B, tc, tu, steps, g, phi,
                                 control_net=self.control_net if control else None,
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
                                 streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=sampler)
-            self._engines = {key: eng}  # one resident engine: its arenas are the big allocations
+            self._engines[key] = eng
         return eng
 
     def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None):

@@ -57,14 +57,15 @@ def schedule(name, n):
     return t, np.append(s, 0.0)
 
 
-def sample(name, n, model, x_k, z):
+def sample(name, n, model, x_k, z, start=0):
     """k-diffusion's sample_dpmpp_2m / sample_dpmpp_2m_sde (eta 1, midpoint) / sample_euler_ancestral (eta 1), float64.
-    model(x_k, i) -> denoised.  Returns (final x_k, [x_k after every step])."""
+    model(x_k, i) -> denoised.  Returns (final x_k, [x_k after every step]).  `start` > 0: the sampler is handed sigmas[start:]
+    (k-diffusion's img2img: x_k is the latent at sigma[start], the first executed step has no previous estimate)."""
     t, s = schedule(name, n)
     kind = name[:-len("_karras")] if name.endswith("_karras") else name
     x = np.asarray(x_k, dtype=np.float64)
     old, h_last, trace = None, None, []
-    for i in range(n):
+    for i in range(start, n):
         d = model(x, i, t[i], s[i])
         if kind == "euler_a":
             s_up = min(s[i + 1], np.sqrt(s[i + 1] ** 2 * (s[i] ** 2 - s[i + 1] ** 2) / s[i] ** 2))
