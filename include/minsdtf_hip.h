@@ -505,6 +505,46 @@ typedef struct MsdLatentResample {
 
 MSD_API int msd_latent_resample(const MsdLatentResample* p, msd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * msd_tile_consensus — the per-step hand-off of a tiled-diffusion job (MultiDiffusion; minsdtf_amd/tiled.py): the
+ * views of a canvas are batch rows of the denoise engine's latent, and after every sampler step each canvas pixel - and every
+ * view's entry for it - becomes the weighted mean of the stepped views that cover it.  An addition to ABI 12: nothing else changed.
+ *
+ *   tiles:  fp32 [batch * rows * cols][th][tw][4], row b * (rows * cols) + r * cols + c (sample-major, views row-major); view
+ *           (r, c) covers canvas rows ys[r] .. ys[r] + th - 1 and columns xs[c] .. xs[c] + tw - 1.  Read and rewritten in place.
+ *   canvas: fp32 [batch][H][W][4] (must not overlap tiles)
+ *   wy:     fp32 [th], wx: fp32 [tw] - separable blend weights, > 0, computed by the host in float64 (tiled.weight_row)
+ *
+ * mode 0 (consensus), per canvas pixel (Y, X) of a sample, per channel, over the covering views in ascending (r, c) order:
+ *   one cover:   out = x_v                                       (copied bit for bit)
+ *   otherwise:   w_v  = wy[Y - ys[r]] * wx[X - xs[c]]            (fp32, rounded once)
+ *                acc  = fma(w_v, x_v, acc),  wsum = wsum + w_v   (both from 0, fp32, the FMA single-rounded)
+ *                out  = acc / wsum                               (one IEEE division)
+ *   canvas[Y, X] = out, and every covering view's entry = out.
+ * mode 1 (gather): every covering view's entry = canvas[Y, X] (plain copies; the canvas is only read).
+ *
+ * One canvas pixel of one sample is one lane's float4.  Each tile entry belongs to exactly one canvas pixel, so the in-place
+ * update is free of races and needs no atomics; nothing couples two pixels, so a sample's bits do not depend on its batch.
+ * The offsets travel by value (in the kernel arguments: a captured graph holds them).  Checked on the host, without a device:
+ * tiles / canvas / wy / wx non-NULL and 16-byte aligned; batch in 1 .. 65535, th, tw >= 1, H >= th, W >= tw; rows, cols in
+ * 1 .. MSD_TILE_MAX_VIEWS; per axis the offsets start at 0, end at L - t and ascend strictly in steps of at most t (every canvas
+ * pixel is covered); tiles and canvas do not overlap; fewer than 2^31 elements in each; mode 0 or 1.  Argument errors return
+ * MSD_E_ARG without launching.  Nothing is allocated; the launch is stream-ordered and capturable. */
+#define MSD_TILE_MAX_VIEWS 64
+
+typedef struct MsdTileConsensus {
+    float* tiles;
+    float* canvas;
+    int32_t ys[MSD_TILE_MAX_VIEWS];   /* [rows] used */
+    int32_t xs[MSD_TILE_MAX_VIEWS];   /* [cols] used */
+    int32_t rows, cols, th, tw, H, W, batch;
+    const float* wy;             /* [th] */
+    const float* wx;             /* [tw] */
+    int32_t mode;                /* 0: consensus, 1: gather */
+} MsdTileConsensus;
+
+MSD_API int msd_tile_consensus(const MsdTileConsensus* p, msd_stream_t stream);
+
 /* msd_add_bf16 — out = a + b elementwise on bf16. n % 8 == 0. */
 MSD_API int msd_add_bf16(const void* a, const void* b, void* out, int64_t n, msd_stream_t stream);
 /* msd_add_f32_bf16 — out = bf16(a + b), a / out bf16, b fp32, summed in fp32 (may run in place, out == a).  The ControlNet

@@ -128,6 +128,17 @@ class MsdLatentResample(C.Structure):
     ]
 
 
+TILE_MAX_VIEWS = 64   # MSD_TILE_MAX_VIEWS
+
+
+class MsdTileConsensus(C.Structure):
+    _fields_ = [
+        ("tiles", C.c_void_p), ("canvas", C.c_void_p), ("ys", C.c_int32 * TILE_MAX_VIEWS), ("xs", C.c_int32 * TILE_MAX_VIEWS),
+        ("rows", C.c_int32), ("cols", C.c_int32), ("th", C.c_int32), ("tw", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("batch", C.c_int32), ("wy", C.c_void_p), ("wx", C.c_void_p), ("mode", C.c_int32),   # tiled diffusion (an addition to ABI 12)
+    ]
+
+
 LORA_ROWS_PER_BLOCK = 8   # csrc/lora.hip LR_ROWS: MsdLoraJob.first_block counts workgroups of this many rows
 
 # every symbol include/minsdtf_hip.h declares: name -> (restype, argtypes)
@@ -154,6 +165,7 @@ SYMBOLS = {
     "msd_sampler_step": (C.c_int, [C.POINTER(MsdSamplerStep), C.c_void_p]),
     "msd_lora_merge": (C.c_int, [C.POINTER(MsdLoraMerge), C.c_void_p]),
     "msd_latent_resample": (C.c_int, [C.POINTER(MsdLatentResample), C.c_void_p]),
+    "msd_tile_consensus": (C.c_int, [C.POINTER(MsdTileConsensus), C.c_void_p]),
     "msd_add_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_add_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

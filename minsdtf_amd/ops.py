@@ -203,6 +203,21 @@ def latent_resample(*, x, out, wx, wy, batch, h_in, w_in, h_out, w_out, a=1.0, s
     return Call(lib.msd_latent_resample, (C.byref(r),), name, keep=r)
 
 
+def tile_consensus(*, tiles, canvas, wy, wx, ys, xs, th, tw, H, W, batch, mode=0, name="tile_consensus") -> Call:
+    """msd_tile_consensus: mode 0 - every canvas pixel and every view's entry for it become the weighted mean of the views that
+    cover it; mode 1 (gather) - the canvas is copied into the views.  tiles fp32 [batch * len(ys) * len(xs)][th][tw][4] (in
+    place), canvas fp32 [batch][H][W][4], wy / wx: device fp32 weight rows [th] / [tw], ys / xs: the view offsets per axis."""
+    lib = _lib.load()
+    ys, xs = [int(v) for v in ys], [int(v) for v in xs]
+    if not 1 <= len(ys) <= _lib.TILE_MAX_VIEWS or not 1 <= len(xs) <= _lib.TILE_MAX_VIEWS:
+        raise ValueError(f"tile_consensus: {len(ys)} x {len(xs)} views (1 .. {_lib.TILE_MAX_VIEWS} per axis)")
+    t = _lib.MsdTileConsensus()
+    t.tiles, t.canvas, t.wy, t.wx = _p(tiles), _p(canvas), _p(wy), _p(wx)
+    t.ys[:len(ys)], t.xs[:len(xs)] = ys, xs
+    t.rows, t.cols, t.th, t.tw, t.H, t.W, t.batch, t.mode = len(ys), len(xs), int(th), int(tw), int(H), int(W), int(batch), int(mode)
+    return Call(lib.msd_tile_consensus, (C.byref(t),), name, keep=t)
+
+
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:
     lib = _lib.load()
     return Call(lib.msd_add_bf16, (_p(a), _p(b), _p(out), n), name)

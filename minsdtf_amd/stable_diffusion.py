@@ -35,6 +35,7 @@ import torch
 from . import _lib, engine, ops
 from . import hires as hires_mod
 from . import samplers as smp
+from . import tiled as tiled_mod
 from . import weights as wtab
 from .models import (ControlNet, DiffusionModel, HintNet, ImageDecoder, ImageEncoder, TextClipEmbedding, TextEncoder, _BoundPlan,
                      _skip_hw, default_device)
@@ -70,7 +71,7 @@ class DenoiseEngine:
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
-                 sampler=None):
+                 sampler=None, tiled=None):
         unet._require_weights()
         # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
         # the 8-wide coefficient rows, the previous denoised estimate and (stochastic samplers) per-step draws on the device
@@ -79,6 +80,14 @@ class DenoiseEngine:
             raise ValueError("a sampler cannot be combined with the TCD sampler")
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
+        # tiled (a tiled.Geometry, or None): the B rows are the views of B / V canvases, sample-major (row b * V + v); the step
+        # plan ends with one msd_tile_consensus launch that averages the stepped views into `canvas` and back into `latent`
+        self.tiled = tiled
+        if tiled is not None:
+            if (tiled.th, tiled.tw) != (self.h, self.w) or B % tiled.views:
+                raise ValueError(f"tiled: {tiled.views} views of {tiled.th} x {tiled.tw} on an engine of batch {B} at {self.h} x {self.w}")
+            if control_net is not None or inpaint or tcd:
+                raise ValueError("tiled: text-to-image only (no ControlNet, inpainting or TCD)")
         self.use_graph = use_graph
         dev = unet.device
         cfg = guidance > 0.0
@@ -211,6 +220,15 @@ class DenoiseEngine:
                      denoised_prev=self.denoised_prev, batch=B, n=n, num_steps=num_steps, guidance=guidance,
                      guidance_rescale=guidance_rescale, advance=2, inpaint_init=ip.get("init"), inpaint_noise=ip.get("noise"),
                      inpaint_mask=ip.get("mask"), step_noise=self.step_noise)
+        self.canvas = self._tile_args = None
+        if tiled is not None:
+            images = B // tiled.views
+            self.canvas = torch.zeros(images, tiled.H, tiled.W, 4, dtype=torch.float32, device=dev)
+            self._tile_w = (torch.from_numpy(tiled.wy).to(dev), torch.from_numpy(tiled.wx).to(dev))
+            self._tile_args = dict(tiles=self.latent, canvas=self.canvas, wy=self._tile_w[0], wx=self._tile_w[1], ys=tiled.ys, xs=tiled.xs,
+                                   th=tiled.th, tw=tiled.tw, H=tiled.H, W=tiled.W, batch=images)
+            # after the sampler step, so inside the per-step graph and the whole-loop graph
+            tail.rec(ops.tile_consensus, mode=tiled_mod.MODE_CONSENSUS, **self._tile_args)
         if self.cn_plan is not None:
             self.cn_plan.finalize()   # (first: the main plan's zero convs record addresses of its feature maps)
             self._join = step.marks["controls"]
@@ -231,6 +249,14 @@ class DenoiseEngine:
         """Destroy the captured step / loop graphs (re-captured on the next run_steps)."""
         self._step_graph = self._loop_graph = None
         self._loop_graph_steps = 0
+
+    def load_canvas(self, canvas_noise) -> None:
+        """Tiled engines: upload the canvas-shaped start latent and cut it into the views with ONE gather launch
+        (msd_tile_consensus, mode 1), stream-ordered in front of prepare(noise=None, ...)."""
+        if self.tiled is None:
+            raise ValueError("load_canvas: not a tiled engine")
+        self.canvas.copy_(_f32_tensor(canvas_noise))
+        ops.tile_consensus(mode=tiled_mod.MODE_GATHER, **self._tile_args)(torch.cuda.current_stream().cuda_stream)
 
     @property
     def calls(self):
@@ -446,13 +472,14 @@ class StableDiffusionBase:
     # ---- public entry points (reference :84-139)
     def text_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                       embedding=None, negative_embedding=None, seed=None, control_net_image=None, guidance_rescale=0.7,
-                      callback=None, hires=None, **kw):
-        """``hires``: None, or a hires.HiresSpec / dict for the two-pass hires fix (see generate_image)."""
+                      callback=None, hires=None, tiled=None, **kw):
+        """``hires``: None, or a hires.HiresSpec / dict for the two-pass hires fix; ``tiled``: None, or a tiled.TiledSpec / dict
+        for tiled diffusion on a canvas larger than the pipeline's size (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
                                    negative_embedding=negative_embedding, control_net_image=control_net_image,
-                                   guidance_rescale=guidance_rescale, callback=callback, hires=hires, **kw)
+                                   guidance_rescale=guidance_rescale, callback=callback, hires=hires, tiled=tiled, **kw)
 
     def image_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
@@ -579,11 +606,13 @@ class StableDiffusionBase:
                                            get_timestep_embedding(timestep, batch_size, dim, max_period))
     rescale_noise_cfg = staticmethod(rescale_noise_cfg)
 
-    def _get_initial_diffusion_noise(self, batch_size, seed):
+    def _get_initial_diffusion_noise(self, batch_size, seed, height=None, width=None):
         """The reference draws keras.random.normal(seed) (backend RNG, :555-557); here the noise is
-        numpy's PCG64 standard normal for the GLOBAL batch, so a sharded run slices the same draw."""
+        numpy's PCG64 standard normal for the GLOBAL batch, so a sharded run slices the same draw.
+        height / width: another image size than the pipeline's own (a tiled job's canvas)."""
         rng = np.random.default_rng(seed)
-        return rng.standard_normal((batch_size, self.img_height // 8, self.img_width // 8, 4)).astype(np.float32)
+        height, width = self.img_height if height is None else height, self.img_width if width is None else width
+        return rng.standard_normal((batch_size, height // 8, width // 8, 4)).astype(np.float32)
 
     @staticmethod
     def resize(image_array, new_h=None, new_w=None):
@@ -682,7 +711,8 @@ class StableDiffusionBase:
     def generate_image(self, encoded_text, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        diffusion_noise=None, seed=None, negative_embedding=None, control_net_image=None, inpaint_mask=None,
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
-                       callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None):
+                       callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None,
+                       tiled=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
@@ -692,7 +722,26 @@ class StableDiffusionBase:
         pipeline's own size, then the latent is resampled to the target size and re-noised on the device (msd_latent_resample)
         and the last int(steps * strength + 0.5) steps of a `steps`-step schedule run at the target size; the result has the
         target size.  ``hires_noise``: the re-noise draw (B, H2/8, W2/8, 4) (default: default_rng([seed, 2]), or numpy's global
-        stream without a seed).  `callback` counts through both passes."""
+        stream without a seed).  `callback` counts through both passes.
+        ``tiled`` (a tiled.TiledSpec or a dict of its fields: size = (height, width) of the canvas, stride, blend; txt2img only):
+        tiled diffusion (MultiDiffusion) - every step the UNet runs at the pipeline's own size on overlapping views of one canvas
+        latent, the views being batch rows of the one engine, and one msd_tile_consensus launch averages the stepped views where
+        they overlap.  The result has the canvas size; `seed` draws the start noise - and a stochastic sampler's per-step draws -
+        at canvas shape, `diffusion_noise` is taken at canvas shape.  At most tiled.MAX_VIEW_BATCH views (batch_size * views)."""
+        geo = tiled_mod.parse(tiled, self.img_height, self.img_width)   # (ValueError for a bad description)
+        if geo is not None:
+            refused = [n for n, v in (("reference_image", reference_image), ("inpaint_mask", inpaint_mask),
+                                      ("control_net_image", control_net_image), ("hires", hires)) if v is not None]
+            if host_loop:
+                refused.append("host_loop=True")
+            if self.active_tcd:
+                refused.append("a TCD pipeline (active_tcd=True)")
+            if refused:
+                raise ValueError(f"tiled is text-to-image on the device loop only: it cannot be combined with {', '.join(refused)}")
+            if int(batch_size) * geo.views > tiled_mod.MAX_VIEW_BATCH:
+                raise ValueError(f"tiled: {batch_size} image(s) of {geo.rows} x {geo.cols} views are {int(batch_size) * geo.views} UNet rows "
+                                 f"per step, more than tiled.MAX_VIEW_BATCH = {tiled_mod.MAX_VIEW_BATCH}: use a larger stride, a smaller "
+                                 "canvas or a smaller batch")
         job = hires_mod.parse(hires, self.img_height, self.img_width, num_steps)   # (ValueError for a bad description)
         if job is None and hires_noise is not None:
             raise ValueError("`hires_noise` without `hires`")
@@ -714,6 +763,14 @@ class StableDiffusionBase:
         B = batch_size
         context = self._batch_of(encoded_text, B, 2)
         unconditional_context = self._negative_context(negative_prompt, negative_embedding, B)
+        if geo is not None:
+            noise = (self._get_initial_diffusion_noise(B, seed, geo.height, geo.width) if diffusion_noise is None
+                     else self._batch_of(diffusion_noise, B, 3))
+            if tuple(noise.shape) != (B, geo.H, geo.W, 4):
+                raise ValueError(f"tiled: diffusion_noise has shape {tuple(noise.shape)}, the {geo.height}x{geo.width} canvas latent of "
+                                 f"batch {B} is {(B, geo.H, geo.W, 4)}")
+            return self._generate_tiled(geo, spec, context, unconditional_context, noise, num_steps, float(unconditional_guidance_scale),
+                                        float(guidance_rescale), seed, callback, return_latent)
         noise = self._get_initial_diffusion_noise(B, seed) if diffusion_noise is None else self._batch_of(diffusion_noise, B, 3)
         if job is not None:
             return self._generate_hires(job, spec, context, unconditional_context, noise, hires_noise, num_steps,
@@ -918,22 +975,70 @@ class StableDiffusionBase:
                                      shard=sharded)
         return self._to_host(out, dev, sharded)
 
-    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None) -> tuple:
+    # ---- tiled diffusion: the views of a canvas as batch rows of one engine (minsdtf_amd/tiled.py)
+    def _generate_tiled(self, geo, spec, context, unconditional_context, noise, num_steps, g, phi, seed, callback, return_latent):
+        """One engine of batch images * V keyed by the geometry: the canvas noise is uploaded and gathered into the views by one
+        launch, the loop (UNet on every view, sampler step per view, consensus) is the engine's replayed graph, the canvas latent
+        is decoded.  The engine stays resident, so a repeated job constructs nothing and captures nothing."""
+        from . import dist as mdist
+
+        B, V = noise.shape[0], geo.views
+        self.scheduler.set_timesteps(num_steps)
+        sched = None
+        per_sample = {}   # name -> array of the GLOBAL batch; insertion order = argument order of `local`
+        if spec is not None:
+            sched = smp.schedule(spec, self.scheduler, num_steps)
+            if spec.stochastic:   # drawn at CANVAS shape and cut per view (tiled.slice_views): overlapping pixels share a draw
+                per_sample["sampler_z"] = smp.draw_step_noise(B, num_steps, geo.H, geo.W, seed).reshape(B, num_steps, -1)
+        sname = None if spec is None else spec.name
+        dev = getattr(self, "device", None) or self.diffusion_model.device
+        names = list(per_sample)
+
+        def per_view(x):
+            """(b, ...) -> (b * V, ...): a sample's rows repeated for its V views (sample-major)."""
+            return x.repeat_interleave(V, dim=0) if isinstance(x, torch.Tensor) else np.repeat(x, V, axis=0)
+
+        def local(c, u, z, *rest):
+            """This rank's slice of the images: engine for b * V views -> gather -> prepare -> loop -> decode the canvas."""
+            a = dict(zip(names, rest))
+            b = int(z.shape[0])
+            eng = self._engine(b * V, c.shape[1], u.shape[1], num_steps, g, phi, False, sampler=sname, tiled=geo)
+            zs = a.get("sampler_z")
+            if zs is not None:
+                zs = tiled_mod.slice_views(zs.reshape(b, num_steps, geo.H, geo.W, 4), geo)
+            eng.load_canvas(z)
+            eng.prepare(eng.contexts(per_view(u), per_view(c)), None, self.scheduler, self.scheduler.timesteps, 0, step_noise=zs,
+                        sampler=sched)
+            eng.run_steps(num_steps, callback)
+            if return_latent:
+                return eng.canvas
+            return self.image_decoder.decode_to_uint8(eng.canvas)
+
+        sharded = (mdist.world_size() if getattr(self, "shard_batch", False) else 1) > 1 or \
+            (getattr(self, "shard_batch", False) and mdist.collectives_on())
+        out = mdist.generate_sharded(local, context, unconditional_context, noise, dev, per_sample=list(per_sample.values()),
+                                     shard=sharded)
+        return self._to_host(out, dev, sharded)
+
+    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None, tiled=None) -> tuple:
         # the engine's plans (and captured hipGraphs) hold raw addresses of the packed weights: a set_weights() /
         # load_synthetic() / LoRA reload on any of the models it was built from must retire it
         base = self.diffusion_model
         unet = base if unet is None else unet
         wver = (unet.weights_version,) + ((self.control_net.weights_version, self.hint_net.weights_version) if control else ())
         key = (B, tc, tu, steps, g, phi, control, self.denoise_streams, inpaint, self.active_tcd, wver, engine.GN_EPOCH, sampler)
-        return key if unet is base else key + ((unet.h, unet.w),)   # (a hires job's second size: a view of the same weights)
+        key = key if unet is base else key + ((unet.h, unet.w),)   # (a hires job's second size: a view of the same weights)
+        return key if tiled is None else key + (tiled.key,)        # (a tiled job: B counts views)
 
-    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None, job_keys=None) -> DenoiseEngine:
+    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None, job_keys=None,
+                tiled=None) -> DenoiseEngine:
         """The resident engine of this shape, built if need be.  `unet`: the UNet of another size (a hires job's second pass);
-        `job_keys`: the keys of every engine the current job uses (default: this one alone).  The engines' arenas are the big
+        `job_keys`: the keys of every engine the current job uses (default: this one alone); `tiled`: the geometry of a tiled job
+        (B counts its views).  The engines' arenas are the big
         allocations, so whatever the current job does not need goes BEFORE anything is built: a re-recording (another shape,
         new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than the job's own engines - one for a
         plain job, two for a hires job."""
-        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, sampler, unet)
+        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, sampler, unet, tiled)
         keep = {key} | set(job_keys or ())
         if any(k not in keep for k in self._engines):
             import gc
@@ -949,7 +1054,7 @@ class StableDiffusionBase:
             eng = DenoiseEngine(self.diffusion_model if unet is None else unet, B, tc, tu, steps, g, phi,
                                 control_net=self.control_net if control else None,
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
-                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=sampler)
+                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=sampler, tiled=tiled)
             self._engines[key] = eng
         return eng
 
