@@ -545,6 +545,41 @@ typedef struct MsdTileConsensus {
 
 MSD_API int msd_tile_consensus(const MsdTileConsensus* p, msd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * msd_region_combine — the per-step combine of a regional-prompting job (Latent Couple / MultiDiffusion region control;
+ * minsdtf_amd/regions.py): the UNet's conditional rows are evaluated once per region prompt, and in front of the
+ * guidance / sampler step every latent pixel's conditional eps becomes the weighted sum of the regions' predictions for it.
+ * An addition to ABI 12: nothing else changed.
+ *
+ *   eps: fp32 [regions * batch][n], row r * batch + b (region-major, like the pass's context rows); n = h * w * 4 (NHWC, C = 4)
+ *   w:   fp32 [regions][n / 4] - the weight of region r at each pixel, shared by the batch and by the 4 channels; >= 0 and
+ *        normalised by the host (regions.weights: weight_r * mask_r / sum in float64, rounded once) - the kernel does not divide
+ *   out: fp32 [batch][n]; may be eps itself (region 0's rows are then rewritten in place)
+ *
+ * Per sample b, pixel p and channel c, over r = 0 .. regions - 1 in this order (pinned; all fp32, the FMA single-rounded):
+ *   v = w[0][p] * eps[0 * batch + b][p, c]
+ *   v = fma(w[r][p], eps[r * batch + b][p, c], v)        r = 1 .. regions - 1
+ *   out[b][p, c] = v
+ * Where one region's weight is exactly 1.0 and every other one exactly 0.0, a finite non-zero value of that region is copied
+ * bit for bit (a zero may change sign).  A region of weight 0 still takes part in the sum: its NaN / Inf reach the output.
+ *
+ * One pixel of one sample is one lane's float4, one grid row per sample.  An output element reads only its own position of each
+ * region's row, so the in-place form is free of races and needs no atomics; nothing couples two pixels or two samples, so a
+ * sample's bits do not depend on its batch.  Checked on the host, without a device: eps / w / out non-NULL and 16-byte aligned;
+ * n a positive multiple of 4; regions in 1 .. MSD_REGION_MAX; batch in 1 .. 65535 (one grid row per sample); fewer than 2^31
+ * elements in eps; out == eps or out apart from all of eps; w apart from both.  Argument errors return MSD_E_ARG without
+ * launching.  Nothing is allocated; the launch is stream-ordered and capturable. */
+#define MSD_REGION_MAX 16
+
+typedef struct MsdRegionCombine {
+    const float* eps;
+    const float* w;
+    float* out;
+    int32_t regions, batch, n;
+} MsdRegionCombine;
+
+MSD_API int msd_region_combine(const MsdRegionCombine* p, msd_stream_t stream);
+
 /* msd_add_bf16 — out = a + b elementwise on bf16. n % 8 == 0. */
 MSD_API int msd_add_bf16(const void* a, const void* b, void* out, int64_t n, msd_stream_t stream);
 /* msd_add_f32_bf16 — out = bf16(a + b), a / out bf16, b fp32, summed in fp32 (may run in place, out == a).  The ControlNet

@@ -139,6 +139,16 @@ class MsdTileConsensus(C.Structure):
     ]
 
 
+REGION_MAX = 16   # MSD_REGION_MAX
+
+
+class MsdRegionCombine(C.Structure):
+    _fields_ = [
+        ("eps", C.c_void_p), ("w", C.c_void_p), ("out", C.c_void_p),
+        ("regions", C.c_int32), ("batch", C.c_int32), ("n", C.c_int32),   # regional prompting (an addition to ABI 12)
+    ]
+
+
 LORA_ROWS_PER_BLOCK = 8   # csrc/lora.hip LR_ROWS: MsdLoraJob.first_block counts workgroups of this many rows
 
 # every symbol include/minsdtf_hip.h declares: name -> (restype, argtypes)
@@ -166,6 +176,7 @@ SYMBOLS = {
     "msd_lora_merge": (C.c_int, [C.POINTER(MsdLoraMerge), C.c_void_p]),
     "msd_latent_resample": (C.c_int, [C.POINTER(MsdLatentResample), C.c_void_p]),
     "msd_tile_consensus": (C.c_int, [C.POINTER(MsdTileConsensus), C.c_void_p]),
+    "msd_region_combine": (C.c_int, [C.POINTER(MsdRegionCombine), C.c_void_p]),
     "msd_add_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_add_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -218,6 +218,16 @@ def tile_consensus(*, tiles, canvas, wy, wx, ys, xs, th, tw, H, W, batch, mode=0
     return Call(lib.msd_tile_consensus, (C.byref(t),), name, keep=t)
 
 
+def region_combine(*, eps, w, out, regions, batch, n, name="region_combine") -> Call:
+    """msd_region_combine: out[b] = sum_r w[r] * eps[r * batch + b] per pixel, r ascending, fp32 FMAs.  eps fp32 [regions * batch][n]
+    (region-major), w fp32 [regions][n / 4] (normalised on the host: regions.weights), out fp32 [batch][n] (may be eps: in place)."""
+    lib = _lib.load()
+    s = _lib.MsdRegionCombine()
+    s.eps, s.w, s.out = _p(eps), _p(w), _p(out)
+    s.regions, s.batch, s.n = int(regions), int(batch), int(n)
+    return Call(lib.msd_region_combine, (C.byref(s),), name, keep=s)
+
+
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:
     lib = _lib.load()
     return Call(lib.msd_add_bf16, (_p(a), _p(b), _p(out), n), name)

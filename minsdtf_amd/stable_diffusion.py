@@ -34,6 +34,7 @@ import torch
 
 from . import _lib, engine, ops
 from . import hires as hires_mod
+from . import regions as regions_mod
 from . import samplers as smp
 from . import tiled as tiled_mod
 from . import weights as wtab
@@ -71,7 +72,7 @@ class DenoiseEngine:
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
-                 sampler=None, tiled=None):
+                 sampler=None, tiled=None, regions: int = 0):
         unet._require_weights()
         # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
         # the 8-wide coefficient rows, the previous denoised estimate and (stochastic samplers) per-step draws on the device
@@ -88,6 +89,15 @@ class DenoiseEngine:
                 raise ValueError(f"tiled: {tiled.views} views of {tiled.th} x {tiled.tw} on an engine of batch {B} at {self.h} x {self.w}")
             if control_net is not None or inpaint or tcd:
                 raise ValueError("tiled: text-to-image only (no ControlNet, inpainting or TCD)")
+        # regions (R, the number of evaluated region prompts, or 0): the conditional half is R * B rows, region-major (row
+        # r * B + b) behind the unconditional rows; one msd_region_combine launch in front of the guidance / sampler step sums them
+        # per pixel with the weights of `region_w` into the first B of those rows, in place (minsdtf_amd/regions.py)
+        self.regions = R = int(regions or 0)
+        if R:
+            if not 1 <= R <= regions_mod.MAX_REGIONS:
+                raise ValueError(f"regions: {R} region prompts (1 .. {regions_mod.MAX_REGIONS})")
+            if control_net is not None or inpaint or tcd or tiled is not None or streams == 2:
+                raise ValueError("regions: text-to-image on one stream only (no ControlNet, inpainting, TCD, tiled, denoise_streams = 2)")
         self.use_graph = use_graph
         dev = unet.device
         cfg = guidance > 0.0
@@ -106,12 +116,13 @@ class DenoiseEngine:
         self.dual = bool(cfg and streams == 2)
         fuse = cfg and (t_cond == t_uncond) and not self.dual
         # passes: list of (rows in eps, NB, context length); fused = uncond rows then cond rows
+        RC = R or 1   # conditional copies of the batch
         if not cfg:
-            passes = [(0, B, t_cond, "cond")]
+            passes = [(0, RC * B, t_cond, "cond")]
         elif fuse:
-            passes = [(0, 2 * B, t_cond, "both")]
+            passes = [(0, (1 + RC) * B, t_cond, "both")]
         else:
-            passes = [(0, B, t_uncond, "uncond"), (B, B, t_cond, "cond")]
+            passes = [(0, B, t_uncond, "uncond"), (B, RC * B, t_cond, "cond")]
         self.passes = passes
         self.has_control = control_net is not None
 
@@ -164,7 +175,8 @@ class DenoiseEngine:
 
         # ---- per-step plans: one per stream (`branches`) + the sampler step (`tail`) ------------
         n = h * w * 4
-        self.eps = torch.zeros((2 * B if cfg else B), n, dtype=torch.float32, device=dev)
+        self.eps = torch.zeros(((1 + RC) * B if cfg else RC * B), n, dtype=torch.float32, device=dev)
+        self.region_w = torch.zeros(R, h, w, dtype=torch.float32, device=dev) if R else None
         cols_u = engine.temb_columns(False)
         cols_c = engine.temb_columns(True)
         self.branches = []
@@ -208,6 +220,10 @@ class DenoiseEngine:
         self.step_noise = torch.zeros(num_steps, B, n, dtype=torch.float32, device=dev) if stochastic else None
         self.noise_coef = torch.zeros(num_steps, dtype=torch.float32, device=dev) if tcd else None
         self.denoised_prev = None
+        if R:
+            # (R == 1 too: a weight of all ones copies the row bit for bit)  Behind it the step kernels read [2B][n] (or [B][n])
+            cond = _Ptr(self.eps.data_ptr() + (B if cfg else 0) * n * 4)
+            tail.rec(ops.region_combine, eps=cond, w=self.region_w, out=cond, regions=R, batch=B, n=n)
         if self.sampler is None:
             tail.rec(ops.cfg_step, eps=self.eps, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr, batch=B, n=n,
                      num_steps=num_steps, guidance=guidance, guidance_rescale=guidance_rescale, advance=2,
@@ -267,7 +283,16 @@ class DenoiseEngine:
         return out + (self.tail.calls if self.tail is not None else [])
 
     def contexts(self, unconditional_context, context) -> dict:
-        """The `prepare` input for this engine's pass layout (host arrays or device tensors)."""
+        """The `prepare` input for this engine's pass layout (host arrays or device tensors).  A regional engine takes `context`
+        as the list of its R region contexts, each (B, T, 768): laid out uncond, region 0, region 1, ..., each B rows."""
+        if isinstance(context, (list, tuple)):
+            if len(context) != self.regions:
+                raise ValueError(f"this engine evaluates {self.regions} region prompt(s): pass that many contexts as a list")
+            if any(isinstance(c, torch.Tensor) for c in context):
+                dev = next(c.device for c in context if isinstance(c, torch.Tensor))
+                context = torch.cat([_f32_tensor(c).to(dev) for c in context], dim=0)
+            else:
+                context = np.concatenate([np.asarray(c, dtype=np.float32) for c in context], axis=0)
         if not self.cfg:
             return {"cond": context}
         if len(self.passes) == 1:
@@ -355,7 +380,8 @@ class DenoiseEngine:
             callback(i + 1)
 
     def prepare(self, contexts: Dict[str, np.ndarray], noise: np.ndarray, scheduler: Scheduler, timesteps,
-                start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None) -> None:
+                start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None,
+                regions=None) -> None:
         """Upload the per-call inputs and run the preparation plan.  Every array may be a host array or a (device) tensor.
         noise = None: the start latent is already in `self.latent` (written there by stream-ordered device work queued before
         this call: the hand-off of a hires job), nothing is uploaded for it.
@@ -363,7 +389,15 @@ class DenoiseEngine:
         inpaint=True; step_noise = (B, num_steps, h*w*4) TCD draws made by the caller (sharded runs: the slice of the
         draws for the global batch) instead of the draws made here.  An engine built with a sampler takes its
         samplers.Schedule as `sampler` (the coefficient rows are built here for `start_index`) and, for the stochastic samplers,
-        its draws as `step_noise` (B, num_steps, ...) (drawn here from numpy's global stream when None)."""
+        its draws as `step_noise` (B, num_steps, ...) (drawn here from numpy's global stream when None).
+        regions = the normalised weights (R, h, w) of a regional engine (regions.weights): a per-call upload, like the inpaint mask."""
+        if (regions is None) != (self.region_w is None):
+            raise ValueError("prepare: `regions` (the weights) goes with an engine built with regions=R, and only with one")
+        if self.region_w is not None:
+            rw = _f32_tensor(regions)
+            if tuple(rw.shape) != tuple(self.region_w.shape):
+                raise ValueError(f"prepare: region weights of shape {tuple(rw.shape)}, this engine's are {tuple(self.region_w.shape)}")
+            self.region_w.copy_(rw)
         if self.inpaint is not None:
             init, ip_noise, mask = inpaint
             self.inpaint["init"].copy_(_f32_tensor(init).reshape(-1))
@@ -472,14 +506,16 @@ class StableDiffusionBase:
     # ---- public entry points (reference :84-139)
     def text_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                       embedding=None, negative_embedding=None, seed=None, control_net_image=None, guidance_rescale=0.7,
-                      callback=None, hires=None, tiled=None, **kw):
+                      callback=None, hires=None, tiled=None, regions=None, **kw):
         """``hires``: None, or a hires.HiresSpec / dict for the two-pass hires fix; ``tiled``: None, or a tiled.TiledSpec / dict
-        for tiled diffusion on a canvas larger than the pipeline's size (see generate_image)."""
+        for tiled diffusion on a canvas larger than the pipeline's size; ``regions``: None, or a regions.Regions / dict for
+        regional prompting, `prompt` being the base prompt (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
                                    negative_embedding=negative_embedding, control_net_image=control_net_image,
-                                   guidance_rescale=guidance_rescale, callback=callback, hires=hires, tiled=tiled, **kw)
+                                   guidance_rescale=guidance_rescale, callback=callback, hires=hires, tiled=tiled, regions=regions,
+                                   **kw)
 
     def image_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
@@ -712,7 +748,7 @@ class StableDiffusionBase:
                        diffusion_noise=None, seed=None, negative_embedding=None, control_net_image=None, inpaint_mask=None,
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
                        callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None,
-                       tiled=None):
+                       tiled=None, regions=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
@@ -727,7 +763,27 @@ class StableDiffusionBase:
         tiled diffusion (MultiDiffusion) - every step the UNet runs at the pipeline's own size on overlapping views of one canvas
         latent, the views being batch rows of the one engine, and one msd_tile_consensus launch averages the stepped views where
         they overlap.  The result has the canvas size; `seed` draws the start noise - and a stochastic sampler's per-step draws -
-        at canvas shape, `diffusion_noise` is taken at canvas shape.  At most tiled.MAX_VIEW_BATCH views (batch_size * views)."""
+        at canvas shape, `diffusion_noise` is taken at canvas shape.  At most tiled.MAX_VIEW_BATCH views (batch_size * views).
+        ``regions`` (a regions.Regions or a dict {"regions": [{"prompt", "mask", "weight"}, ...], "base_weight": 0.0}; txt2img only):
+        regional prompting - every step the UNet's conditional half runs once per region prompt (further batch rows of the one
+        engine) and one msd_region_combine launch sums the predictions per latent pixel with the normalised mask weights in front
+        of the guidance / sampler step.  With base_weight > 0 `encoded_text` joins as region 0 with that constant mask; with 0 it is
+        not evaluated.  The region contexts share one token length.  At most 2 * tiled.MAX_VIEW_BATCH UNet rows
+        ((1 + R) * batch_size).  Works with host_loop=True too."""
+        reg = regions_mod.parse(regions, self.img_height, self.img_width)   # (ValueError for a bad description)
+        if reg is not None:
+            refused = [n for n, v in (("tiled", tiled), ("hires", hires), ("control_net_image", control_net_image),
+                                      ("reference_image", reference_image), ("inpaint_mask", inpaint_mask)) if v is not None]
+            if self.active_tcd:
+                refused.append("a TCD pipeline (active_tcd=True)")
+            if self.denoise_streams == 2:
+                refused.append("denoise_streams = 2")
+            if refused:
+                raise ValueError(f"regions is text-to-image on one stream only: it cannot be combined with {', '.join(refused)}")
+            if (1 + reg.count) * int(batch_size) > 2 * tiled_mod.MAX_VIEW_BATCH:
+                raise ValueError(f"regions: {batch_size} image(s) of 1 + {reg.count} prompts are {(1 + reg.count) * int(batch_size)} UNet "
+                                 f"rows per step, more than 2 * tiled.MAX_VIEW_BATCH = {2 * tiled_mod.MAX_VIEW_BATCH}: use fewer regions "
+                                 "or a smaller batch")
         geo = tiled_mod.parse(tiled, self.img_height, self.img_width)   # (ValueError for a bad description)
         if geo is not None:
             refused = [n for n, v in (("reference_image", reference_image), ("inpaint_mask", inpaint_mask),
@@ -807,6 +863,11 @@ class StableDiffusionBase:
                 sampler_z = smp.draw_step_noise(B, num_steps, noise.shape[1], noise.shape[2], seed)
         hint = self._hint_batch(control_net_image, B)
         g, phi = float(unconditional_guidance_scale), float(guidance_rescale)
+        region_ctx = region_w = None
+        if reg is not None:
+            region_ctx, region_w = self._region_inputs(reg, context)   # (R', T, 768) without the base prompt, (R, h, w)
+            if host_loop:   # the conditional context becomes the list of region contexts, each (B, T, 768)
+                context = ([context] if reg.base_weight > 0.0 else []) + [np.repeat(rc[None], B, axis=0) for rc in region_ctx]
 
         def finish(decoded, picture=picture01, mask=pixel_mask):
             """Decoder output in [-1,1] -> uint8, truncating (reference :482-486), through the pixel-space inpaint blend."""
@@ -817,13 +878,13 @@ class StableDiffusionBase:
 
         if host_loop and spec is not None:
             latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
-                                             sampler_z, (encoded, noise, latent_mask[0]) if inpainting else None)
+                                             sampler_z, (encoded, noise, latent_mask[0]) if inpainting else None, region_w=region_w)
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
             return finish(self.image_decoder.predict_on_batch(latent))
         if host_loop:
             latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending,
-                                     (encoded, noise, latent_mask[0]) if inpainting else None)
+                                     (encoded, noise, latent_mask[0]) if inpainting else None, region_w=region_w)
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
             return finish(self.image_decoder.predict_on_batch(latent))
@@ -850,6 +911,8 @@ class StableDiffusionBase:
             per_sample["tcd"] = np.ascontiguousarray(zs.transpose(1, 0, 2))
         if sampler_z is not None:
             per_sample["sampler_z"] = sampler_z.reshape(B, num_steps, -1)
+        if reg is not None:   # one context per region and the weights: whole on every rank
+            shared["region_ctx"], shared["region_w"] = region_ctx, region_w
         dev = getattr(self, "device", None) or self.diffusion_model.device
         names = list(per_sample) + list(shared)
 
@@ -860,13 +923,22 @@ class StableDiffusionBase:
             hint_b = a.get("hint")
             ip = (a["encoded"], a["noise"], a["mask"]) if inpainting else None
             tcd_z = a.get("tcd")
+            R, rw = 0, a.get("region_w")
+            if reg is not None:   # the region contexts, each repeated over this rank's samples; the base prompt's rows first
+                rc = a["region_ctx"]
+                rep = (lambda x: x.unsqueeze(0).expand(b, -1, -1)) if isinstance(rc, torch.Tensor) else (lambda x: np.repeat(x[None], b, axis=0))
+                c = ([c] if reg.base_weight > 0.0 else []) + [rep(rc[i]) for i in range(rc.shape[0])]
+                R = len(c)
+            tc = c[0].shape[1] if R else c.shape[1]
+            ek, pk = (dict(regions=R), dict(regions=rw)) if R else ({}, {})   # (a plain job's calls are what they always were)
             if spec is None:
-                eng = self._engine(b, c.shape[1], u.shape[1], num_steps, g, phi, hint_b is not None, ip is not None)
-                eng.prepare(eng.contexts(u, c), z, self.scheduler, self.scheduler.timesteps, start_index, hint_b, ip, step_noise=tcd_z)
+                eng = self._engine(b, tc, u.shape[1], num_steps, g, phi, hint_b is not None, ip is not None, **ek)
+                eng.prepare(eng.contexts(u, c), z, self.scheduler, self.scheduler.timesteps, start_index, hint_b, ip, step_noise=tcd_z,
+                            **pk)
             else:
-                eng = self._engine(b, c.shape[1], u.shape[1], num_steps, g, phi, hint_b is not None, ip is not None, sampler=spec.name)
+                eng = self._engine(b, tc, u.shape[1], num_steps, g, phi, hint_b is not None, ip is not None, sampler=spec.name, **ek)
                 eng.prepare(eng.contexts(u, c), z, self.scheduler, self.scheduler.timesteps, start_index, hint_b, ip,
-                            step_noise=a.get("sampler_z"), sampler=sched)
+                            step_noise=a.get("sampler_z"), sampler=sched, **pk)
             eng.run_steps(run_steps, callback)
             if return_latent:
                 return eng.latent
@@ -1020,7 +1092,26 @@ class StableDiffusionBase:
                                      shard=sharded)
         return self._to_host(out, dev, sharded)
 
-    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None, tiled=None) -> tuple:
+    # ---- regional prompting: one prompt per masked region (minsdtf_amd/regions.py)
+    def _region_inputs(self, reg, context):
+        """The region prompts encoded -> (R', T, 768) fp32 (the base prompt, which `context` (B, T, 768) holds per sample, is not
+        among them), and the normalised weights (R, h, w) with the base prompt's first when it takes part.  ValueError when the
+        evaluated contexts do not share one token length."""
+        encoded = []
+        for i, prompt in enumerate(reg.prompts):
+            e = np.asarray(self.encode_text(prompt), dtype=np.float32)
+            e = e[0] if e.ndim == 3 and e.shape[0] == 1 else e
+            if e.ndim != 2 or e.shape[1] != 768:
+                raise ValueError(f"regions: the prompt of region {i} encodes to shape {tuple(e.shape)}, expected (T, 768)")
+            encoded.append(e)
+        lengths = ([("the base prompt", context.shape[1])] if reg.base_weight > 0.0 else []) + \
+            [(f"region {i}", e.shape[0]) for i, e in enumerate(encoded)]
+        if len({n for _w, n in lengths}) != 1:
+            raise ValueError("regions: the region contexts must share one token length, got "
+                             + ", ".join(f"{w}: {n}" for w, n in lengths))
+        return np.stack(encoded, axis=0), reg.weights()
+
+    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None, tiled=None, regions=0) -> tuple:
         # the engine's plans (and captured hipGraphs) hold raw addresses of the packed weights: a set_weights() /
         # load_synthetic() / LoRA reload on any of the models it was built from must retire it
         base = self.diffusion_model
@@ -1028,17 +1119,19 @@ class StableDiffusionBase:
         wver = (unet.weights_version,) + ((self.control_net.weights_version, self.hint_net.weights_version) if control else ())
         key = (B, tc, tu, steps, g, phi, control, self.denoise_streams, inpaint, self.active_tcd, wver, engine.GN_EPOCH, sampler)
         key = key if unet is base else key + ((unet.h, unet.w),)   # (a hires job's second size: a view of the same weights)
-        return key if tiled is None else key + (tiled.key,)        # (a tiled job: B counts views)
+        key = key if tiled is None else key + (tiled.key,)         # (a tiled job: B counts views)
+        # (a regional job: the NUMBER of evaluated region prompts only - masks, weights and prompts are per-call uploads)
+        return key if not regions else key + (("regions", int(regions)),)
 
     def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None, job_keys=None,
-                tiled=None) -> DenoiseEngine:
+                tiled=None, regions=0) -> DenoiseEngine:
         """The resident engine of this shape, built if need be.  `unet`: the UNet of another size (a hires job's second pass);
         `job_keys`: the keys of every engine the current job uses (default: this one alone); `tiled`: the geometry of a tiled job
-        (B counts its views).  The engines' arenas are the big
+        (B counts its views); `regions`: the number of evaluated region prompts of a regional job.  The engines' arenas are the big
         allocations, so whatever the current job does not need goes BEFORE anything is built: a re-recording (another shape,
         new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than the job's own engines - one for a
         plain job, two for a hires job."""
-        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, sampler, unet, tiled)
+        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, sampler, unet, tiled, regions)
         keep = {key} | set(job_keys or ())
         if any(k not in keep for k in self._engines):
             import gc
@@ -1054,11 +1147,13 @@ class StableDiffusionBase:
             eng = DenoiseEngine(self.diffusion_model if unet is None else unet, B, tc, tu, steps, g, phi,
                                 control_net=self.control_net if control else None,
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
-                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=sampler, tiled=tiled)
+                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=sampler, tiled=tiled,
+                                regions=regions)
             self._engines[key] = eng
         return eng
 
-    def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None):
+    def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None,
+                   region_w=None):
         """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479)."""
         if timesteps is None:
             timesteps = self.scheduler.timesteps[::-1]
@@ -1068,7 +1163,7 @@ class StableDiffusionBase:
         for _index, timestep in list(enumerate(timesteps))[::-1]:
             latent_prev = latent
             t_emb = get_timestep_embedding(timestep, batch_size)
-            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint)
+            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w)
             latent = self.scheduler.step(latent, timestep, latent_prev)
             if inpaint is not None:   # reference :469-475
                 init_latent, noise, latent_mask = inpaint
@@ -1080,8 +1175,17 @@ class StableDiffusionBase:
                 callback(iteration)
         return latent
 
-    def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint):
-        """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467)."""
+    def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None):
+        """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
+        A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
+        predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host)."""
+        if isinstance(context, (list, tuple)):
+            c = regions_mod.combine_host([self.diffusion_model.predict_on_batch([latent, t_emb, rc]) for rc in context], region_w)
+            if g <= 0.0:
+                return c
+            u = self.diffusion_model.predict_on_batch([latent, t_emb, unconditional_context])
+            e = u + g * (c - u)
+            return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
         if g > 0.0:
             if hint is not None:
                 uc = self.control_net.predict_on_batch([latent, t_emb, unconditional_context, hint])
@@ -1101,7 +1205,7 @@ class StableDiffusionBase:
         return self.diffusion_model.predict_on_batch([latent, t_emb, context])
 
     def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
-                           inpaint=None):
+                           inpaint=None, region_w=None):
         """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`."""
         batch_size = latent.shape[0]
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
@@ -1110,7 +1214,7 @@ class StableDiffusionBase:
         prev = None
         for iteration, i in enumerate(range(start, sched.num_steps), start=1):
             t_emb = get_timestep_embedding(float(sched.timesteps[i]), batch_size)
-            e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint)
+            e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint, region_w)
             z = step_noise[:, i] if step_noise is not None else None
             x, prev = smp.host_step(tab[i], x, e, prev, z)
             if inpaint is not None:   # the row's own alpha / sigma, as in the device kernel
