@@ -74,19 +74,64 @@ class DenoiseEngine:
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
                  sampler=None, tiled=None, regions: int = 0):
         unet._require_weights()
+        self.unet, self.B, self.num_steps = unet, B, num_steps
+        self.h, self.w = unet.h, unet.w
+        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions)
+        self.use_graph = use_graph
+        self.cfg = cfg = guidance > 0.0
+        # Two ways to run the cond and uncond halves of a step (no op couples samples, so both are the
+        # reference's two predict_on_batch calls, :442-460):
+        #  * fused: ONE batch-2B forward;
+        #  * dual (streams=2): two batch-B forwards on two HIP streams that fork after the previous
+        #    sampler step and join before the next one.
+        # The two forms measure the same within noise on MI355X at 512x512 (DESIGN.md §2) because the small-batch
+        # kernels are bounded by per-workgroup latency with idle CUs either way.  Fused is the default (one arena,
+        # one kernel chain); dual stays selectable.
+        self.dual = bool(cfg and streams == 2)
+        fuse = cfg and (t_cond == t_uncond) and not self.dual
+        # passes: list of (rows in eps, NB, context length); fused = uncond rows then cond rows
+        RC = self.regions or 1   # conditional copies of the batch
+        if not cfg:
+            passes = [(0, RC * B, t_cond, "cond")]
+        elif fuse:
+            passes = [(0, (1 + RC) * B, t_cond, "both")]
+        else:
+            passes = [(0, B, t_uncond, "uncond"), (B, RC * B, t_cond, "cond")]
+        self.passes = passes
+        self.has_control = control_net is not None
+        prep = self._build_prep(control_net, hint_net)
+        step = self._build_steps(control_net, prep)
+        tail = self._build_tail(step, guidance, guidance_rescale, inpaint, tcd)
+        if self.cn_plan is not None:
+            self.cn_plan.finalize()   # (first: the main plan's zero convs record addresses of its feature maps)
+            self._join = step.marks["controls"]
+        for pl in self.branches:
+            pl.finalize()
+        self.tail = tail if self.dual else None
+        if self.dual:
+            tail.finalize()
+        if self.dual or self.cn_plan is not None:
+            self._side = torch.cuda.Stream(device=unet.device)
+        self._step_graph: Optional[torch.cuda.CUDAGraph] = None
+        self._loop_graph: Optional[torch.cuda.CUDAGraph] = None
+        self._loop_graph_steps = 0
+        self._warmed = False
+        _lib.track_graph_owner(self)
+
+    def _check_options(self, control_net, streams, inpaint, tcd, sampler, tiled, regions) -> None:
+        """The option combinations an engine refuses (generate_image refuses them earlier, by argument name: _REFUSED; these guard
+        direct construction).  Sets `sampler`, `tiled` and `regions`."""
         # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
         # the 8-wide coefficient rows, the previous denoised estimate and (stochastic samplers) per-step draws on the device
         self.sampler = smp.parse(sampler)
         if self.sampler is not None and tcd:
             raise ValueError("a sampler cannot be combined with the TCD sampler")
-        self.unet, self.B, self.num_steps = unet, B, num_steps
-        self.h, self.w = unet.h, unet.w
         # tiled (a tiled.Geometry, or None): the B rows are the views of B / V canvases, sample-major (row b * V + v); the step
         # plan ends with one msd_tile_consensus launch that averages the stepped views into `canvas` and back into `latent`
         self.tiled = tiled
         if tiled is not None:
-            if (tiled.th, tiled.tw) != (self.h, self.w) or B % tiled.views:
-                raise ValueError(f"tiled: {tiled.views} views of {tiled.th} x {tiled.tw} on an engine of batch {B} at {self.h} x {self.w}")
+            if (tiled.th, tiled.tw) != (self.h, self.w) or self.B % tiled.views:
+                raise ValueError(f"tiled: {tiled.views} views of {tiled.th} x {tiled.tw} on an engine of batch {self.B} at {self.h} x {self.w}")
             if control_net is not None or inpaint or tcd:
                 raise ValueError("tiled: text-to-image only (no ControlNet, inpainting or TCD)")
         # regions (R, the number of evaluated region prompts, or 0): the conditional half is R * B rows, region-major (row
@@ -98,36 +143,13 @@ class DenoiseEngine:
                 raise ValueError(f"regions: {R} region prompts (1 .. {regions_mod.MAX_REGIONS})")
             if control_net is not None or inpaint or tcd or tiled is not None or streams == 2:
                 raise ValueError("regions: text-to-image on one stream only (no ControlNet, inpainting, TCD, tiled, denoise_streams = 2)")
-        self.use_graph = use_graph
-        dev = unet.device
-        cfg = guidance > 0.0
-        self.cfg = cfg
-        h, w = self.h, self.w
-        # Two ways to run the cond and uncond halves of a step (no op couples samples, so both are the
-        # reference's two predict_on_batch calls, :442-460):
-        #  * fused: ONE batch-2B forward;
-        #  * dual (streams=2): two batch-B forwards on two HIP streams that fork after the previous
-        #    sampler step and join before the next one.
-        # The two forms measure the same within noise on MI355X at 512x512 (DESIGN.md §2) because the small-batch
-        # kernels are bounded by per-workgroup latency with idle CUs either way.  Fused is the default (one arena,
-        # one kernel chain); dual stays selectable.
-        if streams is None:
-            streams = 1
-        self.dual = bool(cfg and streams == 2)
-        fuse = cfg and (t_cond == t_uncond) and not self.dual
-        # passes: list of (rows in eps, NB, context length); fused = uncond rows then cond rows
-        RC = R or 1   # conditional copies of the batch
-        if not cfg:
-            passes = [(0, RC * B, t_cond, "cond")]
-        elif fuse:
-            passes = [(0, (1 + RC) * B, t_cond, "both")]
-        else:
-            passes = [(0, B, t_uncond, "uncond"), (B, RC * B, t_cond, "cond")]
-        self.passes = passes
-        self.has_control = control_net is not None
 
-        # ---- preparation plans: per SCHEDULE the time-embedding tables (timestep -> MLP -> every ResBlock's projection: they do
-        #      not depend on the prompt, so they run when the schedule changes, not per call); per CALL contexts -> K/V^T, hint
+    def _build_prep(self, control_net, hint_net) -> dict:
+        """The preparation plans: per SCHEDULE the time-embedding tables (timestep -> MLP -> every ResBlock's projection: they do
+        not depend on the prompt, so they run when the schedule changes, not per call); per CALL contexts -> K/V^T, hint.
+        Returns what the step plans read of them: the tables, the K/V^T of every pass and the hint's activation."""
+        unet, B, num_steps, h, w, passes = self.unet, self.B, self.num_steps, self.h, self.w, self.passes
+        dev = unet.device
         prep_t = engine.Plan(dev)
         prep = engine.Plan(dev)
         e_t = engine.Emitter(prep_t, unet._W)
@@ -172,13 +194,17 @@ class DenoiseEngine:
         prep_t.finalize()
         prep.finalize()
         self.prep, self.prep_t = prep, prep_t
+        return dict(table_u=(table_u, total_u, 0, engine.temb_columns(False)), table_c=(table_c, total_c, 0, engine.temb_columns(True)),
+                    kv_u=ctx_kv_u, kv_c=ctx_kv_c, hint=hint_act)
 
-        # ---- per-step plans: one per stream (`branches`) + the sampler step (`tail`) ------------
+    def _build_steps(self, control_net, prep: dict) -> "engine.Plan":
+        """The per-step UNet plans, one per stream (`branches`; `cn_plan`: the ControlNet encoder beside the UNet's down path).
+        Returns the last of them, which takes the tail unless the engine is dual."""
+        unet, B, h, w, R, passes = self.unet, self.B, self.h, self.w, self.regions, self.passes
+        dev = unet.device
         n = h * w * 4
-        self.eps = torch.zeros(((1 + RC) * B if cfg else RC * B), n, dtype=torch.float32, device=dev)
+        self.eps = torch.zeros(((1 + (R or 1)) * B if self.cfg else (R or 1) * B), n, dtype=torch.float32, device=dev)
         self.region_w = torch.zeros(R, h, w, dtype=torch.float32, device=dev) if R else None
-        cols_u = engine.temb_columns(False)
-        cols_c = engine.temb_columns(True)
         self.branches = []
         step = None
         # ControlNet beside the UNet's down path: its encoder reads the same latent and is independent of the UNet until the
@@ -196,17 +222,23 @@ class DenoiseEngine:
             taps = None
             if self.has_control:
                 # ControlNet encoder first; its 13 zero convs run inside the UNet plan, fused with the residual adds
-                hint_nb = engine.Act(hint_act.buf, nb, h, w, 320)  # first nb rows of the tiled hint
+                hint_nb = engine.Act(prep["hint"].buf, nb, h, w, 320)  # first nb rows of the tiled hint
                 s_cf = s_c
                 if overlap:
                     self.cn_plan = engine.Plan(dev)
                     s_cf = engine.Emitter(self.cn_plan, control_net._W, step_ptr=self.step_ptr)
-                feats = engine.emit_controlnet_features(s_cf, self.latent, B, nb, h, w, (table_c, total_c, 0, cols_c), ctx_kv_c[tag], t,
-                                                        hint_nb)
+                feats = engine.emit_controlnet_features(s_cf, self.latent, B, nb, h, w, prep["table_c"], prep["kv_c"][tag], t, hint_nb)
                 taps = (s_c, feats)
             eps_view = _Ptr(self.eps.data_ptr() + row0 * n * 4)
-            engine.emit_unet(s_u, self.latent, B, nb, h, w, (table_u, total_u, 0, cols_u), ctx_kv_u[tag], t, eps_view,
-                             control_taps=taps)
+            engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps)
+        return step
+
+    def _build_tail(self, step, guidance, guidance_rescale, inpaint, tcd) -> "engine.Plan":
+        """What follows the UNet in a step: the region combine, the guidance / sampler step, the tile consensus - recorded behind
+        the UNet in `step`, or (dual) in a plan of their own, which is returned."""
+        B, num_steps, h, w, R, tiled = self.B, self.num_steps, self.h, self.w, self.regions, self.tiled
+        dev = self.unet.device
+        n = h * w * 4
         tail = engine.Plan(dev) if self.dual else step
         # inpainting (reference :469-475): the blend with the re-noised encoded image is part of the sampler kernel
         self.inpaint = None
@@ -222,7 +254,7 @@ class DenoiseEngine:
         self.denoised_prev = None
         if R:
             # (R == 1 too: a weight of all ones copies the row bit for bit)  Behind it the step kernels read [2B][n] (or [B][n])
-            cond = _Ptr(self.eps.data_ptr() + (B if cfg else 0) * n * 4)
+            cond = _Ptr(self.eps.data_ptr() + (B if self.cfg else 0) * n * 4)
             tail.rec(ops.region_combine, eps=cond, w=self.region_w, out=cond, regions=R, batch=B, n=n)
         if self.sampler is None:
             tail.rec(ops.cfg_step, eps=self.eps, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr, batch=B, n=n,
@@ -245,21 +277,7 @@ class DenoiseEngine:
                                    th=tiled.th, tw=tiled.tw, H=tiled.H, W=tiled.W, batch=images)
             # after the sampler step, so inside the per-step graph and the whole-loop graph
             tail.rec(ops.tile_consensus, mode=tiled_mod.MODE_CONSENSUS, **self._tile_args)
-        if self.cn_plan is not None:
-            self.cn_plan.finalize()   # (first: the main plan's zero convs record addresses of its feature maps)
-            self._join = step.marks["controls"]
-        for pl in self.branches:
-            pl.finalize()
-        self.tail = tail if self.dual else None
-        if self.dual:
-            tail.finalize()
-        if self.dual or self.cn_plan is not None:
-            self._side = torch.cuda.Stream(device=dev)
-        self._step_graph: Optional[torch.cuda.CUDAGraph] = None
-        self._loop_graph: Optional[torch.cuda.CUDAGraph] = None
-        self._loop_graph_steps = 0
-        self._warmed = False
-        _lib.track_graph_owner(self)
+        return tail
 
     def release_graphs(self) -> None:
         """Destroy the captured step / loop graphs (re-captured on the next run_steps)."""
@@ -441,26 +459,28 @@ class DenoiseEngine:
         if init is None:
             init = self._step_init[int(start_index)] = torch.tensor([int(start_index), 0], dtype=torch.int32, device=self.step_ptr.device)
         self.step_ptr.copy_(init)   # {first step, ticket 0}: device -> device
-        if self.step_noise is not None and self.sampler is not None:
+        if self.step_noise is not None:
+            if self.sampler is None:
+                self.noise_coef.copy_(torch.from_numpy(scheduler.noise_coefficients()))
             if step_noise is None:
-                step_noise = smp.draw_step_noise(self.B, self.num_steps, self.h, self.w)
+                step_noise = (tcd_step_noise(self.B, self.num_steps, self.h, self.w, start_index) if self.sampler is None
+                              else smp.draw_step_noise(self.B, self.num_steps, self.h, self.w))
             self.step_noise.copy_(_f32_tensor(step_noise).reshape(self.B, self.num_steps, -1).transpose(0, 1))
-        elif self.step_noise is not None:
-            # scheduler.py:301 draws np.random.randn(*latent.shape) once per executed step except the last
-            self.noise_coef.copy_(torch.from_numpy(scheduler.noise_coefficients()))
-            if step_noise is not None:
-                self.step_noise.copy_(_f32_tensor(step_noise).reshape(self.B, self.num_steps, -1).transpose(0, 1))
-            else:
-                z = np.zeros((self.num_steps, self.B, self.h * self.w * 4), dtype=np.float32)
-                for i in range(int(start_index), self.num_steps - 1):
-                    z[i] = np.random.randn(self.B, self.h, self.w, 4).astype(np.float32).reshape(self.B, -1)
-                self.step_noise.copy_(torch.from_numpy(z))
         if self.has_control:
             hi = _f32_tensor(hint_image)
             if hi.shape[0] != self.B:   # (one hint for the whole batch: the reference tiles it, :435)
                 hi = hi.repeat(self.B // hi.shape[0], 1, 1, 1)
             self.hint_img.copy_(hi)   # the cond / uncond replicas are made on the device (emit_hintnet)
         self.prep.run(torch.cuda.current_stream().cuda_stream)
+
+
+def tcd_step_noise(B, num_steps, h, w, start_index) -> np.ndarray:
+    """The TCD sampler's draws (B, num_steps, h*w*4), sample-major, from numpy's global stream in the reference's order:
+    scheduler.py:301 draws np.random.randn(*latent.shape) once per executed step except the last."""
+    z = np.zeros((B, num_steps, h * w * 4), dtype=np.float32)
+    for i in range(int(start_index), num_steps - 1):
+        z[:, i] = np.random.randn(B, h, w, 4).astype(np.float32).reshape(B, -1)
+    return z
 
 
 def _f32_tensor(x) -> torch.Tensor:
@@ -770,30 +790,18 @@ class StableDiffusionBase:
         of the guidance / sampler step.  With base_weight > 0 `encoded_text` joins as region 0 with that constant mask; with 0 it is
         not evaluated.  The region contexts share one token length.  At most 2 * tiled.MAX_VIEW_BATCH UNet rows
         ((1 + R) * batch_size).  Works with host_loop=True too."""
+        given = dict(tiled=tiled, hires=hires, control_net_image=control_net_image, reference_image=reference_image,
+                     inpaint_mask=inpaint_mask)
         reg = regions_mod.parse(regions, self.img_height, self.img_width)   # (ValueError for a bad description)
         if reg is not None:
-            refused = [n for n, v in (("tiled", tiled), ("hires", hires), ("control_net_image", control_net_image),
-                                      ("reference_image", reference_image), ("inpaint_mask", inpaint_mask)) if v is not None]
-            if self.active_tcd:
-                refused.append("a TCD pipeline (active_tcd=True)")
-            if self.denoise_streams == 2:
-                refused.append("denoise_streams = 2")
-            if refused:
-                raise ValueError(f"regions is text-to-image on one stream only: it cannot be combined with {', '.join(refused)}")
+            self._refuse_combinations("regions", given, host_loop)
             if (1 + reg.count) * int(batch_size) > 2 * tiled_mod.MAX_VIEW_BATCH:
                 raise ValueError(f"regions: {batch_size} image(s) of 1 + {reg.count} prompts are {(1 + reg.count) * int(batch_size)} UNet "
                                  f"rows per step, more than 2 * tiled.MAX_VIEW_BATCH = {2 * tiled_mod.MAX_VIEW_BATCH}: use fewer regions "
                                  "or a smaller batch")
         geo = tiled_mod.parse(tiled, self.img_height, self.img_width)   # (ValueError for a bad description)
         if geo is not None:
-            refused = [n for n, v in (("reference_image", reference_image), ("inpaint_mask", inpaint_mask),
-                                      ("control_net_image", control_net_image), ("hires", hires)) if v is not None]
-            if host_loop:
-                refused.append("host_loop=True")
-            if self.active_tcd:
-                refused.append("a TCD pipeline (active_tcd=True)")
-            if refused:
-                raise ValueError(f"tiled is text-to-image on the device loop only: it cannot be combined with {', '.join(refused)}")
+            self._refuse_combinations("tiled", given, host_loop)
             if int(batch_size) * geo.views > tiled_mod.MAX_VIEW_BATCH:
                 raise ValueError(f"tiled: {batch_size} image(s) of {geo.rows} x {geo.cols} views are {int(batch_size) * geo.views} UNet rows "
                                  f"per step, more than tiled.MAX_VIEW_BATCH = {tiled_mod.MAX_VIEW_BATCH}: use a larger stride, a smaller "
@@ -802,14 +810,7 @@ class StableDiffusionBase:
         if job is None and hires_noise is not None:
             raise ValueError("`hires_noise` without `hires`")
         if job is not None:
-            refused = [n for n, v in (("reference_image", reference_image), ("inpaint_mask", inpaint_mask),
-                                      ("control_net_image", control_net_image)) if v is not None]
-            if host_loop:
-                refused.append("host_loop=True")
-            if self.active_tcd:
-                refused.append("a TCD pipeline (active_tcd=True)")
-            if refused:
-                raise ValueError(f"hires is text-to-image on the device loop only: it cannot be combined with {', '.join(refused)}")
+            self._refuse_combinations("hires", given, host_loop)
         if diffusion_noise is not None and seed is not None:
             raise ValueError("`diffusion_noise` and `seed` should not both be passed to `generate_image`. `seed` is only "
                              "used to generate diffusion noise when it's not already user-specified.")
@@ -854,13 +855,9 @@ class StableDiffusionBase:
         inpainting = latent_mask is not None and encoded is not None
         blend_pixels = pixel_mask is not None and picture01 is not None
         start_index = num_steps - run_steps  # position of the first executed timestep in the descending schedule
-        sched = sampler_z = None
-        if spec is not None:
-            sched = smp.schedule(spec, self.scheduler, num_steps)
-            if encoded is not None:   # (k-diffusion's entry point: the first executed evaluation's own alpha / sigma)
-                start_latent = sched.entry_latent(start_index, encoded, noise)
-            if spec.stochastic:   # the per-step draws of the GLOBAL batch, sample-major
-                sampler_z = smp.draw_step_noise(B, num_steps, noise.shape[1], noise.shape[2], seed)
+        sched, sampler_z = self._sampler_inputs(spec, B, num_steps, noise.shape[1], noise.shape[2], seed)
+        if sched is not None and encoded is not None:   # (k-diffusion's entry point: the first executed evaluation's own alpha / sigma)
+            start_latent = sched.entry_latent(start_index, encoded, noise)
         hint = self._hint_batch(control_net_image, B)
         g, phi = float(unconditional_guidance_scale), float(guidance_rescale)
         region_ctx = region_w = None
@@ -876,25 +873,21 @@ class StableDiffusionBase:
                 decoded = picture * (1.0 - mask) + decoded * mask
             return np.clip(decoded * 255.0, 0, 255).astype("uint8")
 
-        if host_loop and spec is not None:
-            latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
-                                             sampler_z, (encoded, noise, latent_mask[0]) if inpainting else None, region_w=region_w)
-            if return_latent:
-                return np.asarray(latent, dtype=np.float32)
-            return finish(self.image_decoder.predict_on_batch(latent))
         if host_loop:
-            latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending,
-                                     (encoded, noise, latent_mask[0]) if inpainting else None, region_w=region_w)
+            ip = (encoded, noise, latent_mask[0]) if inpainting else None
+            if spec is not None:
+                latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
+                                                 sampler_z, ip, region_w=region_w)
+            else:
+                latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending, ip,
+                                         region_w=region_w)
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
             return finish(self.image_decoder.predict_on_batch(latent))
 
         # ---- device loop, sharded over the process group when there is one --------------------------------
-        from . import dist as mdist
-
-        world = mdist.world_size() if getattr(self, "shard_batch", False) else 1
-        tcd_global = bool(self.active_tcd and world > 1)
-        per_sample, shared = {}, {}   # name -> array; insertion order = argument order of `local`
+        world = self._world()
+        per_sample, shared = {}, {}   # name -> array; insertion order = order in the packed broadcast
         if hint is not None:
             per_sample["hint"] = hint
         if inpainting:
@@ -902,44 +895,27 @@ class StableDiffusionBase:
             shared["encoded"], shared["mask"] = encoded, latent_mask[0]
         if blend_pixels and world > 1:   # rank 0's picture and mask are the ones every slice is blended with
             shared["picture"], shared["pixel_mask"] = picture01, pixel_mask
-        if tcd_global:
-            # the TCD sampler draws N(0,1) for the whole batch once per executed step but the last (scheduler.py:301): made
-            # here for the GLOBAL batch, in that order, so that a sample's draws do not depend on the number of ranks
-            zs = np.zeros((num_steps, B, noise[0].size), dtype=np.float32)
-            for i in range(start_index, num_steps - 1):
-                zs[i] = np.random.randn(*noise.shape).astype(np.float32).reshape(B, -1)
-            per_sample["tcd"] = np.ascontiguousarray(zs.transpose(1, 0, 2))
+        if self.active_tcd and world > 1:
+            # the TCD draws, made here for the GLOBAL batch so that a sample's draws do not depend on the number of ranks
+            per_sample["tcd"] = tcd_step_noise(B, num_steps, noise.shape[1], noise.shape[2], start_index)
         if sampler_z is not None:
             per_sample["sampler_z"] = sampler_z.reshape(B, num_steps, -1)
         if reg is not None:   # one context per region and the weights: whole on every rank
             shared["region_ctx"], shared["region_w"] = region_ctx, region_w
-        dev = getattr(self, "device", None) or self.diffusion_model.device
-        names = list(per_sample) + list(shared)
+        sname = None if spec is None else spec.name
 
-        def local(c, u, z, *rest):
-            """This rank's slice of the batch: engine for b samples -> prepare -> loop -> decode; returns a device tensor."""
-            a = dict(zip(names, rest))
+        def local(c, u, z, a):
+            """This rank's slice of the batch: one denoise pass -> decode; returns a device tensor."""
             b = int(z.shape[0])
-            hint_b = a.get("hint")
-            ip = (a["encoded"], a["noise"], a["mask"]) if inpainting else None
-            tcd_z = a.get("tcd")
-            R, rw = 0, a.get("region_w")
             if reg is not None:   # the region contexts, each repeated over this rank's samples; the base prompt's rows first
                 rc = a["region_ctx"]
                 rep = (lambda x: x.unsqueeze(0).expand(b, -1, -1)) if isinstance(rc, torch.Tensor) else (lambda x: np.repeat(x[None], b, axis=0))
                 c = ([c] if reg.base_weight > 0.0 else []) + [rep(rc[i]) for i in range(rc.shape[0])]
-                R = len(c)
-            tc = c[0].shape[1] if R else c.shape[1]
-            ek, pk = (dict(regions=R), dict(regions=rw)) if R else ({}, {})   # (a plain job's calls are what they always were)
-            if spec is None:
-                eng = self._engine(b, tc, u.shape[1], num_steps, g, phi, hint_b is not None, ip is not None, **ek)
-                eng.prepare(eng.contexts(u, c), z, self.scheduler, self.scheduler.timesteps, start_index, hint_b, ip, step_noise=tcd_z,
-                            **pk)
-            else:
-                eng = self._engine(b, tc, u.shape[1], num_steps, g, phi, hint_b is not None, ip is not None, sampler=spec.name, **ek)
-                eng.prepare(eng.contexts(u, c), z, self.scheduler, self.scheduler.timesteps, start_index, hint_b, ip,
-                            step_noise=a.get("sampler_z"), sampler=sched, **pk)
-            eng.run_steps(run_steps, callback)
+            eng = self._denoise_pass(u, c, z, num_steps, g, phi, start_index, run_steps, callback,
+                                     dict(sampler=sname, regions=None if reg is None else len(c)),
+                                     dict(hint_image=a.get("hint"), inpaint=(a["encoded"], a["noise"], a["mask"]) if inpainting else None,
+                                          step_noise=a.get("tcd") if spec is None else a.get("sampler_z"), sampler=sched,
+                                          regions=a.get("region_w")))
             if return_latent:
                 return eng.latent
             if blend_pixels:   # pixel blend in fp32 before the uint8 cast
@@ -947,11 +923,68 @@ class StableDiffusionBase:
                 return torch.from_numpy(finish(self.image_decoder.predict_on_batch(eng.latent), *host)).to(eng.latent.device)
             return self.image_decoder.decode_to_uint8(eng.latent)
 
+        return self._run_sharded(local, context, unconditional_context, start_latent, per_sample, shared)
+
+    # job kind -> (what it is, the arguments and then the states it cannot be combined with, in the order the error names them)
+    _REFUSED = {
+        "regions": ("text-to-image on one stream only", ("tiled", "hires", "control_net_image", "reference_image", "inpaint_mask"),
+                    ("a TCD pipeline (active_tcd=True)", "denoise_streams = 2")),
+        "tiled": ("text-to-image on the device loop only", ("reference_image", "inpaint_mask", "control_net_image", "hires"),
+                  ("host_loop=True", "a TCD pipeline (active_tcd=True)")),
+        "hires": ("text-to-image on the device loop only", ("reference_image", "inpaint_mask", "control_net_image"),
+                  ("host_loop=True", "a TCD pipeline (active_tcd=True)")),
+    }
+
+    def _refuse_combinations(self, kind, given: dict, host_loop) -> None:
+        """ValueError naming every argument of `given` that is set and every state that holds which job `kind` cannot take."""
+        what, arguments, states = self._REFUSED[kind]
+        holds = {"host_loop=True": host_loop, "a TCD pipeline (active_tcd=True)": self.active_tcd,
+                 "denoise_streams = 2": self.denoise_streams == 2}
+        refused = [n for n in arguments if given[n] is not None] + [s for s in states if holds[s]]
+        if refused:
+            raise ValueError(f"{kind} is {what}: it cannot be combined with {', '.join(refused)}")
+
+    def _sampler_inputs(self, spec, B, steps, h, w, seed, stream_key=1):
+        """(the sampler's Schedule over `steps`, a stochastic sampler's per-step draws of the GLOBAL batch (B, steps, h, w, 4),
+        sample-major, else None); (None, None) without a sampler."""
+        if spec is None:
+            return None, None
+        sched = smp.schedule(spec, self.scheduler, steps)
+        return sched, smp.draw_step_noise(B, steps, h, w, seed, stream_key=stream_key) if spec.stochastic else None
+
+    def _world(self) -> int:
+        """Ranks this job's batch is sharded over."""
+        from . import dist as mdist
+
+        return mdist.world_size() if getattr(self, "shard_batch", False) else 1
+
+    def _run_sharded(self, local, context, unconditional_context, noise, per_sample: dict, shared: dict):
+        """The tail of every device-loop job: `local(context, unconditional_context, noise, extras)` runs on this rank's slice of
+        the batch - `extras` holding the slices of `per_sample` (name -> array of the GLOBAL batch) and `shared` (name -> array
+        every rank needs whole) by name - and returns a device tensor; the gathered result comes back as a host array."""
+        from . import dist as mdist
+
+        dev = getattr(self, "device", None) or self.diffusion_model.device
+        names = list(per_sample) + list(shared)
         # (a one-rank group with FORCE_COLLECTIVES still takes the real exchanges: tests/test_rccl_gpu.py)
-        sharded = world > 1 or (getattr(self, "shard_batch", False) and mdist.collectives_on())
-        out = mdist.generate_sharded(local, context, unconditional_context, start_latent, dev,
-                                     per_sample=list(per_sample.values()), shared=list(shared.values()), shard=sharded)
+        sharded = self._world() > 1 or (getattr(self, "shard_batch", False) and mdist.collectives_on())
+        out = mdist.generate_sharded(lambda c, u, z, *rest: local(c, u, z, dict(zip(names, rest))), context, unconditional_context,
+                                     noise, dev, per_sample=list(per_sample.values()), shared=list(shared.values()), shard=sharded)
         return self._to_host(out, dev, sharded)
+
+    def _denoise_pass(self, u, c, start, steps, g, phi, first, count, callback, engine_opts: dict, extras: dict) -> DenoiseEngine:
+        """Engine for these rows -> contexts -> prepare -> `count` steps from step `first` of the `steps`-step schedule; returns the
+        engine.  `start`: the start latent, or a function of the engine whose device work leaves it in `engine.latent`.
+        `engine_opts` (_engine's keywords) and `extras` (prepare's) are passed on without their None entries, so a job hands
+        _engine and prepare only what is its own."""
+        engine_opts, extras = ({k: v for k, v in d.items() if v is not None} for d in (engine_opts, extras))
+        tc = c[0].shape[1] if isinstance(c, list) else c.shape[1]
+        eng = self._engine(int(u.shape[0]), tc, u.shape[1], steps, g, phi, "hint_image" in extras, "inpaint" in extras, **engine_opts)
+        if callable(start):
+            start = start(eng)
+        eng.prepare(eng.contexts(u, c), start, self.scheduler, self.scheduler.timesteps, first, **extras)
+        eng.run_steps(count, callback)
+        return eng
 
     def _to_host(self, out, dev, sharded):
         """The job's device result -> host array, behind the cluster-GroupNorm give-up check."""
@@ -995,102 +1028,75 @@ class StableDiffusionBase:
         """Pass 1 (the txt2img job at the pipeline's own size, no decode) -> one msd_latent_resample launch from the pass-1 engine's
         latent into the pass-2 engine's, scaled and re-noised with the pass-2 entry rates -> pass 2 at the target size -> decode.
         Both engines stay resident, so a repeated job constructs nothing and captures nothing."""
-        from . import dist as mdist
-
         B = noise.shape[0]
         h1, w1, h2, w2 = self.img_height // 8, self.img_width // 8, job.height // 8, job.width // 8
         a2, s2, start2, run2 = hires_mod.entry(self.scheduler, spec, job.steps, job.strength)
         zh = hires_mod.draw_noise(B, h2, w2, seed) if hires_noise is None else self._batch_of(hires_noise, B, 3)
         if tuple(zh.shape) != (B, h2, w2, 4):
             raise ValueError(f"hires_noise has shape {tuple(zh.shape)}, the {job.height}x{job.width} latent of batch {B} is {(B, h2, w2, 4)}")
-        per_sample = {"hires_noise": zh}   # name -> array of the GLOBAL batch; insertion order = argument order of `local`
-        sched1 = sched2 = None
-        if spec is not None:
-            sched1, sched2 = smp.schedule(spec, self.scheduler, num_steps), smp.schedule(spec, self.scheduler, job.steps)
-            if spec.stochastic:   # the per-step draws of the global batch, sample-major: pass 1 [seed, 1], pass 2 [seed, 3]
-                per_sample["z1"] = smp.draw_step_noise(B, num_steps, h1, w1, seed).reshape(B, num_steps, -1)
-                per_sample["z2"] = smp.draw_step_noise(B, job.steps, h2, w2, seed, stream_key=3).reshape(B, job.steps, -1)
+        per_sample = {"hires_noise": zh}
+        # (a stochastic sampler's draws: pass 1 [seed, 1], pass 2 [seed, 3])
+        sched1, z1 = self._sampler_inputs(spec, B, num_steps, h1, w1, seed)
+        sched2, z2 = self._sampler_inputs(spec, B, job.steps, h2, w2, seed, stream_key=3)
+        if z1 is not None:
+            per_sample["z1"], per_sample["z2"] = z1.reshape(B, num_steps, -1), z2.reshape(B, job.steps, -1)
         sname = None if spec is None else spec.name
-        dev = getattr(self, "device", None) or self.diffusion_model.device
-        names = list(per_sample)
         callback2 = None if callback is None else (lambda i: callback(num_steps + i))
 
-        def local(c, u, z, *rest):
-            """This rank's slice: both engines -> pass 1 -> hand-off -> pass 2 -> decode; returns a device tensor."""
-            a = dict(zip(names, rest))
+        def local(c, u, z, a):
+            """This rank's slice: pass 1 -> hand-off into the pass-2 engine -> pass 2 -> decode; returns a device tensor."""
             b = int(z.shape[0])
-            unet2 = self._unet_for(job.height, job.width)
-            shapes = [dict(steps=num_steps, unet=None), dict(steps=job.steps, unet=unet2)]
-            keys = [self._engine_key(b, c.shape[1], u.shape[1], s["steps"], g, phi, False, sampler=sname, unet=s["unet"]) for s in shapes]
-            eng1, eng2 = (self._engine(b, c.shape[1], u.shape[1], s["steps"], g, phi, False, sampler=sname, unet=s["unet"], job_keys=keys)
-                          for s in shapes)
+            opts = [dict(sampler=sname), dict(sampler=sname, unet=self._unet_for(job.height, job.width))]
+            # (both keys in front of the first build: whatever neither pass needs goes before either arena is allocated)
+            keys = [self._engine_key(b, c.shape[1], u.shape[1], n, g, phi, False, **o) for n, o in zip((num_steps, job.steps), opts)]
             self.scheduler.set_timesteps(num_steps)
-            eng1.prepare(eng1.contexts(u, c), z, self.scheduler, self.scheduler.timesteps, 0, step_noise=a.get("z1"), sampler=sched1)
-            eng1.run_steps(num_steps, callback)
-            wx, wy = self._hires_taps(h1, w1, h2, w2, job.upscaler, eng1.latent.device)
-            zh_dev = _f32_tensor(a["hires_noise"]).to(eng1.latent.device).contiguous()
-            if zh_dev.data_ptr() % 16:   # (a slice of a packed broadcast buffer: the kernel reads 16-byte vectors)
-                zh_dev = zh_dev.clone()
-            ops.latent_resample(x=eng1.latent, out=eng2.latent, wx=wx, wy=wy, batch=b, h_in=h1, w_in=w1, h_out=h2, w_out=w2,
-                                a=a2, s=s2, noise=zh_dev)(torch.cuda.current_stream().cuda_stream)
+            eng1 = self._denoise_pass(u, c, z, num_steps, g, phi, 0, num_steps, callback, dict(opts[0], job_keys=keys),
+                                      dict(step_noise=a.get("z1"), sampler=sched1))
+
+            def hand_off(eng2):
+                wx, wy = self._hires_taps(h1, w1, h2, w2, job.upscaler, eng1.latent.device)
+                zh_dev = _f32_tensor(a["hires_noise"]).to(eng1.latent.device).contiguous()
+                if zh_dev.data_ptr() % 16:   # (a slice of a packed broadcast buffer: the kernel reads 16-byte vectors)
+                    zh_dev = zh_dev.clone()
+                ops.latent_resample(x=eng1.latent, out=eng2.latent, wx=wx, wy=wy, batch=b, h_in=h1, w_in=w1, h_out=h2, w_out=w2,
+                                    a=a2, s=s2, noise=zh_dev)(torch.cuda.current_stream().cuda_stream)
+
             self.scheduler.set_timesteps(job.steps)
-            eng2.prepare(eng2.contexts(u, c), None, self.scheduler, self.scheduler.timesteps, start2, step_noise=a.get("z2"),
-                         sampler=sched2)
-            eng2.run_steps(run2, callback2)
+            eng2 = self._denoise_pass(u, c, hand_off, job.steps, g, phi, start2, run2, callback2, dict(opts[1], job_keys=keys),
+                                      dict(step_noise=a.get("z2"), sampler=sched2))
             if return_latent:
                 return eng2.latent
             return self.image_decoder.decode_to_uint8(eng2.latent)
 
-        sharded = (mdist.world_size() if getattr(self, "shard_batch", False) else 1) > 1 or \
-            (getattr(self, "shard_batch", False) and mdist.collectives_on())
-        out = mdist.generate_sharded(local, context, unconditional_context, noise, dev, per_sample=list(per_sample.values()),
-                                     shard=sharded)
-        return self._to_host(out, dev, sharded)
+        return self._run_sharded(local, context, unconditional_context, noise, per_sample, {})
 
     # ---- tiled diffusion: the views of a canvas as batch rows of one engine (minsdtf_amd/tiled.py, DESIGN.md 4.7)
     def _generate_tiled(self, geo, spec, context, unconditional_context, noise, num_steps, g, phi, seed, callback, return_latent):
         """One engine of batch images * V keyed by the geometry: the canvas noise is uploaded and gathered into the views by one
         launch, the loop (UNet on every view, sampler step per view, consensus) is the engine's replayed graph, the canvas latent
         is decoded.  The engine stays resident, so a repeated job constructs nothing and captures nothing."""
-        from . import dist as mdist
-
         B, V = noise.shape[0], geo.views
         self.scheduler.set_timesteps(num_steps)
-        sched = None
-        per_sample = {}   # name -> array of the GLOBAL batch; insertion order = argument order of `local`
-        if spec is not None:
-            sched = smp.schedule(spec, self.scheduler, num_steps)
-            if spec.stochastic:   # drawn at CANVAS shape and cut per view (tiled.slice_views): overlapping pixels share a draw
-                per_sample["sampler_z"] = smp.draw_step_noise(B, num_steps, geo.H, geo.W, seed).reshape(B, num_steps, -1)
-        sname = None if spec is None else spec.name
-        dev = getattr(self, "device", None) or self.diffusion_model.device
-        names = list(per_sample)
+        # (a stochastic sampler's draws at CANVAS shape, cut per view (tiled.slice_views): overlapping pixels share a draw)
+        sched, sampler_z = self._sampler_inputs(spec, B, num_steps, geo.H, geo.W, seed)
+        per_sample = {} if sampler_z is None else {"sampler_z": sampler_z.reshape(B, num_steps, -1)}
 
         def per_view(x):
             """(b, ...) -> (b * V, ...): a sample's rows repeated for its V views (sample-major)."""
             return x.repeat_interleave(V, dim=0) if isinstance(x, torch.Tensor) else np.repeat(x, V, axis=0)
 
-        def local(c, u, z, *rest):
+        def local(c, u, z, a):
             """This rank's slice of the images: engine for b * V views -> gather -> prepare -> loop -> decode the canvas."""
-            a = dict(zip(names, rest))
-            b = int(z.shape[0])
-            eng = self._engine(b * V, c.shape[1], u.shape[1], num_steps, g, phi, False, sampler=sname, tiled=geo)
             zs = a.get("sampler_z")
             if zs is not None:
-                zs = tiled_mod.slice_views(zs.reshape(b, num_steps, geo.H, geo.W, 4), geo)
-            eng.load_canvas(z)
-            eng.prepare(eng.contexts(per_view(u), per_view(c)), None, self.scheduler, self.scheduler.timesteps, 0, step_noise=zs,
-                        sampler=sched)
-            eng.run_steps(num_steps, callback)
+                zs = tiled_mod.slice_views(zs.reshape(int(z.shape[0]), num_steps, geo.H, geo.W, 4), geo)
+            eng = self._denoise_pass(per_view(u), per_view(c), lambda eng: eng.load_canvas(z), num_steps, g, phi, 0, num_steps, callback,
+                                     dict(sampler=None if spec is None else spec.name, tiled=geo), dict(step_noise=zs, sampler=sched))
             if return_latent:
                 return eng.canvas
             return self.image_decoder.decode_to_uint8(eng.canvas)
 
-        sharded = (mdist.world_size() if getattr(self, "shard_batch", False) else 1) > 1 or \
-            (getattr(self, "shard_batch", False) and mdist.collectives_on())
-        out = mdist.generate_sharded(local, context, unconditional_context, noise, dev, per_sample=list(per_sample.values()),
-                                     shard=sharded)
-        return self._to_host(out, dev, sharded)
+        return self._run_sharded(local, context, unconditional_context, noise, per_sample, {})
 
     # ---- regional prompting: one prompt per masked region (minsdtf_amd/regions.py, DESIGN.md 4.8)
     def _region_inputs(self, reg, context):
@@ -1111,27 +1117,29 @@ class StableDiffusionBase:
                              + ", ".join(f"{w}: {n}" for w, n in lengths))
         return np.stack(encoded, axis=0), reg.weights()
 
-    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None, tiled=None, regions=0) -> tuple:
+    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> tuple:
+        """`opts`: sampler / unet / tiled / regions as _engine takes them; one at its default (None) adds nothing to the key."""
         # the engine's plans (and captured hipGraphs) hold raw addresses of the packed weights: a set_weights() /
         # load_synthetic() / LoRA reload on any of the models it was built from must retire it
         base = self.diffusion_model
-        unet = base if unet is None else unet
+        unet, tiled, regions = opts.get("unet") or base, opts.get("tiled"), opts.get("regions")
         wver = (unet.weights_version,) + ((self.control_net.weights_version, self.hint_net.weights_version) if control else ())
-        key = (B, tc, tu, steps, g, phi, control, self.denoise_streams, inpaint, self.active_tcd, wver, engine.GN_EPOCH, sampler)
+        key = (B, tc, tu, steps, g, phi, control, self.denoise_streams, inpaint, self.active_tcd, wver, engine.GN_EPOCH, opts.get("sampler"))
         key = key if unet is base else key + ((unet.h, unet.w),)   # (a hires job's second size: a view of the same weights)
         key = key if tiled is None else key + (tiled.key,)         # (a tiled job: B counts views)
         # (a regional job: the NUMBER of evaluated region prompts only - masks, weights and prompts are per-call uploads)
         return key if not regions else key + (("regions", int(regions)),)
 
-    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, sampler=None, unet=None, job_keys=None,
-                tiled=None, regions=0) -> DenoiseEngine:
-        """The resident engine of this shape, built if need be.  `unet`: the UNet of another size (a hires job's second pass);
-        `job_keys`: the keys of every engine the current job uses (default: this one alone); `tiled`: the geometry of a tiled job
-        (B counts its views); `regions`: the number of evaluated region prompts of a regional job.  The engines' arenas are the big
-        allocations, so whatever the current job does not need goes BEFORE anything is built: a re-recording (another shape,
-        new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than the job's own engines - one for a
-        plain job, two for a hires job."""
-        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, sampler, unet, tiled, regions)
+    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> DenoiseEngine:
+        """The resident engine of this shape, built if need be.  `opts` are DenoiseEngine's: `sampler`; `unet`: the UNet of another
+        size (a hires job's second pass); `tiled`: the geometry of a tiled job (B counts its views); `regions`: the number of
+        evaluated region prompts of a regional job.  `job_keys`: the keys of every engine the current job uses (default: this one
+        alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is
+        built: a re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than
+        the job's own engines - one for a plain job, two for a hires job."""
+        if not set(opts) <= {"sampler", "unet", "tiled", "regions"}:
+            raise TypeError(f"_engine: unknown option among {sorted(opts)}")
+        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, **opts)
         keep = {key} | set(job_keys or ())
         if any(k not in keep for k in self._engines):
             import gc
@@ -1144,11 +1152,11 @@ class StableDiffusionBase:
             gc.collect()
         eng = self._engines.get(key)
         if eng is None:
-            eng = DenoiseEngine(self.diffusion_model if unet is None else unet, B, tc, tu, steps, g, phi,
+            eng = DenoiseEngine(opts.get("unet") or self.diffusion_model, B, tc, tu, steps, g, phi,
                                 control_net=self.control_net if control else None,
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
-                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=sampler, tiled=tiled,
-                                regions=regions)
+                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=opts.get("sampler"),
+                                tiled=opts.get("tiled"), regions=opts.get("regions") or 0)
             self._engines[key] = eng
         return eng
 
@@ -1179,30 +1187,21 @@ class StableDiffusionBase:
         """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
         A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
         predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host)."""
-        if isinstance(context, (list, tuple)):
-            c = regions_mod.combine_host([self.diffusion_model.predict_on_batch([latent, t_emb, rc]) for rc in context], region_w)
-            if g <= 0.0:
-                return c
-            u = self.diffusion_model.predict_on_batch([latent, t_emb, unconditional_context])
-            e = u + g * (c - u)
-            return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
-        if g > 0.0:
-            if hint is not None:
-                uc = self.control_net.predict_on_batch([latent, t_emb, unconditional_context, hint])
-                u = self.diffusion_model.predict_on_batch([latent, t_emb, unconditional_context] + list(uc))
-                cc = self.control_net.predict_on_batch([latent, t_emb, context, hint])
-                c = self.diffusion_model.predict_on_batch([latent, t_emb, context] + list(cc))
-            else:
-                u = self.diffusion_model.predict_on_batch([latent, t_emb, unconditional_context])
-                c = self.diffusion_model.predict_on_batch([latent, t_emb, context])
-            e = u + g * (c - u)
-            if phi > 0.0:
-                e = rescale_noise_cfg(e, c, guidance_rescale=phi)
-            return e
-        if hint is not None:
-            cc = self.control_net.predict_on_batch([latent, t_emb, context, hint])
-            return self.diffusion_model.predict_on_batch([latent, t_emb, context] + list(cc))
-        return self.diffusion_model.predict_on_batch([latent, t_emb, context])
+        def predict(ctx):
+            """The UNet's prediction for one context, through the ControlNet if there is a hint."""
+            if hint is None:
+                return self.diffusion_model.predict_on_batch([latent, t_emb, ctx])
+            controls = self.control_net.predict_on_batch([latent, t_emb, ctx, hint])
+            return self.diffusion_model.predict_on_batch([latent, t_emb, ctx] + list(controls))
+
+        regional = isinstance(context, (list, tuple))   # (its region prompts run in front of the unconditional one)
+        c = regions_mod.combine_host([predict(rc) for rc in context], region_w) if regional else None
+        u = predict(unconditional_context) if g > 0.0 else None
+        c = c if regional else predict(context)
+        if u is None:
+            return c
+        e = u + g * (c - u)
+        return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
 
     def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
                            inpaint=None, region_w=None):

@@ -1,8 +1,14 @@
-"""Child process of tests/test_regions_gpu.py: a ONE-rank torch.distributed process group (backend nccl = RCCL, on cuda:0) whose
-exchanges really run (minsdtf_amd.dist.FORCE_COLLECTIVES), as tests/_collectives_world1_child.py sets one up.  A regional job
-with shard_batch = True then takes the sharded route - the region contexts and the normalised weights travel whole in the packed
-broadcast, a stochastic sampler's draws are sliced per sample - and must give the bits of the unsharded job.  A fresh
-interpreter: the process group is created before anything else touches the GPU.  Prints one line `OK {...json...}`."""
+"""Child process of tests/test_hires_gpu.py, tests/test_tiled_gpu.py and tests/test_regions_gpu.py: a ONE-rank torch.distributed
+process group (backend nccl = RCCL, on cuda:0) whose exchanges really run (minsdtf_amd.dist.FORCE_COLLECTIVES), as
+tests/_collectives_world1_child.py sets one up.  The job named by the argument (hires | tiled | regions) with shard_batch = True
+then takes the sharded route and must give the bits of the unsharded job:
+* hires: the re-noise draw and the second pass's step draws travel in the packed broadcast, both passes and the hand-off run
+  inside the rank's slice;
+* tiled: the canvas noise is the sharded start latent, a stochastic sampler's canvas-shaped step draws travel in the packed
+  broadcast and are cut per view inside the rank's slice;
+* regions: the region contexts and the normalised weights travel whole in the packed broadcast, a stochastic sampler's draws are
+  sliced per sample.
+A fresh interpreter: the process group is created before anything else touches the GPU.  Prints one line `OK {...json...}`."""
 import json
 import os
 import socket
@@ -12,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def main():
+def main(kind):
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
@@ -39,11 +45,20 @@ def main():
     sd.diffusion_model.load_synthetic(seed=0)
     sd.image_decoder.load_synthetic(seed=0)
     rng = np.random.default_rng(11)
-    ctx, p, q = (rng.standard_normal((77, 768)).astype(np.float32) for _ in range(3))
+    ctx = rng.standard_normal((77, 768)).astype(np.float32)
+    region_job = None
+    if kind == "regions":
+        p, q = (rng.standard_normal((77, 768)).astype(np.float32) for _ in range(2))
+        y, x = np.mgrid[0:8, 0:8] / 7.0
+        region_job = dict(regions=[dict(prompt=p, mask=1.0 - x), dict(prompt=q, mask=x + 0.1 * y, weight=2.0)], base_weight=0.3)
+        assert regions.parse(region_job, 64, 64).count == 3
     sd.unconditional_context = rng.standard_normal((77, 768)).astype(np.float32)
-    y, x = np.mgrid[0:8, 0:8] / 7.0
-    job = dict(regions=[dict(prompt=p, mask=1.0 - x), dict(prompt=q, mask=x + 0.1 * y, weight=2.0)], base_weight=0.3)
-    assert regions.parse(job, 64, 64).count == 3
+    # the job's keyword, the image's shape, the latent's shape (None: not checked)
+    job, image_shape, latent_shape = {
+        "hires": (dict(hires=dict(scale=2, steps=4, strength=0.5, upscaler="bicubic")), (2, 128, 128, 3), None),
+        "tiled": (dict(tiled=dict(size=(64, 128), stride=32, blend="gaussian")), (2, 64, 128, 3), (2, 8, 16, 4)),
+        "regions": (dict(regions=region_job), (2, 64, 64, 3), (2, 8, 8, 4)),
+    }[kind]
     calls = {"broadcast": 0, "all_gather_into_tensor": 0}
     real = {k: getattr(dist, k) for k in calls}
 
@@ -57,7 +72,7 @@ def main():
         setattr(dist, k, counted(k))
     info = {}
     for sampler in (None, "euler_a"):
-        kw = dict(batch_size=2, num_steps=3, unconditional_guidance_scale=7.5, seed=5, guidance_rescale=0.7, sampler=sampler, regions=job)
+        kw = dict(batch_size=2, num_steps=3, unconditional_guidance_scale=7.5, seed=5, guidance_rescale=0.7, sampler=sampler, **job)
         n0 = dict(calls)
         mdist.FORCE_COLLECTIVES = True
         forced = sd.generate_image(ctx, **kw)
@@ -68,9 +83,11 @@ def main():
         plain = sd.generate_image(ctx, **kw)
         plain_latent = sd.generate_image(ctx, return_latent=True, **kw)
         assert calls == n1, "the un-forced run must not touch the process group"
-        assert forced.shape == (2, 64, 64, 3) and forced_latent.shape == (2, 8, 8, 4) and forced.dtype == np.uint8
+        assert forced.shape == image_shape and forced.dtype == np.uint8
+        assert latent_shape is None or forced_latent.shape == latent_shape
         assert np.array_equal(forced, plain) and np.array_equal(forced_latent, plain_latent), "the collectives changed the result"
-        assert len(sd._engines) == 1 and next(iter(sd._engines.values())).regions == 3
+        if kind == "regions":
+            assert len(sd._engines) == 1 and next(iter(sd._engines.values())).regions == 3
         info[str(sampler)] = "bit-identical"
     for k in calls:
         setattr(dist, k, real[k])
@@ -82,4 +99,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1])

@@ -708,3 +708,80 @@ def test_form_of_covers_the_code_space():
     for call in (lambda: t.form_of(6000, 64, 0), lambda: t.numerics_class(1, 6000, 64, 1)):
         with pytest.raises(ValueError):
             call()
+
+
+# ------------------------------------------------------------------ the refused job combinations, word for word
+def test_refused_combinations_say_what_they_always_said():
+    """Every refusal of a regional / tiled / hires job, and DenoiseEngine's own for direct construction: the whole message, as
+    the pipeline worded it before one table drove them; the order in which several refusals are named; nothing built."""
+    import types
+
+    import torch
+
+    from minsdtf_amd import tiled as T
+    from minsdtf_amd.stable_diffusion import DenoiseEngine, StableDiffusion
+
+    ctx, img = np.zeros((77, 768), dtype=np.float32), np.zeros((64, 64, 3), dtype=np.uint8)
+    jobs = {"regions": dict(regions=[dict(prompt=ctx, mask=np.ones((8, 8), np.float32))]), "tiled": dict(size=(64, 128), stride=32),
+            "hires": dict(scale=2)}
+    args = dict(tiled=jobs["tiled"], hires=jobs["hires"], control_net_image=img.astype(np.float32), reference_image=img,
+                inpaint_mask=img[..., 0], host_loop=True)
+    TCD, S2 = "a TCD pipeline (active_tcd=True)", "denoise_streams = 2"
+    heads = {"regions": "regions is text-to-image on one stream only: it cannot be combined with ",
+             "tiled": "tiled is text-to-image on the device loop only: it cannot be combined with ",
+             "hires": "hires is text-to-image on the device loop only: it cannot be combined with "}
+    # (job kind, arguments given, TCD pipeline, denoise_streams = 2) -> what the message names, in its order
+    cases = [("regions", (a,), False, False, a) for a in ("tiled", "hires", "control_net_image", "reference_image", "inpaint_mask")]
+    cases += [("tiled", (a,), False, False, a) for a in ("hires", "control_net_image", "reference_image", "inpaint_mask")]
+    cases += [("hires", (a,), False, False, a) for a in ("control_net_image", "reference_image", "inpaint_mask")]
+    cases += [
+        ("regions", ("inpaint_mask", "reference_image", "control_net_image", "hires", "tiled"), False, False,
+         "tiled, hires, control_net_image, reference_image, inpaint_mask"),
+        ("regions", (), True, False, TCD), ("regions", (), False, True, S2), ("regions", ("tiled",), True, True, f"tiled, {TCD}, {S2}"),
+        ("regions", ("hires",), False, True, f"hires, {S2}"), ("regions", ("control_net_image",), True, False, f"control_net_image, {TCD}"),
+        ("tiled", ("hires", "control_net_image", "inpaint_mask", "reference_image"), False, False,
+         "reference_image, inpaint_mask, control_net_image, hires"),
+        ("tiled", ("host_loop",), False, False, "host_loop=True"), ("tiled", (), True, False, TCD),
+        ("tiled", ("host_loop", "reference_image"), True, False, f"reference_image, host_loop=True, {TCD}"),
+        ("tiled", ("hires",), True, False, f"hires, {TCD}"),
+        ("hires", ("control_net_image", "inpaint_mask", "reference_image"), False, False, "reference_image, inpaint_mask, control_net_image"),
+        ("hires", ("host_loop",), False, False, "host_loop=True"), ("hires", (), True, False, TCD),
+        ("hires", ("host_loop", "reference_image"), True, False, f"reference_image, host_loop=True, {TCD}"),
+        ("hires", ("inpaint_mask",), True, False, f"inpaint_mask, {TCD}"),
+    ]
+    built = []
+    for kind, given, tcd, streams2, named in cases:
+        p = StableDiffusion(64, 64, device=torch.device("cpu"), active_tcd=tcd)
+        p.unconditional_context, p.denoise_streams = ctx, 2 if streams2 else None
+        with pytest.raises(ValueError) as e:
+            p.generate_image(ctx, batch_size=1, num_steps=4, seed=0, **{kind: jobs[kind]}, **{a: args[a] for a in given})
+        assert str(e.value) == heads[kind] + named, (kind, given, tcd, streams2)
+        built.append(p._engines)
+    # a regional job is checked first, its batch-row limit included; a tiled job's limit comes behind its own refusals
+    p = StableDiffusion(64, 64, device=torch.device("cpu"))
+    p.unconditional_context = ctx
+    for kw, msg in ((dict(regions=jobs["regions"], batch_size=17),
+                     "regions: 17 image(s) of 1 + 1 prompts are 34 UNet rows per step, more than 2 * tiled.MAX_VIEW_BATCH = 12: use fewer "
+                     "regions or a smaller batch"),
+                    (dict(tiled=jobs["tiled"], batch_size=6),
+                     "tiled: 6 image(s) of 1 x 3 views are 18 UNet rows per step, more than tiled.MAX_VIEW_BATCH = 6: use a larger stride, "
+                     "a smaller canvas or a smaller batch"),
+                    (dict(regions=jobs["regions"], tiled=jobs["tiled"], batch_size=17), heads["regions"] + "tiled"),
+                    (dict(tiled=jobs["tiled"], batch_size=6, host_loop=True), heads["tiled"] + "host_loop=True")):
+        with pytest.raises(ValueError) as e:
+            p.generate_image(ctx, num_steps=4, seed=0, **kw)
+        assert str(e.value) == msg
+    assert not p._engines and not any(built)
+    # direct construction: refused before anything is allocated (a stand-in UNet on the CPU gets that far)
+    geo = T.parse(jobs["tiled"], 64, 64)
+    unet = types.SimpleNamespace(_require_weights=lambda: None, h=8, w=8, device=torch.device("cpu"))
+    one_stream = "regions: text-to-image on one stream only (no ControlNet, inpainting, TCD, tiled, denoise_streams = 2)"
+    for B, kw, msg in ((3, dict(tiled=geo, inpaint=True), "tiled: text-to-image only (no ControlNet, inpainting or TCD)"),
+                       (3, dict(tiled=geo, tcd=True), "tiled: text-to-image only (no ControlNet, inpainting or TCD)"),
+                       (2, dict(tiled=geo), "tiled: 3 views of 8 x 8 on an engine of batch 2 at 8 x 8"),
+                       (3, dict(sampler="euler_a", tcd=True), "a sampler cannot be combined with the TCD sampler"),
+                       (3, dict(regions=2, streams=2), one_stream), (3, dict(regions=2, inpaint=True), one_stream),
+                       (3, dict(regions=2, tiled=geo), one_stream), (3, dict(regions=99), "regions: 99 region prompts (1 .. 16)")):
+        with pytest.raises(ValueError) as e:
+            DenoiseEngine(unet, B, 77, 77, 4, 7.5, 0.7, **kw)
+        assert str(e.value) == msg

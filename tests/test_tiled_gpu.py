@@ -278,7 +278,8 @@ def test_batch_independence(gpu, nets, sampler):
 def test_sharded_tiled_equals_unsharded(gpu):
     """A one-rank process group with forced collectives (as tests/test_rccl_gpu.py): the sharded tiled job == the unsharded one."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(HERE, "_tiled_world1_child.py")], env=env, stdout=subprocess.PIPE,
+    p = subprocess.run([sys.executable, os.path.join(HERE, "_job_world1_child.py"), "tiled"], env=env,
+                       stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=570)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     assert any(line.startswith("OK ") for line in p.stdout.splitlines()), p.stdout[-2000:]
