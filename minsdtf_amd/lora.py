@@ -10,19 +10,22 @@ This module has three parts:
 
 * :func:`read_factors` - a kohya ``.safetensors`` / ``.pt`` file or state dict -> per target layer ``(up [N][r], down [r][K])``
   with ``alpha / r`` folded into ``up`` and ``down`` in the target's pack order; file results are cached on the device.
-* :func:`build_plan` - the merge plan of a packed model, derived from its weight table and the keys ``HipModel._pack`` made.
-* :class:`MergeBase` - the masters of one model and :meth:`MergeBase.apply` (validate, then prepare, then one launch).
+* :class:`Plan` - the merge plan of a packed model: the entries of its layout table (``layout.layout``, the description
+  ``packing.pack`` built the image from) that a targetable layer feeds.  Nothing here matches a layer name.
+* :class:`MergeBase` - the masters of one model (kept by the packing pass) and :meth:`MergeBase.apply` (validate, then prepare,
+  then one launch).
 """
 from __future__ import annotations
 
 import os
-from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import weights as wtab
+from .layout import VEC, Packed
+from .packing import geglu_row_order
 
 # --------------------------------------------------------------------------------------------------------------------------------
 # factors
@@ -92,53 +95,6 @@ def read_factors(source, device) -> Factors:
 # --------------------------------------------------------------------------------------------------------------------------------
 # merge plan
 # --------------------------------------------------------------------------------------------------------------------------------
-@dataclass
-class Part:
-    """One source layer's block of a packed matrix: logical rows [0, N) -> destination rows row_off + (rowmap or identity),
-    columns [0, K) -> col_off + k, values (master + U D) * rowscale[n] * colscale[k]."""
-    layer: str
-    row_off: int = 0
-    col_off: int = 0
-    qscale: Optional[float] = None        # uniform row scale (the query prescale)
-    colscale: Optional[str] = None        # packed key of the fp32 column scale (a LayerNorm gamma)
-    rowmap: bool = False                  # GEGLU row order
-    ffproj_top: bool = False              # the fused ff.net.2 . proj_out block (master and factors of its own)
-
-
-@dataclass
-class Target:
-    key: str
-    parts: List[Part]
-    colsum: Optional[str] = None          # .lncs key written from this matrix's rounded rows
-    lnb: Optional[Tuple[str, str]] = None  # (.lnb key, packed key of the LayerNorm beta)
-
-    @property
-    def sources(self):
-        s = set()
-        for p in self.parts:
-            s.add(p.layer)
-            if p.ffproj_top:
-                s.add(p.layer.replace(".transformer_blocks.0.ff.net.2", ".proj_out"))
-        return s
-
-
-@dataclass
-class Plan:
-    targets: List[Target]
-    layers: Dict[str, Tuple[int, int, int]]   # target layer -> (N, K, kernel size)
-    ffproj_b: Dict[str, Tuple[str, str]] = field(default_factory=dict)   # ffproj.b key -> (ff.net.2 layer, proj_out layer)
-
-    def keys(self):
-        ks = set()
-        for t in self.targets:
-            ks.add(t.key)
-            if t.colsum:
-                ks.add(t.colsum)
-            if t.lnb:
-                ks.add(t.lnb[0])
-        return ks | set(self.ffproj_b)
-
-
 def targetable(specs) -> Dict[str, Tuple[int, int, int]]:
     """Layers a LoRA may change (the names the reference restores) -> (N, K, kernel size)."""
     unet = {v[: -len(".weight")] for v in wtab._lora_unet_name_map().values()}
@@ -156,108 +112,36 @@ def targetable(specs) -> Dict[str, Tuple[int, int, int]]:
     return out
 
 
-def build_plan(specs, W) -> Plan:
-    """Every packed tensor each targetable layer feeds, following the decisions HipModel._pack made (read off the keys it
-    produced): stacked q|k|v / k|v, prescaled queries, the LayerNorm folds, the GEGLU row order, ffproj, conv2sc, the
-    concatenated time-embedding projections."""
-    from .models import _q_prescale
+class Plan:
+    """The part of a packed image a LoRA can change: the matrices of the layout table (layout.layout) that targetable layers
+    feed, in table order (the order of the merge jobs); the parts of each stay in the order they are stacked."""
 
-    layers = targetable(specs)
-    targets: Dict[str, Target] = {}
+    def __init__(self, specs, table: List[Packed]):
+        self.layers = targetable(specs)           # target layer -> (N, K, kernel size)
+        fed = lambda e: not e.sources.isdisjoint(self.layers)  # noqa: E731
+        self.targets = [e for e in table if e.store != VEC and fed(e)]
+        assert all(e.sources <= set(self.layers) for e in self.targets), "a packed matrix is switched as a whole"
+        # ffproj.b key -> (ff.net.2 layer, proj_out layer)
+        self.ffproj_b = {e.key: tuple(p.layer for p in e.parts) for e in table if e.how == "ffproj_b" and fed(e)}
 
-    def add(key, part, colsum=None, lnb=None):
-        if key not in W:
-            return
-        t = targets.get(key)
-        if t is None:
-            t = targets[key] = Target(key, [], colsum if colsum in W else None, lnb if lnb and lnb[0] in W else None)
-        t.parts.append(part)
-
-    tproj_off = 0
-    ffproj_b = {}
-    for s in specs:   # table order (the order _pack concatenates the time-embedding projections in)
-        n = s.name
-        if s.kind not in ("conv_w", "dense_w"):
-            continue
-        if n.endswith(".time_emb_proj"):
-            if n in layers:
-                add("time_emb_proj_cat.w", Part(n, row_off=tproj_off))
-            tproj_off += s.shape[1]
-            continue
-        if n not in layers:
-            continue
-        N = layers[n][0]
-        for trio, stacked in ((("attn1.to_q", "attn1.to_k", "attn1.to_v"), "attn1.qkv"),
-                              (("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "self_attn.qkv")):
-            hit = [i for i, x in enumerate(trio) if n.endswith("." + x)]
-            if hit:
-                i = hit[0]
-                base = n[: -len(trio[i])] + stacked
-                q = _q_prescale(N) if (i == 0 and stacked == "attn1.qkv") else None
-                add(base + ".w", Part(n, row_off=i * N, qscale=q))
-                if stacked == "attn1.qkv":
-                    tb = n[: -len(".attn1." + trio[i].split(".")[1])]
-                    add(base + ".lnw", Part(n, row_off=i * N, qscale=q, colscale=tb + ".norm1.g"), base + ".lncs",
-                        (base + ".lnb", tb + ".norm1.b"))
-                break
-        else:
-            if n.endswith(".attn2.to_q"):
-                tb = n[: -len(".attn2.to_q")]
-                q = _q_prescale(N)
-                add(n + ".w", Part(n, qscale=q))
-                add(n + ".lnw", Part(n, qscale=q, colscale=tb + ".norm2.g"), n + ".lncs", (n + ".lnb", tb + ".norm2.b"))
-            elif n.endswith((".attn2.to_k", ".attn2.to_v")):
-                add(n[: -len(".to_k")] + ".kv.w", Part(n, row_off=0 if n.endswith(".to_k") else N))
-            elif n.endswith(".ff.net.0.proj"):
-                tb = n[: -len(".ff.net.0.proj")]
-                add(n + ".w", Part(n, rowmap=True))
-                add(n + ".lnw", Part(n, rowmap=True, colscale=tb + ".norm3.g"), n + ".lncs", (n + ".lnb", tb + ".norm3.b"))
-            else:
-                add(n + ".w", Part(n))
-                if n.endswith(".transformer_blocks.0.ff.net.2"):
-                    att = n[: -len(".transformer_blocks.0.ff.net.2")]
-                    add(att + ".ffproj.w", Part(n, ffproj_top=True))
-                    if att + ".ffproj.b" in W:
-                        ffproj_b[att + ".ffproj.b"] = (n, att + ".proj_out")
-                elif n.endswith(".proj_out"):
-                    att = n[: -len(".proj_out")]
-                    tb2 = att + ".transformer_blocks.0.ff.net.2"
-                    if tb2 in layers:
-                        add(att + ".ffproj.w", Part(n, col_off=layers[tb2][1]))
-                elif n.endswith(".conv2"):
-                    add(n[: -len(".conv2")] + ".conv2sc.w", Part(n))
-                elif n.endswith(".conv_shortcut"):
-                    rb = n[: -len(".conv_shortcut")]
-                    if rb + ".conv2" in layers:
-                        add(rb + ".conv2sc.w", Part(n, col_off=layers[rb + ".conv2"][1]))
-    return Plan(list(targets.values()), layers, ffproj_b)
+    def keys(self):
+        ks = set(self.ffproj_b)
+        for t in self.targets:
+            ks |= {t.key} | ({t.colsum, t.lnb[0]} if t.norm else set())
+        return ks
 
 
 # --------------------------------------------------------------------------------------------------------------------------------
 # masters and the merge
 # --------------------------------------------------------------------------------------------------------------------------------
-def logical(spec_kind: str, a: np.ndarray) -> torch.Tensor:
-    """Keras layout -> fp32 [N][K] in pack order."""
-    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-    if spec_kind == "conv_w":
-        return t.permute(3, 0, 1, 2).reshape(t.shape[3], -1)
-    return t.t()
-
-
 class MergeBase:
-    """The fp32 masters of one packed model and its merge plan (built by HipModel.set_weights when lora_switch is on)."""
+    """The fp32 masters of one packed model (packing.Masters, kept by the packing pass for lora.targetable's layers) and its
+    merge plan, read from the layout table the image was packed by (built by HipModel.set_weights when lora_switch is on)."""
 
-    def __init__(self, model, named, W, ffproj_top: Dict[str, np.ndarray]):
-        d = model.device
-        self.device = d
-        self.plan = build_plan(model._specs, W)
-        kinds = {s.name: s.kind for s in model._specs if s.kind in ("conv_w", "dense_w")}
-        self.master: Dict[str, torch.Tensor] = {}
-        for n in self.plan.layers:
-            self.master[n] = logical(kinds[n], named[(n, kinds[n])]).contiguous().to(d)
-        self.top = {att: torch.from_numpy(np.ascontiguousarray(v.T, dtype=np.float32)).to(d) for att, v in ffproj_top.items()}
-        self.vec = {k: W[k].clone() for t in self.plan.targets for k in (t.colsum, t.lnb[0] if t.lnb else None) if k}
-        self.vec.update({k: W[k].clone() for k in self.plan.ffproj_b})
+    def __init__(self, device, specs, table: List[Packed], masters):
+        self.device = device
+        self.plan = Plan(specs, table)
+        self.master, self.top, self.vec = masters
         self.rowmaps: Dict[int, torch.Tensor] = {}
         self.active: set = set()   # layers whose factors are merged now
         self.version = 0
@@ -287,8 +171,6 @@ class MergeBase:
     def _rowmap(self, n_rows: int) -> torch.Tensor:
         m = self.rowmaps.get(n_rows)
         if m is None:
-            from .packing import geglu_row_order
-
             order = geglu_row_order(n_rows // 2)
             m = self.rowmaps[n_rows] = torch.from_numpy(np.argsort(order).astype(np.int32)).to(self.device)
         return m
@@ -315,10 +197,9 @@ class MergeBase:
                 layout, out_rows, out_cols, dt = ops.LORA_LAYOUT_ROWS, dst.shape[0], dst.shape[1], ops.OUT_BF16
             colsum = W[t.colsum] if (t.colsum and touched) else None
             for p in t.parts:
-                if p.ffproj_top:
-                    att = p.layer[: -len(".transformer_blocks.0.ff.net.2")]
-                    master = self.top[att]
-                    U, D = self._ffproj_factors(p.layer, att + ".proj_out", fac)
+                if p.ffproj_top:   # (the part after it is proj_out's)
+                    master = self.top[p.layer]
+                    U, D = self._ffproj_factors(p.layer, t.parts[1].layer, fac)
                 else:
                     master = self.master[p.layer]
                     U, D = fac.get(p.layer, (None, None))
@@ -378,7 +259,7 @@ class MergeBase:
             ds.append(Dp @ A2)
         return torch.cat(us, 1).contiguous(), torch.cat(ds, 0).contiguous()
 
-    def _lnb(self, t: Target, fac, W) -> torch.Tensor:
+    def _lnb(self, t: Packed, fac, W) -> torch.Tensor:
         """lnb' = lnb + rowscale * U (D beta), placed at the parts' destination rows (float64)."""
         out = self.vec[t.lnb[0]].double().clone()
         beta = W[t.lnb[1]].double()

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, engine, ops, packing
+from . import _lib, engine, layout, ops, packing
 from . import weights as wtab
 
 
@@ -46,23 +46,6 @@ def default_device() -> torch.device:
     if not torch.cuda.is_available():
         raise _lib.HipExtensionError("no HIP device visible: the MI355X path has no CPU fallback")
     return torch.device("cuda", torch.cuda.current_device())
-
-
-# names whose convs / denses run on the fp32 vector-FMA path (channel counts below an MFMA tile)
-_DIRECT = {
-    "conv_in", "conv_out", "time_embedding.linear_1", "time_embedding.linear_2",
-    "post_quant_conv", "decoder.conv_in", "decoder.conv_out", "encoder.conv_in", "quant_conv",
-} | {f"input_hint_block.{i}" for i in range(7)}
-
-
-UNET_HEADS = 8   # CrossAttention(num_heads=8) everywhere in the UNet / ControlNet (diffusion_model.py:60-65)
-
-
-def _q_prescale(c_out: int) -> np.float32:
-    """Factor folded into the UNet's query projections (attn1.to_q, attn2.to_q) at pack time: the attention scale
-    head_size**-0.5 (diffusion_model.py:105,123) times log2(e), so the attention kernel takes exp2 of q k^T directly
-    (MsdAttention.q_prescaled).  Exact up to the bf16 rounding of the weights, which happens once either way."""
-    return np.float32((c_out // UNET_HEADS) ** -0.5 * 1.4426950408889634)
 
 
 class HipModel:
@@ -109,19 +92,17 @@ class HipModel:
             if tuple(a.shape) != tuple(s.shape):
                 raise ValueError(f"{self.name}: {s.name} has shape {a.shape}, expected {s.shape}")
             named[(s.name, s.kind)] = a
+        # the packed image is what the layout table says (layout.py); W records which matrices are stored chunk-major, and the
+        # emitters pass that per-key layout to the op (Emitter.conv)
+        table = layout.layout(self._specs, layout.Flags(engine.W_CHUNK_MAJOR, engine.MFMA_TEMB_PROJ))
         self._lora = None
-        self._ffproj_stash = {} if getattr(self, "lora_switch", False) else None
-        W = packing.PackedWeights(self._pack(named))
-        if engine.W_CHUNK_MAJOR:
-            # the bf16 matrices the MFMA kernels read (msd_conv_gemm, msd_cross_attention_q: keys *.w / *.lnw) are stored
-            # chunk-major; W records which ones, and the emitters pass that per-key layout to the op (Emitter.conv)
-            for k in [k for k, t in W.items() if t.dtype == torch.bfloat16 and t.dim() == 2 and k.endswith((".w", ".lnw"))]:
-                W.to_chunk_major(k)
-        if self._ffproj_stash is not None:   # (lora_switch)
+        if getattr(self, "lora_switch", False):   # also keep the fp32 masters the merge starts from
             from . import lora
 
-            self._lora = lora.MergeBase(self, named, W, self._ffproj_stash)
-        self._ffproj_stash = None
+            W, masters = packing.pack(table, named, self.device, keep=lora.targetable(self._specs))
+            self._lora = lora.MergeBase(self.device, self._specs, table, masters)
+        else:
+            W, _ = packing.pack(table, named, self.device)
         self._W = W
         self.weights_version += 1
         self._plans.clear()
@@ -188,118 +169,6 @@ class HipModel:
         """Reference constructors load a local checkpoint if given one; no network download here."""
         if ckpt_path is not None and os.path.exists(ckpt_path):
             wtab.load_weights_from_file(self, ckpt_path, self.kind, lora_dict=lora_dict, specs=self._specs)
-
-    # ---- packing
-    def _pack(self, named) -> Dict[str, torch.Tensor]:
-        d = self.device
-        W: Dict[str, torch.Tensor] = {}
-        get = lambda n, k: named.get((n, k))  # noqa: E731
-        names = []
-        for s in self._specs:
-            if s.name not in names:
-                names.append(s.name)
-        tproj_w, tproj_b = [], []
-        for n in names:
-            cw, dw = get(n, "conv_w"), get(n, "dense_w")
-            b, g, beta = get(n, "bias"), get(n, "gamma"), get(n, "beta")
-            if g is not None:
-                W[n + ".g"], W[n + ".b"] = packing.dev_f32(g, d), packing.dev_f32(beta, d)
-                continue
-            if n.endswith(".time_emb_proj"):
-                tproj_w.append(dw)
-                tproj_b.append(b)
-                continue
-            if n in _DIRECT:
-                w = cw if cw is not None else dw.reshape(1, 1, *dw.shape)
-                W[n + ".w"] = packing.dev_f32(w, d)
-                W[n + ".b"] = packing.dev_f32(b, d)
-                if n == "conv_out" and cw is not None and cw.shape[2] % 64 == 0:
-                    # 320 -> 4: K = 2880 fills MFMA tiles even though N does not; 48 -> ~15 us per step (engine.MFMA_CONV_OUT)
-                    W[n + ".m.w"], W[n + ".m.b"] = packing.pack_conv(cw, d), W[n + ".b"]
-                continue
-            if n.endswith(".ff.net.0.proj"):
-                W[n + ".w"], W[n + ".b"] = packing.pack_geglu(dw, b, d)
-                continue
-            if n.endswith((".attn1.to_q", ".attn1.to_k", ".attn1.to_v", ".attn2.to_k", ".attn2.to_v",
-                           ".query", ".key", ".value", ".self_attn.q_proj", ".self_attn.k_proj", ".self_attn.v_proj")):
-                continue  # stacked below
-            if cw is not None:
-                W[n + ".w"] = packing.pack_conv(cw, d)
-            else:
-                W[n + ".w"] = packing.pack_dense(dw, d)
-            if b is not None:
-                W[n + ".b"] = packing.dev_f32(b, d)
-        for n in names:
-            if n.endswith(".attn1.to_q"):
-                base = n[: -len(".to_q")]
-                wq = get(base + ".to_q", "dense_w")
-                W[base + ".qkv.w"] = packing.pack_dense_stack(
-                    [wq * _q_prescale(wq.shape[1]), get(base + ".to_k", "dense_w"), get(base + ".to_v", "dense_w")], d)
-            elif n.endswith(".attn2.to_q"):   # (the generic branch above packed it unscaled)
-                wq = get(n, "dense_w")
-                W[n + ".w"] = packing.pack_dense(wq * _q_prescale(wq.shape[1]), d)
-            elif n.endswith(".attn2.to_k"):
-                base = n[: -len(".to_k")]
-                W[base + ".kv.w"] = packing.pack_dense_stack([get(base + ".to_k", "dense_w"), get(base + ".to_v", "dense_w")], d)
-            elif n.endswith(".query") or n.endswith(".self_attn.q_proj"):
-                trio = ("query", "key", "value") if n.endswith(".query") else ("q_proj", "k_proj", "v_proj")
-                base = n[: -len("." + trio[0])]
-                W[base + ".qkv.w"] = packing.pack_dense_stack([get(base + "." + k, "dense_w") for k in trio], d)
-                W[base + ".qkv.b"] = packing.dev_f32(np.concatenate([get(base + "." + k, "bias") for k in trio]), d)
-        # LayerNorm folds of the transformer blocks (engine.Emitter.attentions): norm1 -> q|k|v, norm2 -> attn2.to_q,
-        # norm3 -> GEGLU projection.  Keys: <consumer>.lnw (bf16 gamma-folded), .lncs (column sums), .lnb (W beta + b)
-        for n in names:
-            if not n.endswith(".transformer_blocks.0.norm1"):
-                continue
-            tb = n[: -len(".norm1")]
-            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).t().contiguous()  # noqa: E731  (in,out) -> [out][in]
-            cq = _q_prescale(get(tb + ".attn1.to_q", "dense_w").shape[1])
-            qkv = torch.cat([t(get(tb + ".attn1." + k, "dense_w")) * (cq if k == "to_q" else 1.0) for k in ("to_q", "to_k", "to_v")],
-                            dim=0)
-            W[tb + ".attn1.qkv.lnw"], W[tb + ".attn1.qkv.lncs"], W[tb + ".attn1.qkv.lnb"] = packing.fold_layer_norm(
-                qkv, None, get(tb + ".norm1", "gamma"), get(tb + ".norm1", "beta"), d)
-            W[tb + ".attn2.to_q.lnw"], W[tb + ".attn2.to_q.lncs"], W[tb + ".attn2.to_q.lnb"] = packing.fold_layer_norm(
-                t(get(tb + ".attn2.to_q", "dense_w")) * cq, None, get(tb + ".norm2", "gamma"), get(tb + ".norm2", "beta"), d)
-            gw, gb = get(tb + ".ff.net.0.proj", "dense_w"), get(tb + ".ff.net.0.proj", "bias")
-            order = packing.geglu_row_order(gw.shape[1] // 2)
-            W[tb + ".ff.net.0.proj.lnw"], W[tb + ".ff.net.0.proj.lncs"], W[tb + ".ff.net.0.proj.lnb"] = packing.fold_layer_norm(
-                t(gw)[torch.from_numpy(order)], np.asarray(gb)[order], get(tb + ".norm3", "gamma"), get(tb + ".norm3", "beta"), d)
-        # ff.net.2 followed by proj_out (diffusion_model.py:146-147 and :66-67: two Dense layers with only the
-        # residual add of t2 between them) as ONE GEMM over the channel concat [ff | t2]:
-        #   proj_out(ff W2 + b2 + t2) = ff (W2 Wp) + t2 Wp + (b2 Wp + bp)        key <attentions>.ffproj
-        for n in names:
-            if not n.endswith(".transformer_blocks.0.ff.net.2"):
-                continue
-            att = n[: -len(".transformer_blocks.0.ff.net.2")]
-            w2, b2 = get(n, "dense_w"), get(n, "bias")
-            wp, bp = get(att + ".proj_out", "conv_w"), get(att + ".proj_out", "bias")
-            if w2 is None or wp is None:
-                continue
-            w2d, wpd = np.asarray(w2, np.float64), np.asarray(wp, np.float64).reshape(wp.shape[-2], wp.shape[-1])
-            wcat = np.concatenate([w2d @ wpd, wpd], axis=0)                       # (4C + C, C) as (in, out)
-            if getattr(self, "_ffproj_stash", None) is not None:   # the LoRA merge's master of the top block (lora.MergeBase)
-                self._ffproj_stash[att] = wcat[: w2d.shape[0]]
-            W[att + ".ffproj.w"] = packing.pack_dense(wcat.astype(np.float32), d)
-            W[att + ".ffproj.b"] = packing.dev_f32((np.asarray(b2, np.float64) @ wpd + np.asarray(bp, np.float64)).astype(np.float32), d)
-        # ResBlock conv2 + conv_shortcut (diffusion_model.py:34-38,50) as one contraction: W = [conv2 taps | shortcut], b = b2 + bs
-        for n in names:
-            if not n.endswith(".conv_shortcut"):
-                continue
-            rb = n[: -len(".conv_shortcut")]
-            w2, b2 = get(rb + ".conv2", "conv_w"), get(rb + ".conv2", "bias")
-            ws, bs = get(n, "conv_w"), get(n, "bias")
-            if w2 is None or ws is None or w2.shape[0] != 3 or ws.shape[0] != 1 or ws.shape[2] % 64:
-                continue
-            t2 = torch.from_numpy(np.ascontiguousarray(w2)).permute(3, 0, 1, 2).reshape(w2.shape[3], -1)      # [N][9 C_out]
-            tsc = torch.from_numpy(np.ascontiguousarray(ws)).permute(3, 0, 1, 2).reshape(ws.shape[3], -1)     # [N][C_in]
-            W[rb + ".conv2sc.w"] = torch.cat([t2, tsc], dim=1).to(torch.bfloat16).contiguous().to(d)
-            W[rb + ".conv2sc.b"] = packing.dev_f32(np.asarray(b2, np.float32) + np.asarray(bs, np.float32), d)
-        if tproj_w:
-            cat = np.concatenate(tproj_w, axis=1)   # (1280, sum of the ResBlocks' C_out)
-            W["time_emb_proj_cat.w"] = (packing.pack_dense(cat, d) if engine.MFMA_TEMB_PROJ
-                                        else packing.dev_f32(cat.reshape(1, 1, 1280, -1), d))
-            W["time_emb_proj_cat.b"] = packing.dev_f32(np.concatenate(tproj_b), d)
-        return W
 
     def _require_weights(self):
         if self._W is None:
@@ -577,16 +446,6 @@ class ImageEncoder(HipModel):
         super().__init__(name or "image_encoder", device)
         self._maybe_load(ckpt_path)
 
-    def _pack(self, named):
-        W = super()._pack(named)
-        # quant_conv (1x1, 8 -> 8) followed by "take the first 4 channels, times 0.18215" is one
-        # 8 -> 4 conv with pre-scaled weights (exact: both steps are linear)
-        w = np.asarray(named[("quant_conv", "conv_w")], dtype=np.float32)[:, :, :, :4] * np.float32(0.18215)
-        b = np.asarray(named[("quant_conv", "bias")], dtype=np.float32)[:4] * np.float32(0.18215)
-        W["quant_conv.mean.w"] = packing.dev_f32(w, self.device)
-        W["quant_conv.mean.b"] = packing.dev_f32(b, self.device)
-        return W
-
     def _build(self, B, H, Wd) -> _BoundPlan:
         plan = engine.Plan(self.device)
         e = engine.Emitter(plan, self._W)
@@ -624,9 +483,6 @@ class TextClipEmbedding(HipModel):
             raise ValueError("only the SD1.5 CLIP ViT-L/14 text model geometry is built (77, 768, 49408)")
         super().__init__(name or "text_clip_embedding", device)
         self._maybe_load(ckpt_path)
-
-    def _pack(self, named):
-        return {s.name: packing.dev_f32(named[(s.name, s.kind)], self.device) for s in self._specs}
 
     def emit(self, plan: engine.Plan, tokens, positions, out: engine.Act, status) -> None:
         plan.rec(ops.embedding_sum, tokens=tokens, positions=positions,

@@ -1,6 +1,8 @@
 """Weight pre-packing: Keras-layout fp32 weights -> the layouts the gfx950 kernels consume.
 
-Done once at ``set_weights`` time on the host (layout only, no arithmetic beyond the bf16 round):
+Done once at ``set_weights`` time on the host.  WHAT is packed is the layout table's business (``layout.layout``: one entry per
+packed key); this module executes it (:func:`pack`): every matrix starts as :func:`logical` of its layer(s), the table's scales,
+row maps and offsets are applied in fp32, then the bf16 round.  The forms:
 
 * MFMA path (``msd_conv_gemm``): ``W[N][K]`` bf16, K contiguous, ``k = (ky*ks + kx)*C_in + c`` —
   i.e. HWIO ``(kh,kw,cin,cout)`` -> ``(cout,kh,kw,cin)``; Dense ``(in,out)`` -> ``(out,in)``.
@@ -12,8 +14,12 @@ Done once at ``set_weights`` time on the host (layout only, no arithmetic beyond
 """
 from __future__ import annotations
 
+from typing import Dict, List, NamedTuple, Optional, Tuple
+
 import numpy as np
 import torch
+
+from .layout import KERAS, VEC, Packed
 
 
 def _dev_bf16(t: torch.Tensor, device) -> torch.Tensor:
@@ -80,21 +86,24 @@ def chunk_major(w_nk: torch.Tensor) -> torch.Tensor:
     return w_nk.view(n, k // 64, 64).permute(1, 0, 2).contiguous()
 
 
-def pack_conv(w_hwio: np.ndarray, device) -> torch.Tensor:
-    """(kh,kw,cin,cout) fp32 -> [cout][kh*kw*cin] bf16 on device."""
-    t = torch.from_numpy(np.ascontiguousarray(w_hwio))
-    kh, kw, cin, cout = t.shape
-    return _dev_bf16(t.permute(3, 0, 1, 2).reshape(cout, kh * kw * cin), device)
+def logical(w: np.ndarray) -> torch.Tensor:
+    """Keras layout -> fp32 logical [N][K] in pack order (a view where it can be): a conv (kh,kw,cin,cout) ->
+    [cout][(ky*kw + kx)*cin + c], a Dense (in,out) -> [out][in].  Every packed matrix and every LoRA master starts here."""
+    t = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
+    return t.permute(3, 0, 1, 2).reshape(t.shape[3], -1) if t.dim() == 4 else t.t()
 
 
-def pack_dense(w_io: np.ndarray, device) -> torch.Tensor:
-    """(in,out) fp32 -> [out][in] bf16 on device."""
-    return _dev_bf16(torch.from_numpy(np.ascontiguousarray(w_io)).t(), device)
+def pack_matrix(w: np.ndarray, device) -> torch.Tensor:
+    """(kh,kw,cin,cout) or (in,out) fp32 -> bf16 [N][K] on device."""
+    return _dev_bf16(logical(w), device)
+
+
+pack_conv = pack_dense = pack_matrix
 
 
 def pack_dense_stack(ws, device) -> torch.Tensor:
     """Stack several (in,out_i) matrices along the output axis -> [sum out_i][in] bf16."""
-    return _dev_bf16(torch.cat([torch.from_numpy(np.ascontiguousarray(w)).t() for w in ws], dim=0), device)
+    return _dev_bf16(torch.cat([logical(w) for w in ws], dim=0), device)
 
 
 def geglu_row_order(n_half: int) -> np.ndarray:
@@ -111,8 +120,7 @@ def geglu_row_order(n_half: int) -> np.ndarray:
 def pack_geglu(w_io: np.ndarray, b: np.ndarray, device):
     n_half = w_io.shape[1] // 2
     order = geglu_row_order(n_half)
-    wt = torch.from_numpy(np.ascontiguousarray(w_io)).t()[torch.from_numpy(order)]
-    return _dev_bf16(wt, device), dev_f32(np.asarray(b)[order], device)
+    return _dev_bf16(logical(w_io)[torch.from_numpy(order)], device), dev_f32(np.asarray(b)[order], device)
 
 
 def fold_layer_norm(w_oi: torch.Tensor, bias, gamma: np.ndarray, beta: np.ndarray, device):
@@ -133,6 +141,106 @@ def fold_layer_norm(w_oi: torch.Tensor, bias, gamma: np.ndarray, beta: np.ndarra
 
 def dev_f32(a: np.ndarray, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+
+
+# ---- the host executor of the layout table --------------------------------------------------------------------------------
+class Masters(NamedTuple):
+    """What the LoRA merge starts from (lora.MergeBase), kept by pack() for the layers it is asked to: fp32, on the device."""
+    layer: Dict[str, torch.Tensor]   # layer -> logical [N][K]
+    top: Dict[str, torch.Tensor]     # ff.net.2 layer -> the ffproj top block (fp32 of the float64 W2 Wp), [C][4C]
+    vec: Dict[str, torch.Tensor]     # .lncs / .lnb / ffproj.b key -> a copy of the vector as loaded
+
+
+def _weight(named, layer) -> np.ndarray:
+    w = named.get((layer, "conv_w"))
+    return w if w is not None else named[(layer, "dense_w")]
+
+
+def _as_1x1(w: np.ndarray) -> np.ndarray:
+    return np.asarray(w, np.float64).reshape(w.shape[-2], w.shape[-1])
+
+
+def _matrix(e: Packed, named) -> torch.Tensor:
+    """The fp32 logical [N][K] of a ROWS entry, before the column scale and the rounding."""
+    blocks = []
+    for i, p in enumerate(e.parts):
+        if p.ffproj_top:   # (in, out) product in float64, then fp32, as one Dense
+            m = logical((np.asarray(_weight(named, p.layer), np.float64) @ _as_1x1(_weight(named, e.parts[i + 1].layer)))
+                        .astype(np.float32))
+        else:
+            m = logical(_weight(named, p.layer))
+        if p.qscale is not None:
+            m = m * float(p.qscale)
+        if p.rowmap:
+            m = m[torch.from_numpy(geglu_row_order(m.shape[0] // 2))]
+        blocks.append(m)
+    return blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1 if e.parts[1].col_off else 0)
+
+
+def _keras(e: Packed, named) -> np.ndarray:
+    blocks = []
+    for p in e.parts:
+        w = _weight(named, p.layer)
+        w = w.reshape(1, 1, *w.shape) if w.ndim == 2 else w
+        if p.rows:
+            w = np.asarray(w, dtype=np.float32)[..., :p.rows]
+        blocks.append(w if p.qscale is None else w * p.qscale)
+    return blocks[0] if len(blocks) == 1 else np.concatenate(blocks, axis=-1)
+
+
+def _vector(e: Packed, named) -> Optional[np.ndarray]:
+    kind = e.how if e.how in ("gamma", "beta", "embedding") else "bias"
+    blocks = []
+    for p in e.parts:
+        v = np.asarray(named[(p.layer, kind)])
+        if p.rowmap:
+            v = v[geglu_row_order(len(v) // 2)]
+        if p.rows:
+            v = np.asarray(v, dtype=np.float32)[:p.rows]
+        blocks.append(v if p.qscale is None else v * p.qscale)
+    if e.how == "bias_sum":
+        return np.asarray(blocks[0], np.float32) + np.asarray(blocks[1], np.float32)
+    if e.how == "ffproj_b":
+        wp = _as_1x1(_weight(named, e.parts[1].layer))
+        return (np.asarray(blocks[0], np.float64) @ wp + np.asarray(blocks[1], np.float64)).astype(np.float32)
+    return None if not blocks else blocks[0] if len(blocks) == 1 else np.concatenate(blocks)
+
+
+def pack(layout: List[Packed], named, device, keep=None) -> Tuple[PackedWeights, Optional[Masters]]:
+    """Execute the layout table (layout.layout) on the Keras-layout arrays `named[(layer, kind)]`: the packed image on `device`.
+    `keep`: the layers whose masters are kept too (lora_switch), else None.  One layer's fp32 matrix and the entry being
+    assembled are alive at a time; a chunk-major matrix is re-laid out as soon as it is made."""
+    W = PackedWeights()
+    by_key = {e.key: e for e in layout}
+    masters = None if keep is None else Masters({}, {}, {})
+    kept = lambda e: masters is not None and not e.sources.isdisjoint(keep)  # noqa: E731
+    for e in layout:
+        if e.how in ("lncs", "lnb"):
+            continue   # made below with the .lnw they belong to
+        if e.store == VEC:
+            W[e.key] = dev_f32(_vector(e, named), device)
+            if e.how == "ffproj_b" and kept(e):
+                masters.vec[e.key] = W[e.key].clone()
+            continue
+        if e.store == KERAS:
+            W[e.key] = dev_f32(_keras(e, named), device)
+            continue
+        m = _matrix(e, named)
+        if e.parts[0].ffproj_top and kept(e):
+            masters.top[e.parts[0].layer] = m[:, : e.parts[1].col_off].contiguous().to(device)
+        if e.norm is None:
+            W[e.key] = _dev_bf16(m, device)
+        else:
+            lncs, lnb = e.colsum, e.lnb[0]
+            W[e.key], W[lncs], W[lnb] = fold_layer_norm(m.contiguous(), _vector(by_key[lnb], named), named[(e.norm, "gamma")],
+                                                        named[(e.norm, "beta")], device)
+            if kept(e):
+                masters.vec[lncs], masters.vec[lnb] = W[lncs].clone(), W[lnb].clone()
+        if e.chunk_major:
+            W.to_chunk_major(e.key)
+    for n in keep or ():
+        masters.layer[n] = logical(_weight(named, n)).contiguous().to(device)
+    return W, masters
 
 
 # ---- packed weights on disk (one rank packs, the others map) ----------------------------------------------------------------

@@ -1,5 +1,5 @@
 """LoRA switch at run time (minsdtf_amd/lora.py, csrc/lora.hip) without a GPU: the factors against the load-time dense deltas, the
-merge plan against what HipModel._pack actually changes, the ffproj / lnb correction algebra, and the C ABI of msd_lora_merge."""
+merge plan against what packing.pack actually changes, the ffproj / lnb correction algebra, and the C ABI of msd_lora_merge."""
 import ctypes
 import os
 import subprocess
@@ -65,18 +65,14 @@ def test_factors_from_state_dict_and_missing_file(tmp_path):
 
 
 def _packed_cpu(model_cls, arrays):
-    """HipModel._pack on the host (device = cpu): the packed image without a GPU."""
-    from minsdtf_amd import packing
+    """packing.pack on the host (device = cpu): the packed image without a GPU, and the layout table it was packed by."""
+    from minsdtf_amd import layout, packing
     from minsdtf_amd import weights as Wt
 
-    m = model_cls.__new__(model_cls)
-    m.device = torch.device("cpu")
-    m._specs = Wt.table(model_cls.kind, **({"clip_skip": -1} if model_cls.kind == "text_encoder" else {}))
-    if model_cls.kind == "text_encoder":
-        m.clip_skip = -1
-    named = {(s.name, s.kind): a for s, a in zip(m._specs, arrays)}
-    m._ffproj_stash = None
-    return m, packing.PackedWeights(m._pack(named))
+    specs = Wt.table(model_cls.kind, **({"clip_skip": -1} if model_cls.kind == "text_encoder" else {}))
+    table = layout.layout(specs)
+    named = {(s.name, s.kind): a for s, a in zip(specs, arrays)}
+    return specs, table, packing.pack(table, named, torch.device("cpu"))[0]
 
 
 def _plan_vs_pack(model_cls, seed):
@@ -85,14 +81,14 @@ def _plan_vs_pack(model_cls, seed):
 
     kw = {"clip_skip": -1} if model_cls.kind == "text_encoder" else {}
     base = Wt.synth_keras_weights(model_cls.kind, seed=seed, bias_scale=0.05, **kw)
-    m, W0 = _packed_cpu(model_cls, base)
-    layers = lora.targetable(m._specs)
+    specs, table, W0 = _packed_cpu(model_cls, base)
+    layers = lora.targetable(specs)
     rng = np.random.default_rng(seed)
     bumped = [a + (rng.standard_normal(a.shape).astype(np.float32) * 0.05 if s.name in layers and s.kind.endswith("_w") else 0)
-              for s, a in zip(m._specs, base)]
-    _, W1 = _packed_cpu(model_cls, bumped)
+              for s, a in zip(specs, base)]
+    _, _, W1 = _packed_cpu(model_cls, bumped)
     changed = {k for k in W0 if not torch.equal(W0[k], W1[k])}
-    plan = lora.build_plan(m._specs, W0)
+    plan = lora.Plan(specs, table)
     return changed, plan, layers
 
 

@@ -1024,7 +1024,7 @@ def test_cross_attention_q(gpu, case, layout, nw):
     if case.get("spike"):
         k[:, T // 2] *= 8.0
         k = bf(k)
-    c2 = (d ** -0.5) * 1.4426950408889634                 # folded into the projection, as models._q_prescale does
+    c2 = (d ** -0.5) * 1.4426950408889634                 # folded into the projection, as layout.q_prescale does
     ln = F.layer_norm(x, (C,), gamma, beta, eps=1e-5)
     q = bf(ln @ (wq * c2))
     qh = q.view(B, S, H, d).permute(0, 2, 1, 3)
