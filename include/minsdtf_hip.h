@@ -580,6 +580,32 @@ typedef struct MsdRegionCombine {
 
 MSD_API int msd_region_combine(const MsdRegionCombine* p, msd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * msd_attention_identity — self-attention with the IDENTITY attention map: the perturbed forward of perturbed-attention
+ * guidance (PAG, Ahn et al. 2024; minsdtf_amd/pag.py).  Where msd_attention computes softmax(q k^T) v, the
+ * perturbed layer's output is v itself; the step plan holds v only transposed, as msd_attention's `vt` operand, so this is
+ * the transpose back, recorded for the perturbed batch rows in place of (or next to) the msd_attention launch, with the same
+ * operands.  An addition to ABI 12: nothing else changed.
+ *
+ *   vt:  bf16 [batch][channels][vt_ld], key index contiguous (all heads: channels = heads * head_dim); vt_ld % 8 == 0,
+ *        vt_ld >= s; columns >= s are padding, whatever they hold (NaN included) does not reach out
+ *   out: bf16 [batch][s][o_ld]; out[b][k][c] = vt[b][c][k] for k < s, c < channels, bit for bit; columns >= channels of a
+ *        row (o_ld > channels) are not written
+ *
+ * A tiled transpose through LDS, 16-byte global loads along vt_ld and 16-byte global stores along channels; one workgroup
+ * per 64 x 64 tile per sample.  Checked on the host, without a device: vt / out non-NULL and 16-byte aligned; batch in
+ * 1 .. 65535; s >= 1; channels a positive multiple of 8; vt_ld % 8 == 0 and vt_ld >= s; o_ld >= channels and o_ld % 8 == 0
+ * (every row of out 16-byte aligned); fewer than 2^31 elements in vt and in out; the bytes of out apart from the bytes of vt.
+ * Argument errors return MSD_E_ARG without launching.  Nothing is allocated; the launch is stream-ordered and capturable. */
+typedef struct MsdAttentionIdentity {
+    const void* vt;
+    void* out;
+    int32_t batch, channels, s;
+    int32_t vt_ld, o_ld;
+} MsdAttentionIdentity;
+
+MSD_API int msd_attention_identity(const MsdAttentionIdentity* p, msd_stream_t stream);
+
 /* msd_add_bf16 — out = a + b elementwise on bf16. n % 8 == 0. */
 MSD_API int msd_add_bf16(const void* a, const void* b, void* out, int64_t n, msd_stream_t stream);
 /* msd_add_f32_bf16 — out = bf16(a + b), a / out bf16, b fp32, summed in fp32 (may run in place, out == a).  The ControlNet

@@ -149,7 +149,15 @@ class MsdRegionCombine(C.Structure):
     ]
 
 
-LORA_ROWS_PER_BLOCK = 8   # csrc/lora.hip LR_ROWS: MsdLoraJob.first_block counts workgroups of this many rows
+class MsdAttentionIdentity(C.Structure):
+    _fields_ = [
+        ("vt", C.c_void_p), ("out", C.c_void_p),
+        ("batch", C.c_int32), ("channels", C.c_int32), ("s", C.c_int32),
+        ("vt_ld", C.c_int32), ("o_ld", C.c_int32),   # perturbed-attention guidance (an addition to ABI 12)
+    ]
+
+
+LORA_ROWS_PER_BLOCK = 8  # csrc/lora.hip LR_ROWS: MsdLoraJob.first_block counts workgroups of this many rows
 
 # every symbol include/minsdtf_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -177,6 +185,7 @@ SYMBOLS = {
     "msd_latent_resample": (C.c_int, [C.POINTER(MsdLatentResample), C.c_void_p]),
     "msd_tile_consensus": (C.c_int, [C.POINTER(MsdTileConsensus), C.c_void_p]),
     "msd_region_combine": (C.c_int, [C.POINTER(MsdRegionCombine), C.c_void_p]),
+    "msd_attention_identity": (C.c_int, [C.POINTER(MsdAttentionIdentity), C.c_void_p]),
     "msd_add_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_add_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

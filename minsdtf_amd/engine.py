@@ -527,13 +527,18 @@ class Emitter:
                 p.free(a)
         return out
 
-    def attentions(self, x: Act, name, ctx_kv, ctx_len, heads=8, free_input=False, shared: int = 1) -> Act:
+    def attentions(self, x: Act, name, ctx_kv, ctx_len, heads=8, free_input=False, shared: int = 1, perturbed: int = 0) -> Act:
         """Attentions / TransformerBlock / CrossAttention / GEGLU (diffusion_model.py:54-153).  shared > 1 (SHARE_CFG_PREFIX): `x` holds
         `shared` identical copies of x.B / shared samples (the cond and uncond halves in front of the first cross-attention): norm,
         proj_in, q|k|v, the self-attention and its to_out run on ONE copy, their result (rows + LayerNorm partials) is replicated, and the
-        block continues on the whole batch from attn2 on, where the halves' text contexts differ."""
+        block continues on the whole batch from attn2 on, where the halves' text contexts differ.
+        perturbed (perturbed-attention guidance, minsdtf_amd/pag.py): the number of TRAILING batch rows whose attn1 uses the identity
+        attention map - their output is V itself (msd_attention_identity, the transpose of V^T), the rows in front of them take
+        msd_attention as always.  Not with shared > 1: the copies are no longer identical behind this attn1."""
         p = self.p
         x_all = x
+        if not 0 <= perturbed <= x.B or (perturbed and shared > 1):
+            raise ValueError(f"{name}: {perturbed} perturbed rows of {x.B} (shared = {shared})")
         if shared > 1:
             assert x.B % shared == 0
             x = Act(x.buf, x.B // shared, x.H, x.W, x.C)   # the first copy
@@ -557,8 +562,12 @@ class Emitter:
             self.conv(n1, tb + ".attn1.qkv", 3 * C, bias=False, split=(C, C, q.buf, k.buf, vt, sp))
             p.free(n1)
         a1 = p.act(B, H, Wd, C)
-        p.rec(ops.attention, q=q.buf, k=k.buf, vt=vt, out=a1.buf, batch=B, heads=heads, head_dim=d, s=S, t=S, q_ld=C,
-              k_ld=C, vt_ld=sp, o_ld=C, scale=d ** -0.5, q_prescaled=True, name=tb + ".attn1")
+        if perturbed < B:
+            p.rec(ops.attention, q=q.buf, k=k.buf, vt=vt, out=a1.buf, batch=B - perturbed, heads=heads, head_dim=d, s=S, t=S, q_ld=C,
+                  k_ld=C, vt_ld=sp, o_ld=C, scale=d ** -0.5, q_prescaled=True, name=tb + ".attn1")
+        if perturbed:   # the last `perturbed` rows: out = V
+            p.rec(ops.attention_identity, vt=vt.at((B - perturbed) * C * sp * 2), out=a1.buf.at((B - perturbed) * S * C * 2),
+                  batch=perturbed, channels=C, s=S, vt_ld=sp, o_ld=C, name=tb + ".attn1.identity")
         p.free(q, k, vt)
         if shared > 1:
             t1_wide = p.act(B * shared, H, Wd, C)
@@ -648,6 +657,10 @@ for _ui, _lvl in enumerate((3, 2, 1, 0)):
             UNET_ATTN_LAYERS.append((f"up_blocks.{_ui}.attentions.{_r}.transformer_blocks.0.attn2", wtab.UNET_CH[_lvl]))
 
 
+# the 16 attention blocks of the UNet, in forward order: what a PAG job may select (minsdtf_amd/pag.py)
+PAG_LAYERS: Tuple[str, ...] = tuple(n[:-len(".transformer_blocks.0.attn2")] for n, _c in UNET_ATTN_LAYERS)
+
+
 def resblock_names(encoder_only: bool) -> List[Tuple[str, int]]:
     """(name, c_out) of every ResBlock in weight-table order: column layout of the time-projection table."""
     out = []
@@ -695,9 +708,14 @@ def temb_columns(encoder_only: bool) -> Dict[str, int]:
     return cols
 
 
-def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1) -> Act:
+def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1,
+                  pag_layers=frozenset(), perturbed: int = 0) -> Act:
     """Down path + mid block shared by the UNet (diffusion_model.py:193-229) and the ControlNet.  shared > 1: `x` (conv_in's output) is
-    `shared` identical copies of x.B / shared samples - the first ResBlock and the front of the first transformer block run on one."""
+    `shared` identical copies of x.B / shared samples - the first ResBlock and the front of the first transformer block run on one.
+    pag_layers / perturbed: the attention blocks (by name) whose attn1 is the identity for the last `perturbed` rows."""
+    def pert(block):
+        return perturbed if block in pag_layers else 0
+
     for lvl, ch in enumerate(wtab.UNET_CH):
         for r in range(2):
             name = f"down_blocks.{lvl}.resnets.{r}"
@@ -709,20 +727,24 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
                 continue
             x = e.res_block(x, name, ch, temb=temb_of(name))
             if lvl < 3:
-                x = e.attentions(x, f"down_blocks.{lvl}.attentions.{r}", ctx_kv, ctx_len, free_input=True)
+                blk = f"down_blocks.{lvl}.attentions.{r}"
+                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=pert(blk))
             outputs.append(x)
         if lvl < 3:
             x = e.conv(x, f"down_blocks.{lvl}.downsamplers.0.conv", ch, ksize=3, stride=2)
             outputs.append(x)
     x = e.res_block(x, "mid_block.resnets.0", 1280, temb=temb_of("mid_block.resnets.0"))
-    x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True)
+    x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True, perturbed=pert("mid_block.attentions.0"))
     x = e.res_block(x, "mid_block.resnets.1", 1280, temb=temb_of("mid_block.resnets.1"), free_input=True)
     return x
 
 
 def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w: int, temb, ctx_kv, ctx_len: int,
-              eps_out_f32, controls=None, control_taps=None) -> None:
+              eps_out_f32, controls=None, control_taps=None, pag_layers=None, perturbed: int = 0) -> None:
     """DiffusionModel graph (diffusion_model.py:184-279).
+
+    pag_layers (a set of attention block names, PAG_LAYERS) / perturbed: the last `perturbed` of the NB rows run those blocks'
+    self-attention with the identity map (Emitter.attentions); perturbed = 0 records exactly the plain forward.
 
     latent_f32: fp32 [latent_batch_mod][h][w][4] (sample b reads row b % latent_batch_mod);
     temb = (table, step_stride, batch_stride, {resblock: column}); eps_out_f32: fp32 [NB][h][w][4].
@@ -747,7 +769,14 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
     outputs: List[Act] = [x]
     # (conv_in itself stays on the whole batch: every row reads latent row b % latent_batch_mod, a 10-us launch whose output is skip 0)
     shared = NB // latent_batch_mod if (SHARE_CFG_PREFIX and latent_batch_mod > 0 and NB % latent_batch_mod == 0) else 1
-    x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared)
+    pag_layers = frozenset(pag_layers or ()) if perturbed else frozenset()
+    if pag_layers - set(PAG_LAYERS):
+        raise ValueError(f"emit_unet: unknown attention block(s) {sorted(pag_layers - set(PAG_LAYERS))}")
+    if PAG_LAYERS[0] in pag_layers:
+        # the first block's front is no longer identical across the copies: nothing is shared (exact either way - a sample's bits
+        # do not depend on its batch)
+        shared = 1
+    x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared, pag_layers=pag_layers, perturbed=perturbed)
     p.mark("controls")   # everything above is independent of the ControlNet (its encoder may run beside it on another stream)
     if control_taps is not None:
         e_c, feats = control_taps
@@ -767,7 +796,8 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
             name = f"up_blocks.{ui}.resnets.{r}"
             x = e.res_block((x, skip), name, ch, temb=temb_of(name), free_input=True)
             if lvl < 3:
-                x = e.attentions(x, f"up_blocks.{ui}.attentions.{r}", ctx_kv, ctx_len, free_input=True)
+                blk = f"up_blocks.{ui}.attentions.{r}"
+                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=perturbed if blk in pag_layers else 0)
         if lvl > 0:
             y = e.conv(x, f"up_blocks.{ui}.upsamplers.0.conv", ch, ksize=3, upsample=True)
             p.free(x)

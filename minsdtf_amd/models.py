@@ -254,7 +254,8 @@ class DiffusionModel(HipModel):
         self.apply_control_net = apply_control_net
         self._maybe_load(ckpt_path, lora_dict)
 
-    def _build(self, B: int, T: int, with_controls: bool) -> _BoundPlan:
+    def _build(self, B: int, T: int, with_controls: bool, pag_layers=None) -> _BoundPlan:
+        """pag_layers: the attention blocks whose self-attention is the identity map for ALL B rows (predict_perturbed)."""
         h, w = self.h, self.w
         plan = engine.Plan(self.device)
         e = engine.Emitter(plan, self._W)
@@ -275,7 +276,8 @@ class DiffusionModel(HipModel):
                 cstage.append((st, (B, hh, ww, ch)))
                 controls.append(st)
         eps = plan.alloc(B * h * w * 4 * 4)
-        engine.emit_unet(e, ins["latent"], B, B, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls)
+        engine.emit_unet(e, ins["latent"], B, B, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls,
+                         pag_layers=pag_layers, perturbed=B if pag_layers else 0)
         plan.finalize()
         bp = _BoundPlan(plan, self._use_graph)
         bp.io = {k: b.tensor(torch.float32, s) for (k, b), s in
@@ -286,6 +288,21 @@ class DiffusionModel(HipModel):
         return bp
 
     def predict_on_batch(self, x):
+        return self._predict(x, None)
+
+    def predict_perturbed(self, x, layers):
+        """predict_on_batch([latent, t_emb, context]) with the self-attention map of the attention blocks `layers` (names of
+        engine.PAG_LAYERS) replaced by the identity: those layers' output is V (msd_attention_identity).  The perturbed forward of
+        perturbed-attention guidance (minsdtf_amd/pag.py); a bound plan of its own per layer set."""
+        layers = frozenset([layers] if isinstance(layers, str) else layers)
+        unknown = layers - set(engine.PAG_LAYERS)
+        if not layers or unknown:
+            raise ValueError(f"predict_perturbed: layers {sorted(layers)} (a non-empty subset of engine.PAG_LAYERS)")
+        if len(x) != 3:
+            raise ValueError("predict_perturbed takes [latent, t_emb, context] (no control tensors)")
+        return self._predict(x, layers)
+
+    def _predict(self, x, pag_layers):
         latent, t_emb, context = _np32(x[0]), _np32(x[1]), _np32(x[2])
         controls = [_np32(c) for c in x[3:]]
         if controls and len(controls) != 13:
@@ -293,7 +310,8 @@ class DiffusionModel(HipModel):
         B, T = latent.shape[0], context.shape[1]
         if latent.shape[1:] != (self.h, self.w, 4):
             raise ValueError(f"latent shape {latent.shape} does not match the model ({self.h},{self.w},4)")
-        bp = self._bound((B, T, bool(controls)), lambda: self._build(B, T, bool(controls)))
+        key = (B, T, bool(controls)) if pag_layers is None else (B, T, False, ("pag", tuple(sorted(pag_layers))))
+        bp = self._bound(key, lambda: self._build(B, T, bool(controls), pag_layers))
         bp.io["latent"].copy_(torch.from_numpy(latent))
         bp.io["t_emb"].copy_(torch.from_numpy(t_emb))
         bp.io["context"].copy_(torch.from_numpy(context))

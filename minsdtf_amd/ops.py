@@ -228,6 +228,16 @@ def region_combine(*, eps, w, out, regions, batch, n, name="region_combine") -> 
     return Call(lib.msd_region_combine, (C.byref(s),), name, keep=s)
 
 
+def attention_identity(*, vt, out, batch, channels, s, vt_ld, o_ld, name="attention_identity") -> Call:
+    """msd_attention_identity: out[b][k][c] = vt[b][c][k] - self-attention with the identity map (the perturbed rows of a PAG job).
+    vt bf16 [batch][channels][vt_ld] (msd_attention's operand), out bf16 [batch][s][o_ld]."""
+    lib = _lib.load()
+    a = _lib.MsdAttentionIdentity()
+    a.vt, a.out = _p(vt), _p(out)
+    a.batch, a.channels, a.s, a.vt_ld, a.o_ld = int(batch), int(channels), int(s), int(vt_ld), int(o_ld)
+    return Call(lib.msd_attention_identity, (C.byref(a),), name, keep=a)
+
+
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:
     lib = _lib.load()
     return Call(lib.msd_add_bf16, (_p(a), _p(b), _p(out), n), name)

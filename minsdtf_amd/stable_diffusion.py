@@ -34,6 +34,7 @@ import torch
 
 from . import _lib, engine, ops
 from . import hires as hires_mod
+from . import pag as pag_mod
 from . import regions as regions_mod
 from . import samplers as smp
 from . import tiled as tiled_mod
@@ -72,12 +73,13 @@ class DenoiseEngine:
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
-                 sampler=None, tiled=None, regions: int = 0):
+                 sampler=None, tiled=None, regions: int = 0, pag=None):
         unet._require_weights()
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
-        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions)
+        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag)
         self.use_graph = use_graph
+        self.guidance = float(guidance)
         self.cfg = cfg = guidance > 0.0
         # Two ways to run the cond and uncond halves of a step (no op couples samples, so both are the
         # reference's two predict_on_batch calls, :442-460):
@@ -90,7 +92,7 @@ class DenoiseEngine:
         self.dual = bool(cfg and streams == 2)
         fuse = cfg and (t_cond == t_uncond) and not self.dual
         # passes: list of (rows in eps, NB, context length); fused = uncond rows then cond rows
-        RC = self.regions or 1   # conditional copies of the batch
+        RC = self.regions or (2 if self.pag else 1)   # conditional copies of the batch (a PAG job: the c rows, then the p rows)
         if not cfg:
             passes = [(0, RC * B, t_cond, "cond")]
         elif fuse:
@@ -118,9 +120,9 @@ class DenoiseEngine:
         self._warmed = False
         _lib.track_graph_owner(self)
 
-    def _check_options(self, control_net, streams, inpaint, tcd, sampler, tiled, regions) -> None:
+    def _check_options(self, control_net, streams, inpaint, tcd, sampler, tiled, regions, pag=None) -> None:
         """The option combinations an engine refuses (generate_image refuses them earlier, by argument name: _REFUSED; these guard
-        direct construction).  Sets `sampler`, `tiled` and `regions`."""
+        direct construction).  Sets `sampler`, `tiled`, `regions` and `pag`."""
         # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
         # the 8-wide coefficient rows, the previous denoised estimate and (stochastic samplers) per-step draws on the device
         self.sampler = smp.parse(sampler)
@@ -143,6 +145,17 @@ class DenoiseEngine:
                 raise ValueError(f"regions: {R} region prompts (1 .. {regions_mod.MAX_REGIONS})")
             if control_net is not None or inpaint or tcd or tiled is not None or streams == 2:
                 raise ValueError("regions: text-to-image on one stream only (no ControlNet, inpainting, TCD, tiled, denoise_streams = 2)")
+        # pag (the set of attention blocks of a perturbed-attention-guidance job, or None): the conditional half is 2 * B rows, the
+        # c rows and behind them the p rows (the same context; the selected blocks' attn1 is the identity for them); one
+        # msd_region_combine launch in front of the guidance / sampler step writes c' = (1 + k) c - k p over the c rows with the two
+        # constant planes of `pag_w` (minsdtf_amd/pag.py)
+        self.pag = frozenset(pag) if pag else None
+        if self.pag:
+            unknown = self.pag - set(engine.PAG_LAYERS)
+            if unknown:
+                raise ValueError(f"pag: unknown layer(s) {sorted(unknown)}")
+            if control_net is not None or inpaint or tiled is not None or R or streams == 2:
+                raise ValueError("pag: text-to-image on one stream only (no ControlNet, inpainting, tiled, regions, denoise_streams = 2)")
 
     def _build_prep(self, control_net, hint_net) -> dict:
         """The preparation plans: per SCHEDULE the time-embedding tables (timestep -> MLP -> every ResBlock's projection: they do
@@ -203,8 +216,10 @@ class DenoiseEngine:
         unet, B, h, w, R, passes = self.unet, self.B, self.h, self.w, self.regions, self.passes
         dev = unet.device
         n = h * w * 4
-        self.eps = torch.zeros(((1 + (R or 1)) * B if self.cfg else (R or 1) * B), n, dtype=torch.float32, device=dev)
+        RC = R or (2 if self.pag else 1)
+        self.eps = torch.zeros(((1 + RC) * B if self.cfg else RC * B), n, dtype=torch.float32, device=dev)
         self.region_w = torch.zeros(R, h, w, dtype=torch.float32, device=dev) if R else None
+        self.pag_w = torch.zeros(2, h, w, dtype=torch.float32, device=dev) if self.pag else None
         self.branches = []
         step = None
         # ControlNet beside the UNet's down path: its encoder reads the same latent and is independent of the UNet until the
@@ -230,7 +245,9 @@ class DenoiseEngine:
                 feats = engine.emit_controlnet_features(s_cf, self.latent, B, nb, h, w, prep["table_c"], prep["kv_c"][tag], t, hint_nb)
                 taps = (s_c, feats)
             eps_view = _Ptr(self.eps.data_ptr() + row0 * n * 4)
-            engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps)
+            # (a PAG job: the p rows are the last B rows of the pass that holds the conditional rows)
+            pert = dict(pag_layers=self.pag, perturbed=B) if self.pag and tag != "uncond" else {}
+            engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps, **pert)
         return step
 
     def _build_tail(self, step, guidance, guidance_rescale, inpaint, tcd) -> "engine.Plan":
@@ -256,6 +273,10 @@ class DenoiseEngine:
             # (R == 1 too: a weight of all ones copies the row bit for bit)  Behind it the step kernels read [2B][n] (or [B][n])
             cond = _Ptr(self.eps.data_ptr() + (B if self.cfg else 0) * n * 4)
             tail.rec(ops.region_combine, eps=cond, w=self.region_w, out=cond, regions=R, batch=B, n=n)
+        if self.pag:
+            # c' = (1 + k) c - k p over the c rows; behind it the step kernels read [2B][n] (or [B][n]) as always
+            cond = _Ptr(self.eps.data_ptr() + (B if self.cfg else 0) * n * 4)
+            tail.rec(ops.region_combine, eps=cond, w=self.pag_w, out=cond, regions=2, batch=B, n=n, name="pag_combine")
         if self.sampler is None:
             tail.rec(ops.cfg_step, eps=self.eps, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr, batch=B, n=n,
                      num_steps=num_steps, guidance=guidance, guidance_rescale=guidance_rescale, advance=2,
@@ -302,7 +323,8 @@ class DenoiseEngine:
 
     def contexts(self, unconditional_context, context) -> dict:
         """The `prepare` input for this engine's pass layout (host arrays or device tensors).  A regional engine takes `context`
-        as the list of its R region contexts, each (B, T, 768): laid out uncond, region 0, region 1, ..., each B rows."""
+        as the list of its R region contexts, each (B, T, 768): laid out uncond, region 0, region 1, ..., each B rows.  A PAG engine
+        repeats `context` for its p rows: uncond, cond, cond."""
         if isinstance(context, (list, tuple)):
             if len(context) != self.regions:
                 raise ValueError(f"this engine evaluates {self.regions} region prompt(s): pass that many contexts as a list")
@@ -311,6 +333,8 @@ class DenoiseEngine:
                 context = torch.cat([_f32_tensor(c).to(dev) for c in context], dim=0)
             else:
                 context = np.concatenate([np.asarray(c, dtype=np.float32) for c in context], axis=0)
+        if getattr(self, "pag", None):   # the p rows read the conditional context again
+            context = torch.cat([context, context], dim=0) if isinstance(context, torch.Tensor) else np.concatenate([context, context], axis=0)
         if not self.cfg:
             return {"cond": context}
         if len(self.passes) == 1:
@@ -399,7 +423,7 @@ class DenoiseEngine:
 
     def prepare(self, contexts: Dict[str, np.ndarray], noise: np.ndarray, scheduler: Scheduler, timesteps,
                 start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None,
-                regions=None) -> None:
+                regions=None, pag_scale=None) -> None:
         """Upload the per-call inputs and run the preparation plan.  Every array may be a host array or a (device) tensor.
         noise = None: the start latent is already in `self.latent` (written there by stream-ordered device work queued before
         this call: the hand-off of a hires job), nothing is uploaded for it.
@@ -408,7 +432,13 @@ class DenoiseEngine:
         draws for the global batch) instead of the draws made here.  An engine built with a sampler takes its
         samplers.Schedule as `sampler` (the coefficient rows are built here for `start_index`) and, for the stochastic samplers,
         its draws as `step_noise` (B, num_steps, ...) (drawn here from numpy's global stream when None).
-        regions = the normalised weights (R, h, w) of a regional engine (regions.weights): a per-call upload, like the inpaint mask."""
+        regions = the normalised weights (R, h, w) of a regional engine (regions.weights): a per-call upload, like the inpaint mask.
+        pag_scale = the scale s of a PAG engine: the two planes fp32(1 + k), fp32(-k) (pag.weights, k from s and the engine's
+        guidance in float64) are a per-call upload too, so another scale needs no other engine."""
+        if (pag_scale is None) != (self.pag_w is None):
+            raise ValueError("prepare: `pag_scale` goes with an engine built with pag=<layers>, and only with one")
+        if self.pag_w is not None:
+            self.pag_w.copy_(torch.from_numpy(pag_mod.weights(pag_scale, self.guidance, self.h, self.w)))
         if (regions is None) != (self.region_w is None):
             raise ValueError("prepare: `regions` (the weights) goes with an engine built with regions=R, and only with one")
         if self.region_w is not None:
@@ -526,16 +556,17 @@ class StableDiffusionBase:
     # ---- public entry points (reference :84-139)
     def text_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                       embedding=None, negative_embedding=None, seed=None, control_net_image=None, guidance_rescale=0.7,
-                      callback=None, hires=None, tiled=None, regions=None, **kw):
+                      callback=None, hires=None, tiled=None, regions=None, pag=None, **kw):
         """``hires``: None, or a hires.HiresSpec / dict for the two-pass hires fix; ``tiled``: None, or a tiled.TiledSpec / dict
         for tiled diffusion on a canvas larger than the pipeline's size; ``regions``: None, or a regions.Regions / dict for
-        regional prompting, `prompt` being the base prompt (see generate_image)."""
+        regional prompting, `prompt` being the base prompt; ``pag``: None, or a pag.PagSpec / dict for perturbed-attention
+        guidance (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
                                    negative_embedding=negative_embedding, control_net_image=control_net_image,
                                    guidance_rescale=guidance_rescale, callback=callback, hires=hires, tiled=tiled, regions=regions,
-                                   **kw)
+                                   pag=pag, **kw)
 
     def image_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
@@ -768,7 +799,7 @@ class StableDiffusionBase:
                        diffusion_noise=None, seed=None, negative_embedding=None, control_net_image=None, inpaint_mask=None,
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
                        callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None,
-                       tiled=None, regions=None):
+                       tiled=None, regions=None, pag=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
@@ -789,9 +820,25 @@ class StableDiffusionBase:
         engine) and one msd_region_combine launch sums the predictions per latent pixel with the normalised mask weights in front
         of the guidance / sampler step.  With base_weight > 0 `encoded_text` joins as region 0 with that constant mask; with 0 it is
         not evaluated.  The region contexts share one token length.  At most 2 * tiled.MAX_VIEW_BATCH UNet rows
-        ((1 + R) * batch_size).  Works with host_loop=True too."""
+        ((1 + R) * batch_size).  Works with host_loop=True too.
+        ``pag`` (a pag.PagSpec or a dict {"scale": 3.0, "layers": "mid"}; txt2img only): perturbed-attention guidance - every step the
+        UNet evaluates the conditional context once more with the self-attention of the selected blocks replaced by the identity map
+        (further batch rows of the one engine, msd_attention_identity in those blocks) and eps = u + g (c - u) + s (c - p); one
+        msd_region_combine launch writes c' = (1 + k) c - k p over the conditional rows (k = s / g, or s without guidance) in front of
+        the guidance / sampler step, so `guidance_rescale` takes its reference std from c'.  ``layers``: "mid" or names of
+        engine.PAG_LAYERS.  scale = 0 is the plain job.  Works with every sampler, on a TCD pipeline, with shard_batch and with
+        host_loop=True; at most 2 * tiled.MAX_VIEW_BATCH UNet rows (3 * batch_size with guidance, 2 * batch_size without)."""
         given = dict(tiled=tiled, hires=hires, control_net_image=control_net_image, reference_image=reference_image,
-                     inpaint_mask=inpaint_mask)
+                     inpaint_mask=inpaint_mask, regions=regions)
+        pg = pag_mod.parse(pag)   # (ValueError for a bad description)
+        if pg is not None and pg.scale == 0.0:
+            pg = None   # (c' = c: the plain job, on the plain engine)
+        if pg is not None:
+            self._refuse_combinations("pag", given, host_loop)
+            rows = (3 if float(unconditional_guidance_scale) > 0.0 else 2) * int(batch_size)
+            if rows > 2 * tiled_mod.MAX_VIEW_BATCH:
+                raise ValueError(f"pag: {batch_size} image(s) are {rows} UNet rows per step, more than 2 * tiled.MAX_VIEW_BATCH = "
+                                 f"{2 * tiled_mod.MAX_VIEW_BATCH}: use a smaller batch")
         reg = regions_mod.parse(regions, self.img_height, self.img_width)   # (ValueError for a bad description)
         if reg is not None:
             self._refuse_combinations("regions", given, host_loop)
@@ -877,10 +924,10 @@ class StableDiffusionBase:
             ip = (encoded, noise, latent_mask[0]) if inpainting else None
             if spec is not None:
                 latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
-                                                 sampler_z, ip, region_w=region_w)
+                                                 sampler_z, ip, region_w=region_w, pag=pg)
             else:
                 latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending, ip,
-                                         region_w=region_w)
+                                         region_w=region_w, pag=pg)
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
             return finish(self.image_decoder.predict_on_batch(latent))
@@ -912,10 +959,10 @@ class StableDiffusionBase:
                 rep = (lambda x: x.unsqueeze(0).expand(b, -1, -1)) if isinstance(rc, torch.Tensor) else (lambda x: np.repeat(x[None], b, axis=0))
                 c = ([c] if reg.base_weight > 0.0 else []) + [rep(rc[i]) for i in range(rc.shape[0])]
             eng = self._denoise_pass(u, c, z, num_steps, g, phi, start_index, run_steps, callback,
-                                     dict(sampler=sname, regions=None if reg is None else len(c)),
+                                     dict(sampler=sname, regions=None if reg is None else len(c), pag=None if pg is None else pg.key),
                                      dict(hint_image=a.get("hint"), inpaint=(a["encoded"], a["noise"], a["mask"]) if inpainting else None,
                                           step_noise=a.get("tcd") if spec is None else a.get("sampler_z"), sampler=sched,
-                                          regions=a.get("region_w")))
+                                          regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale))
             if return_latent:
                 return eng.latent
             if blend_pixels:   # pixel blend in fp32 before the uint8 cast
@@ -933,6 +980,8 @@ class StableDiffusionBase:
                   ("host_loop=True", "a TCD pipeline (active_tcd=True)")),
         "hires": ("text-to-image on the device loop only", ("reference_image", "inpaint_mask", "control_net_image"),
                   ("host_loop=True", "a TCD pipeline (active_tcd=True)")),
+        "pag": ("text-to-image on one stream only", ("regions", "tiled", "hires", "control_net_image", "reference_image", "inpaint_mask"),
+                ("denoise_streams = 2",)),
     }
 
     def _refuse_combinations(self, kind, given: dict, host_loop) -> None:
@@ -1118,7 +1167,7 @@ class StableDiffusionBase:
         return np.stack(encoded, axis=0), reg.weights()
 
     def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> tuple:
-        """`opts`: sampler / unet / tiled / regions as _engine takes them; one at its default (None) adds nothing to the key."""
+        """`opts`: sampler / unet / tiled / regions / pag as _engine takes them; one at its default (None) adds nothing to the key."""
         # the engine's plans (and captured hipGraphs) hold raw addresses of the packed weights: a set_weights() /
         # load_synthetic() / LoRA reload on any of the models it was built from must retire it
         base = self.diffusion_model
@@ -1128,16 +1177,18 @@ class StableDiffusionBase:
         key = key if unet is base else key + ((unet.h, unet.w),)   # (a hires job's second size: a view of the same weights)
         key = key if tiled is None else key + (tiled.key,)         # (a tiled job: B counts views)
         # (a regional job: the NUMBER of evaluated region prompts only - masks, weights and prompts are per-call uploads)
-        return key if not regions else key + (("regions", int(regions)),)
+        key = key if not regions else key + (("regions", int(regions)),)
+        # (a PAG job: the selected blocks only - the scale is a per-call upload)
+        return key if not opts.get("pag") else key + (("pag", tuple(sorted(opts["pag"]))),)
 
     def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> DenoiseEngine:
         """The resident engine of this shape, built if need be.  `opts` are DenoiseEngine's: `sampler`; `unet`: the UNet of another
         size (a hires job's second pass); `tiled`: the geometry of a tiled job (B counts its views); `regions`: the number of
-        evaluated region prompts of a regional job.  `job_keys`: the keys of every engine the current job uses (default: this one
+        evaluated region prompts of a regional job; `pag`: the attention blocks of a PAG job.  `job_keys`: the keys of every engine the current job uses (default: this one
         alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is
         built: a re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than
         the job's own engines - one for a plain job, two for a hires job."""
-        if not set(opts) <= {"sampler", "unet", "tiled", "regions"}:
+        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag"}:
             raise TypeError(f"_engine: unknown option among {sorted(opts)}")
         key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, **opts)
         keep = {key} | set(job_keys or ())
@@ -1156,12 +1207,12 @@ class StableDiffusionBase:
                                 control_net=self.control_net if control else None,
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
                                 streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=opts.get("sampler"),
-                                tiled=opts.get("tiled"), regions=opts.get("regions") or 0)
+                                tiled=opts.get("tiled"), regions=opts.get("regions") or 0, pag=opts.get("pag"))
             self._engines[key] = eng
         return eng
 
     def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None,
-                   region_w=None):
+                   region_w=None, pag=None):
         """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479)."""
         if timesteps is None:
             timesteps = self.scheduler.timesteps[::-1]
@@ -1171,7 +1222,7 @@ class StableDiffusionBase:
         for _index, timestep in list(enumerate(timesteps))[::-1]:
             latent_prev = latent
             t_emb = get_timestep_embedding(timestep, batch_size)
-            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w)
+            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag)
             latent = self.scheduler.step(latent, timestep, latent_prev)
             if inpaint is not None:   # reference :469-475
                 init_latent, noise, latent_mask = inpaint
@@ -1183,10 +1234,11 @@ class StableDiffusionBase:
                 callback(iteration)
         return latent
 
-    def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None):
+    def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None):
         """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
         A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
-        predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host)."""
+        predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host).  A PAG job passes
+        its pag.Resolved: the conditional prediction becomes c' = (1 + k) c - k p, p from predict_perturbed (pag.combine_host)."""
         def predict(ctx):
             """The UNet's prediction for one context, through the ControlNet if there is a hint."""
             if hint is None:
@@ -1198,13 +1250,16 @@ class StableDiffusionBase:
         c = regions_mod.combine_host([predict(rc) for rc in context], region_w) if regional else None
         u = predict(unconditional_context) if g > 0.0 else None
         c = c if regional else predict(context)
+        if pag is not None:
+            p = self.diffusion_model.predict_perturbed([latent, t_emb, context], pag.layers)
+            c = pag_mod.combine_host(c, p, pag_mod.weights(pag.scale, g, latent.shape[1], latent.shape[2]))
         if u is None:
             return c
         e = u + g * (c - u)
         return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
 
     def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
-                           inpaint=None, region_w=None):
+                           inpaint=None, region_w=None, pag=None):
         """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`."""
         batch_size = latent.shape[0]
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
@@ -1213,7 +1268,7 @@ class StableDiffusionBase:
         prev = None
         for iteration, i in enumerate(range(start, sched.num_steps), start=1):
             t_emb = get_timestep_embedding(float(sched.timesteps[i]), batch_size)
-            e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint, region_w)
+            e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint, region_w, pag)
             z = step_noise[:, i] if step_noise is not None else None
             x, prev = smp.host_step(tab[i], x, e, prev, z)
             if inpaint is not None:   # the row's own alpha / sigma, as in the device kernel
