@@ -17,6 +17,16 @@
  *  - `step_ptr` (nullable) points at a device int32 holding the current denoise-step index, so a
  *    captured step graph can be replayed for every step: per-step tables (time-embedding
  *    projections, scheduler coefficients) are indexed with it on the device.
+ *
+ * Memory contract (tests/_extents.py restates it as formulas; the guard bands of the kernel tests, tests/_guard.py, hold every
+ * entry point to it, tests/test_plan_extents_cpu.py the launch plans): the comment of every
+ * operand below gives its extent - [rows][ld] carrying `cols` columns means the (rows - 1) * ld + cols elements from its base
+ * address, a [batch][...][ld] operand described with whole rows means all of them.  No entry point writes a byte outside the
+ * extents of its outputs (nor any byte of an input: the unused columns of a wide leading dimension are not its own), and no
+ * value outside the extents, nor inside a region documented as padding ("ignored", "unspecified content"), influences a
+ * result: callers pack buffers back to back and recycle them, so such bytes hold whatever the previous tenant left, NaN
+ * included.  Operands of one launch may overlap only where a comment says so (msd_replicate src == dst, msd_add_f32_bf16
+ * out == a, msd_conv_gemm residual == out, msd_region_combine out == eps).
  */
 #ifndef MINSDTF_HIP_H
 #define MINSDTF_HIP_H

@@ -218,3 +218,98 @@ def config_is_built(cfg, shape):
     if -(-N // bn) >= 256:   # column tiles travel in 8 bits of a packed launch argument (cg_hot_ok)
         return False
     return not (bm == 256 and M < 1024) and not (bn == 128 and N <= 64) and not (bn == 80 and (N % 80 or not allow_split)) and not (bn == 160 and (N % 160 or N < 1280))
+
+
+# ---- the second walker: EVERY recorded launch with the state of its buffers (tests/test_plan_extents_cpu.py) -----------------------
+# walk() above keeps what decides a conv launch's arithmetic; this one keeps, for every Plan.rec call of any op, the keyword
+# arguments and - at the moment of the rec - where each Buf / BufView / Act operand lies and whether its Buf was already freed.
+# Beyond ALL_WALKS: the CLIP text transformer (engine.emit_text_encoder), a UNet with perturbed-attention rows (msd_attention_identity
+# next to msd_attention), the ControlNet's HintNet, and the UNet fed by ControlNet taps (zero convs with residual == out).
+EXTENT_WALKS = ALL_WALKS + (("text", 1, 77, 1), ("text", 2, 77, 1), ("unet_pag", 3, 64, 64), ("hintnet", 2, 64, 64), ("unet_taps", 2, 64, 64))
+
+# one operand of a recorded launch: the Buf's identity, the operand's first byte in the arena, the bytes from there to the end of its
+# Buf, whether the Buf was freed when the launch was recorded; kind "buf" | "ws" | "gn_partials" | "gn_sync" | "gn_stats" (plan scratch,
+# sized at finalize()) | "outside" (a _Tensor stand-in: weights and buffers handed in from outside the plan, no size known)
+Operand = collections.namedtuple("Operand", ["kind", "buf", "offset", "avail", "freed"])
+Rec = collections.namedtuple("Rec", ["op", "name", "kw", "operands"])
+
+
+def _operand(v):
+    from minsdtf_amd import engine
+
+    if isinstance(v, engine.Act):
+        v = v.buf
+    if isinstance(v, engine.Buf):
+        return Operand("buf", id(v), v.offset, v.nbytes, v.freed)
+    if isinstance(v, engine.BufView):
+        return Operand("buf", id(v.buf), v.buf.offset + v.off, v.buf.nbytes - v.off, v.buf.freed)
+    if isinstance(v, engine._Lazy):
+        return Operand("gn_stats", None, 0, 0, False)
+    if isinstance(v, _Tensor):
+        return Operand("outside", None, 0, 0, False)
+    return None
+
+
+def walk_all(what, nb, h, w):
+    """Every Plan.rec call the emitters make for `what` at fused batch nb and latent size h x w, in recording order, as Rec records,
+    and the Plan (not finalized: ws_floats, gn_batch, gn_slots are what finalize() would size the scratch by)."""
+    from minsdtf_amd import engine
+    from minsdtf_amd import weights as wtab
+
+    out = []
+    orig = engine.Plan.rec
+
+    def rec(self, fn, **kw):
+        ops_ = {}
+        for k, v in kw.items():
+            if k == "split" and v is not None:
+                for part, item in (("out1", v[2]), ("out2", v[4])):
+                    o = _operand(item)
+                    if o is not None:
+                        ops_[part] = o
+                continue
+            if k in ("workspace", "partials", "sync") and isinstance(v, engine._Lazy):
+                ops_[k] = Operand({"workspace": "ws", "partials": "gn_partials", "sync": "gn_sync"}[k], None, 0, 0, False)
+                continue
+            o = _operand(v)
+            if o is not None:
+                ops_[k] = o
+        out.append(Rec(fn.__name__, kw.get("name", ""), kw, ops_))
+        return orig(self, fn, **kw)
+
+    engine.Plan.rec = rec
+    try:
+        p = engine.Plan("cpu")
+        e = engine.Emitter(p, _AnyWeights())
+        T = _Tensor
+        if what in ("unet", "controlnet", "unet_pag", "unet_taps"):
+            layers = engine.ENCODER_ATTN_LAYERS if what == "controlnet" else engine.UNET_ATTN_LAYERS
+            ctx = engine.Act(p.alloc(nb * 77 * 768 * 2), nb, 77, 1, 768)
+            kv = engine.emit_context_kv(e, ctx, layers, p)
+            temb = (T(), 0, 0, engine.temb_columns(what == "controlnet"))
+            if what == "unet":
+                engine.emit_unet(e, T(), nb, nb, h, w, temb, kv, 77, T(), None)
+            elif what == "unet_pag":   # the last row perturbed, in a 64x64-level block, the mid block and an up block
+                layers_ = (engine.PAG_LAYERS[1], "mid_block.attentions.0", engine.PAG_LAYERS[-1])
+                engine.emit_unet(e, T(), 1, nb, h, w, temb, kv, 77, T(), None, pag_layers=layers_, perturbed=1)
+            elif what == "unet_taps":  # ControlNet features -> zero convs into the skips (residual == out)
+                kv_c = engine.emit_context_kv(e, ctx, engine.ENCODER_ATTN_LAYERS, p)
+                feats = engine.emit_controlnet_features(e, T(), nb // 2, nb, h, w, (T(), 0, 0, engine.temb_columns(True)), kv_c, 77,
+                                                        p.act(nb, h, w, 320))
+                engine.emit_unet(e, T(), nb // 2, nb, h, w, temb, kv, 77, T(), None, control_taps=(e, feats))
+            else:
+                outs = [p.act(nb, h >> lv, w >> lv, ch) for lv, ch in zip((0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3), wtab.UNET_SKIP_CH + (1280,))]
+                engine.emit_controlnet(e, T(), nb, nb, h, w, temb, kv, 77, p.act(nb, h, w, 320), outs)
+        elif what == "vae":
+            engine.emit_decoder(e, T(), nb, h, w, T(), 0)
+        elif what == "vae_enc":
+            engine.emit_encoder(e, T(), nb, 8 * h, 8 * w, T())
+        elif what == "text":
+            engine.emit_text_encoder(e, p.act(nb, h, w, 768), 12)
+        elif what == "hintnet":
+            engine.emit_hintnet(e, T(), nb // 2, 8 * h, 8 * w, p.act(nb, h, w, 320), copies=2)
+        else:
+            raise ValueError(what)
+    finally:
+        engine.Plan.rec = orig
+    return out, p

@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _extents as X
+import _guard as G
 import _layer_walk as LW
 from conftest import run_calls
 from test_ops_gpu import bf, close, conv_ref
@@ -153,47 +155,64 @@ def test_layer_launch(gpu, sig):
     ref = _reference(s, t, w, wsc, bias, gamma, beta).reshape(Bmax, S, n_out)
     wnk, bdev, colsum = _packed(s, w, wsc, bias, gamma, beta, dev)
     del w, wsc
-    layouts = {0: wnk}
-    d = {k: (v.to(torch.bfloat16).to(dev) if (v is not None and k != "rv") else v) for k, v in t.items()}
-    rvd = t["rv"].to(dev) if s.rowvec else None
-    step = torch.tensor([STEP], dtype=torch.int32, device=dev)
+    # every operand between guard bands (tests/_guard.py), sized by the header's extents (tests/_extents.py) for the batch it is launched
+    # at; gw: what all batches share (weights, epilogue vectors, the step counter), g: one batch's activations and outputs
+    geo0 = dict(h_in=s.h_in, w_in=s.w_in, c0=s.c0, c1=s.c1, c2=s.c2, c3=s.c3, N=s.N, ksize=s.ksize, stride=s.stride, upsample=s.upsample,
+                pad=s.pad, pad_end=s.pad_end, act=s.act, out_dtype=s.out_dtype)
+    gw = G.Guard(dev, X.conv_gemm(w=1, bias=bdev, ln_colsum=colsum, step_ptr=1, batch=1, **geo0))
+    layouts = {0: gw.inp(wnk, "w")}
+    bdev = None if bdev is None else gw.inp(bdev, "bias")
+    colsum = None if colsum is None else gw.inp(colsum, "ln_colsum")
+    step = gw.inp(torch.tensor([STEP], dtype=torch.int32), "step_ptr")
+    d16 = {k: (v.to(torch.bfloat16) if (v is not None and k != "rv") else v) for k, v in t.items()}   # on the host: uploaded per batch
     atol = 2e-2 * float(ref.abs().max()) if s.ln_in else None
     sp = (S + 7) // 8 * 8          # V^T rows are read in 16-byte chunks
     ns2 = s.N - s.ns0 - s.ns1
+    out_ld = max(s.ns0, 4)
+    odt = torch.float32 if f32 else torch.bfloat16
     first = None                   # the largest batch's outputs, on the host
     for b in sorted(per, reverse=True):
+        M = b * S
+        geo = dict(batch=b, rv_step_stride=b * s.N if s.rowvec else 0, rv_batch_stride=s.N if s.rowvec else 0, **geo0)
+        split_dims = (s.ns0, s.ns1, 1, s.ns1, 1, sp) if s.split else None
+        g = G.Guard(dev, X.conv_gemm(a0=1, a1=d16["a1"], a2=d16["a2"], a3=d16["a3"], residual=d16["res"], rowvec=t["rv"], rv_steps=STEPS, **geo))
+        d = {k: (g.inp(v[:b], {"res": "residual"}.get(k, k)) if (v is not None and k != "rv") else None) for k, v in d16.items()}
+        rvd = g.inp(t["rv"][:, :b].contiguous(), "rowvec") if s.rowvec else None     # [STEPS][b][N]
         for l in per[b]:
-            M = b * S
             if l.w_layout not in layouts:
-                layouts[l.w_layout] = packing.chunk_major(wnk) if l.w_layout == 1 else packing.fragment_major(wnk)
-            ws = torch.empty(l.splitk * M * s.N, dtype=torch.float32, device=dev) if l.splitk > 1 else None
-            kw = dict(a0=d["a0"], a1=d["a1"], c1=s.c1, a2=d["a2"], c2=s.c2, a3=d["a3"], c3=s.c3, w=layouts[l.w_layout], w_layout=l.w_layout,
-                      batch=b, h_in=s.h_in, w_in=s.w_in, c0=s.c0, N=s.N, ksize=s.ksize, stride=s.stride, upsample=s.upsample, pad=s.pad,
-                      pad_end=s.pad_end, bias=bdev, residual=d["res"], act=s.act, out_dtype=s.out_dtype, workspace=ws,
-                      workspace_floats=0 if ws is None else ws.numel(), splitk=l.splitk, tile_m=l.tile_m, tile_n=l.tile_n, stages=l.stages)
+                layouts[l.w_layout] = gw.inp(packing.chunk_major(wnk) if l.w_layout == 1 else packing.fragment_major(wnk), "w", label=f"w layout {l.w_layout}")
+            g.ext.update(X.conv_gemm(out=1, split=split_dims, out_ld=out_ld if s.split else None, workspace=1 if l.splitk > 1 else None, splitk=l.splitk,
+                                     ln_in=1 if s.ln_in else None, ln_in_slots=l.ln_in_slots, ln_out=1 if s.ln_out else None,
+                                     ln_out_slots=l.ln_out_slots, **geo))
+            tag = f" {l.tile_m}x{l.tile_n} stages {l.stages} splitk {l.splitk} layout {l.w_layout}"
+            ws = g.out((l.splitk * M, s.N), torch.float32, float("nan"), "workspace", label="workspace" + tag) if l.splitk > 1 else None
+            kw = dict(a0=d["a0"], a1=d["a1"], a2=d["a2"], a3=d["a3"], w=layouts[l.w_layout], w_layout=l.w_layout,
+                      bias=bdev, residual=d["res"], workspace=ws,
+                      workspace_floats=0 if ws is None else ws.numel(), splitk=l.splitk, tile_m=l.tile_m, tile_n=l.tile_n, stages=l.stages, **geo)
             if s.rowvec:
-                kw.update(rowvec=rvd, rv_step_stride=Bmax * s.N, rv_batch_stride=s.N, step_ptr=step)
+                kw.update(rowvec=rvd, step_ptr=step)
             stats_in = stats_out = None
             if s.ln_in:
-                stats_in = _row_moments(t["a0"][:b].reshape(M, s.c0), l.ln_in_slots).to(dev)
+                stats_in = g.inp(_row_moments(t["a0"][:b].reshape(M, s.c0), l.ln_in_slots), "ln_in", label="ln_in" + tag)
                 kw.update(ln_in=stats_in, ln_in_slots=l.ln_in_slots, ln_colsum=colsum, ln_eps=1e-5)
             if s.ln_out:
                 assert l.ln_out_slots == ops.conv_gemm_ln_slots(N=s.N, tile_n=l.tile_n, tile_m=l.tile_m, ksize=s.ksize, act=s.act)
-                stats_out = torch.full((M, l.ln_out_slots, 2), float("nan"), dtype=torch.float32, device=dev)
+                stats_out = g.out((M, l.ln_out_slots, 2), torch.float32, float("nan"), "ln_out", label="ln_out" + tag)
                 kw.update(ln_out=stats_out, ln_out_slots=l.ln_out_slots)
             if s.split:
-                q = torch.full((M, max(s.ns0, 4)), float("nan"), dtype=torch.bfloat16, device=dev) if s.ns0 else None
-                k = torch.full((M, s.ns1), float("nan"), dtype=torch.bfloat16, device=dev)
-                vt = torch.full((b, ns2, sp), float("nan"), dtype=torch.bfloat16, device=dev)
-                kw.update(out=q, out_ld=max(s.ns0, 4), split=(s.ns0, s.ns1, k, s.ns1, vt, sp))
+                q = g.out((M, out_ld), torch.bfloat16, float("nan"), "out", label="q" + tag) if s.ns0 else None
+                k = g.out((M, s.ns1), torch.bfloat16, float("nan"), "out1", label="k" + tag)
+                vt = g.out((b, ns2, sp), torch.bfloat16, float("nan"), "out2", label="v^T" + tag)
+                g.gaps(vt, S)      # columns [S, sp) of v^T are padding: a canary, not written
+                kw.update(out=q, out_ld=out_ld, split=(s.ns0, s.ns1, k, s.ns1, vt, sp))
                 outs = ([("q", q.view(b, S, -1), ref[:b, :, :s.ns0])] if s.ns0 else []) + \
                     [("k", k.view(b, S, s.ns1), ref[:b, :, s.ns0:s.ns0 + s.ns1]), ("v^T", vt[:, :, :S].permute(0, 2, 1), ref[:b, :, s.ns0 + s.ns1:])]
             else:
-                out = torch.full((M, n_out), float("nan"), dtype=torch.float32 if f32 else torch.bfloat16, device=dev)
+                out = g.out((M, n_out), odt, float("nan"), "out", label="out" + tag)
                 kw.update(out=out)
                 outs = [("out", out.view(b, S, n_out), ref[:b])]
             run_calls(ops.conv_gemm(**kw))
-            what = f"{sid} | batch {b} {l.tile_m}x{l.tile_n} stages {l.stages} splitk {l.splitk} layout {l.w_layout}"
+            what = f"{sid} | batch {b}{tag}"
             got = [(name, o.cpu().contiguous()) for name, o, _ in outs]
             for (name, o, r), (_, g_) in zip(outs, got):
                 close(g_, r, atol=atol, what=f"{what} {name}")
@@ -207,9 +226,12 @@ def test_layer_launch(gpu, sig):
             for (name, g_), (_, g0) in zip(got, first):   # one numerics class per layer: a sample's bits do not depend on its batch
                 for i in {0, b - 1}:
                     assert torch.equal(g_[i].view(bits), g0[i].view(bits)), f"{what} {name}: sample {i} differs from its bits at batch {Bmax}"
+            g.check()
             del ws, kw, outs, got, stats_in, stats_out
+        del g, d, rvd
+    gw.check()
     _ran.add(sid)
-    del t, d, ref, layouts, wnk, first
+    del t, d16, ref, layouts, wnk, first, gw
     gc.collect()
     torch.cuda.empty_cache()
 

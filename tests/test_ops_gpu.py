@@ -9,34 +9,55 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _extents as X
+import _guard as G
+from _checks import bf, close   # noqa: F401  (tests/test_layer_shapes_gpu.py takes them from here too)
 from conftest import run_calls
 
 pytestmark = pytest.mark.gpu
 
-
-def bf(x):
-    """Round an fp32 CPU tensor to bf16 and back (what the device will see)."""
-    return x.to(torch.bfloat16).to(torch.float32)
+BF16 = torch.bfloat16
+NAN = float("nan")
 
 
-def close(got, ref, rtol=1e-2, atol=None, what="", rms=None):
-    """Element-wise: |got - ref| <= atol + rtol |ref| everywhere.  Aggregate: relative RMS error ||got - ref|| / ||ref|| <=
-    `rms`, by default 2^-7 for a bf16 result (its own rounding is 2^-9 relative per element) and 2^-12 for an fp32 result of
-    bf16 operands — the element-wise floor alone would let a dropped K chunk of one tap of a K = 2,304 contraction through;
-    the aggregate does not."""
-    is_f32 = got.dtype == torch.float32
-    got = got.detach().float().cpu()
-    ref = ref.detach().float().cpu()
-    if atol is None:
-        atol = 1e-2 * float(ref.abs().max()) + 1e-6
-    assert bool(torch.isfinite(got).all()), f"{what}: {int((~torch.isfinite(got)).sum())}/{got.numel()} non-finite outputs"
-    err = (got - ref).abs()
-    bad = err > (atol + rtol * ref.abs())
-    assert not bool(bad.any()), f"{what}: {int(bad.sum())}/{bad.numel()} mismatches, max err {float(err.max()):.4g}, ref max {float(ref.abs().max()):.4g}"
-    if rms is None:
-        rms = 2.0 ** -12 if is_f32 else 2.0 ** -7
-    rel = float((got - ref).double().norm() / max(float(ref.double().norm()), 1e-30))
-    assert rel <= rms, f"{what}: relative RMS error {rel:.3g} > {rms:.3g}"
+def guarded_attention(dev, q, k, v, *, H, d, q_ld, vt_ld, poison, workspace=False):
+    """The operands of one msd_attention launch between guard bands (tests/_guard.py), sized by the header's extents: q [B, S, H d] as rows
+    of a q_ld-wide buffer, k [B, T, H d], v [B, T, H d] stored transposed with vt_ld >= T columns.  The padding the header calls
+    ignored - V^T's columns [T, vt_ld) and the columns of the q buffer outside the head block - holds NaN (poison) or zeros (the A / B
+    launch: the same bits are expected).  Returns (guard, the launch's keyword arguments, out [B, S, H d])."""
+    B, S, C = q.shape
+    T = k.shape[1]
+    assert C == H * d
+    geo = dict(batch=B, heads=H, head_dim=d, s=S, t=T, q_ld=q_ld, k_ld=C, vt_ld=vt_ld, o_ld=C)
+    g = G.Guard(dev, X.attention(q=1, k=1, vt=1, out=1, workspace=1 if workspace else None, **geo))
+    pad = None if poison else 0.0
+    qd = g.inp(q.to(BF16).reshape(B * S, C), "q", ld=q_ld if q_ld > C else None, gap=pad)
+    kd = g.inp(k.to(BF16), "k")
+    vt = g.out((B, C, vt_ld), BF16, 0.0, "vt")
+    vt[:, :, :T] = v.permute(0, 2, 1).to(BF16).to(dev)
+    g.operands[-1].role = "in"
+    g.gaps(vt, T, gap=pad)
+    out = g.out((B, S, C), BF16, NAN, "out")
+    kw = dict(q=qd, k=kd, vt=vt, out=out, **geo)
+    if workspace:
+        wsf = X.attention_workspace_floats(B, H, S)
+        kw.update(workspace=g.out((4 * B * H * S, d + 2), torch.float32, NAN, "workspace"), workspace_floats=wsf)
+    return g, kw, out
+
+
+def attention_ab(dev, make_call, q, k, v, **kw):
+    """Run the launch make_call(**operands) twice: NaN in every padding region, then zeros.  Returns (guard, operands, out) of both;
+    the caller compares the first with its reference; here: the same bits (padding content never reaches a result), bands intact."""
+    a = guarded_attention(dev, q, k, v, poison=True, **kw)
+    b = guarded_attention(dev, q, k, v, poison=False, **kw)
+    run_calls([make_call(**a[1]), make_call(**b[1])])
+    return a, b
+
+
+def same_bits_whatever_the_padding(a, b, what=""):
+    assert torch.equal(a[2].view(torch.int16), b[2].view(torch.int16)), f"{what}: the content of a padding region reached the result"
+    a[0].check()
+    b[0].check()
 
 
 def conv_ref(x_nhwc, w_hwio, bias=None, stride=1, pad=1, upsample=False):
@@ -224,44 +245,40 @@ def test_conv_gemm(gpu, case):
     ref = ref + resid
 
     d = gpu
-    wp = packing.pack_conv(w.numpy(), d)
-    x0d, x1d = x0.to(torch.bfloat16).to(d), (x1.to(torch.bfloat16).to(d) if c1 else None)
     f32out = case.get("f32out", False)
-    out = torch.full((M, N), float("nan"), dtype=torch.float32 if f32out else torch.bfloat16, device=d)
-    ws = torch.empty(max(1, splitk * M * N), dtype=torch.float32, device=d)
-    step = torch.tensor([2], dtype=torch.int32, device=d)
-    biasd, tembd, residd = bias.to(d), temb.to(d), resid.to(torch.bfloat16).to(d)   # (a Call holds addresses, not tensors)
+    odt = torch.float32 if f32out else BF16
+    # every operand between guard bands, sized by the header's extents (tests/_extents.py); geo = the launch's dimensions
+    geo = dict(batch=B, h_in=H, w_in=W, c0=c0, c1=c1, N=N, ksize=ks, stride=stride, upsample=ups, rv_step_stride=B * N, rv_batch_stride=N,
+               out_dtype=ops.OUT_F32 if f32out else ops.OUT_BF16, splitk=splitk, **(dict(pad=0, pad_end=1) if asym else {}))
+    g = G.Guard(d, X.conv_gemm(a0=1, a1=x1, w=1, bias=1, rowvec=1, step_ptr=1, residual=1, out=1, workspace=1 if splitk > 1 else None,
+                               rv_steps=steps, **geo))
+    wp = g.inp(packing.pack_conv(w.numpy(), d), "w")
+    x0d, x1d = g.inp(x0.to(BF16), "a0"), (g.inp(x1.to(BF16), "a1") if c1 else None)
+    out = g.out((M, N), odt, NAN, "out")
+    ws = g.out((splitk * M, N), torch.float32, NAN, "workspace") if splitk > 1 else None   # (the header: NULL if splitk <= 1)
+    step = g.inp(torch.tensor([2], dtype=torch.int32), "step_ptr")
+    biasd, tembd, residd = g.inp(bias, "bias"), g.inp(temb, "rowvec"), g.inp(resid.to(BF16), "residual")   # (a Call holds addresses, not tensors)
     wreg = 4000 <= case.get("tile_m", 0) < 5000
-    wmain = packing.fragment_major(wp) if wreg else wp
-    call = ops.conv_gemm(a0=x0d, a1=x1d, c1=c1, w=wmain, w_layout=2 if wreg else 0, out=out, batch=B, h_in=H, w_in=W, c0=c0, N=N, ksize=ks, stride=stride,
-                         upsample=ups, bias=biasd, rowvec=tembd, rv_step_stride=B * N, rv_batch_stride=N,
-                         step_ptr=step, residual=residd, act=ops.ACT_SILU if case.get("act") else ops.ACT_NONE,
-                         out_dtype=ops.OUT_F32 if f32out else ops.OUT_BF16, workspace=ws, workspace_floats=ws.numel(),
-                         splitk=splitk, tile_n=case.get("tile_n", 0), tile_m=case.get("tile_m", 0), stages=case.get("stages", 0),
-                         **(dict(pad=0, pad_end=1) if asym else {}))
+    wmain = g.inp(packing.fragment_major(wp), "w", label="w fragment-major") if wreg else wp
+    common = dict(a0=x0d, a1=x1d, bias=biasd, rowvec=tembd, step_ptr=step, residual=residd, act=ops.ACT_SILU if case.get("act") else ops.ACT_NONE,
+                  workspace=ws, workspace_floats=0 if ws is None else ws.numel(), **geo)
+    call = ops.conv_gemm(w=wmain, w_layout=2 if wreg else 0, out=out, tile_n=case.get("tile_n", 0), tile_m=case.get("tile_m", 0),
+                         stages=case.get("stages", 0), **common)
     run_calls(call)
     close(out.reshape(B, Ho, Wo, N), ref, what=str(case))
+    bits = torch.int32 if f32out else torch.int16
     if case.get("same_as"):   # tile shape / kernel form never changes a result's bits (K tiles are summed in the same order)
         tm, tn, stg = case["same_as"]
-        out2 = torch.full_like(out, float("nan"))
-        run_calls(ops.conv_gemm(a0=x0d, a1=x1d, c1=c1, w=wp, out=out2, batch=B, h_in=H, w_in=W, c0=c0, N=N, ksize=ks, stride=stride,
-                                upsample=ups, bias=biasd, rowvec=tembd, rv_step_stride=B * N, rv_batch_stride=N, step_ptr=step,
-                                residual=residd, act=ops.ACT_SILU if case.get("act") else ops.ACT_NONE,
-                                out_dtype=ops.OUT_F32 if f32out else ops.OUT_BF16, tile_n=tn, tile_m=tm, stages=stg,
-                                workspace=ws, workspace_floats=ws.numel(), splitk=splitk, **(dict(pad=0, pad_end=1) if asym else {})))
-        bits = torch.int32 if f32out else torch.int16
+        out2 = g.out((M, N), odt, NAN, "out", label="out same_as")
+        run_calls(ops.conv_gemm(w=wp, out=out2, tile_n=tn, tile_m=tm, stages=stg, **common))
         assert torch.equal(out.view(bits), out2.view(bits)), "tile shape / kernel form changed the bits"
-    if wreg:   # (the fragment-major image IS the layout this form reads)
-        return
-    # chunk-major weights [K/64][N][64] (w_layout = 1, the form the models keep): storage order only, the same bits
-    out3 = torch.full_like(out, float("nan"))
-    run_calls(ops.conv_gemm(a0=x0d, a1=x1d, c1=c1, w=packing.chunk_major(wp), w_layout=1, out=out3, batch=B, h_in=H, w_in=W, c0=c0, N=N,
-                            ksize=ks, stride=stride, upsample=ups, bias=biasd, rowvec=tembd, rv_step_stride=B * N,
-                            rv_batch_stride=N, step_ptr=step, residual=residd,
-                            act=ops.ACT_SILU if case.get("act") else ops.ACT_NONE, out_dtype=ops.OUT_F32 if f32out else ops.OUT_BF16,
-                            workspace=ws, workspace_floats=ws.numel(), splitk=splitk, tile_n=case.get("tile_n", 0),
-                            tile_m=case.get("tile_m", 0), stages=case.get("stages", 0), **(dict(pad=0, pad_end=1) if asym else {})))
-    assert torch.equal(out.view(torch.int32 if f32out else torch.int16), out3.view(torch.int32 if f32out else torch.int16)), "weight layout changed the bits"
+    if not wreg:   # (wreg: the fragment-major image IS the layout this form reads)
+        # chunk-major weights [K/64][N][64] (w_layout = 1, the form the models keep): storage order only, the same bits
+        out3 = g.out((M, N), odt, NAN, "out", label="out chunk-major")
+        run_calls(ops.conv_gemm(w=g.inp(packing.chunk_major(wp), "w", label="w chunk-major"), w_layout=1, out=out3, tile_n=case.get("tile_n", 0),
+                                tile_m=case.get("tile_m", 0), stages=case.get("stages", 0), **common))
+        assert torch.equal(out.view(bits), out3.view(bits)), "weight layout changed the bits"
+    g.check()
 
 
 @pytest.mark.parametrize("case", [
@@ -309,19 +326,22 @@ def test_conv_gemm_shortcut_operand(gpu, case):
     xin = torch.cat([x0, x1], dim=-1) if cx1 else x0
     ref = conv_ref(h, w2, b2, pad=1 if ks == 3 else 0) + conv_ref(xin, wsc, bs, pad=0)
     d = gpu
-    wcat = torch.cat([w2.permute(3, 0, 1, 2).reshape(N, -1), wsc.permute(3, 0, 1, 2).reshape(N, -1)], dim=1).to(torch.bfloat16).contiguous().to(d)
+    wcat = torch.cat([w2.permute(3, 0, 1, 2).reshape(N, -1), wsc.permute(3, 0, 1, 2).reshape(N, -1)], dim=1).to(torch.bfloat16).contiguous()
     M = B * H * W
     sk = case.get("splitk", 1)
-    keep = [h.to(torch.bfloat16).to(d), x0.to(torch.bfloat16).to(d), x1.to(torch.bfloat16).to(d) if cx1 else None, (b2 + bs).to(d),
-            torch.empty(max(1, sk * M * N), dtype=torch.float32, device=d)]
     from minsdtf_amd import packing
 
-    out = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=d)
+    geo = dict(batch=B, h_in=H, w_in=W, c0=c, N=N, ksize=ks, c2=cx0, c3=cx1, splitk=sk)
+    g = G.Guard(d, X.conv_gemm(a0=1, w=1, out=1, bias=1, a2=1, a3=x1, workspace=1 if sk > 1 else None, **geo))
+    wcat = g.inp(wcat, "w")
+    ws = g.out((sk * M, N), torch.float32, NAN, "workspace") if sk > 1 else None
+    common = dict(a0=g.inp(h.to(BF16), "a0"), a2=g.inp(x0.to(BF16), "a2"), a3=g.inp(x1.to(BF16), "a3") if cx1 else None, bias=g.inp(b2 + bs, "bias"),
+                  workspace=ws, workspace_floats=0 if ws is None else ws.numel(), **geo)
+    out = g.out((M, N), BF16, NAN, "out")
     wreg = 4000 <= case.get("tile_m", 0) < 5000
-    wmain = packing.fragment_major(wcat) if wreg else wcat
-    call = ops.conv_gemm(a0=keep[0], w=wmain, w_layout=2 if wreg else 0, out=out, batch=B, h_in=H, w_in=W, c0=c, N=N, ksize=ks, bias=keep[3],
-                         a2=keep[1], c2=cx0, a3=keep[2], c3=cx1, workspace=keep[4], workspace_floats=keep[4].numel(), splitk=sk,
-                         tile_m=case.get("tile_m", 0), tile_n=case.get("tile_n", 0), stages=case.get("stages", 0))
+    wmain = g.inp(packing.fragment_major(wcat), "w", label="w fragment-major") if wreg else wcat
+    call = ops.conv_gemm(w=wmain, w_layout=2 if wreg else 0, out=out, tile_m=case.get("tile_m", 0), tile_n=case.get("tile_n", 0),
+                         stages=case.get("stages", 0), **common)
     run_calls(call)
     close(out.reshape(B, H, W, N), ref, what=str(case))
     # chunk-major weights on the same tile (wreg: on the tile kernel): storage order / kernel form only, the same bits
@@ -329,11 +349,10 @@ def test_conv_gemm_shortcut_operand(gpu, case):
     other = dict(tile_m=64, tile_n=128) if (wreg or big) else dict(tile_m=case.get("tile_m", 0), tile_n=case.get("tile_n", 0), stages=case.get("stages", 0))
     if case.get("other"):
         other = dict(tile_m=case["other"][0], tile_n=case["other"][1], stages=case["other"][2])
-    out2 = torch.full_like(out, float("nan"))
-    run_calls(ops.conv_gemm(a0=keep[0], w=packing.chunk_major(wcat), w_layout=1, out=out2, batch=B, h_in=H, w_in=W, c0=c, N=N, ksize=ks,
-                            bias=keep[3], a2=keep[1], c2=cx0, a3=keep[2], c3=cx1, workspace=keep[4], workspace_floats=keep[4].numel(),
-                            splitk=sk, **other))
+    out2 = g.out((M, N), BF16, NAN, "out", label="out chunk-major")
+    run_calls(ops.conv_gemm(w=g.inp(packing.chunk_major(wcat), "w", label="w chunk-major"), w_layout=1, out=out2, **common, **other))
     assert torch.equal(out.view(torch.int16), out2.view(torch.int16)), "weight layout / kernel form changed the bits"
+    g.check()
 
 
 @pytest.mark.parametrize("tile", [(0, 0), (128, 160), (64, 128), (3128, 320), (4128, 128), (4064, 256), (5256, 256), (5128, 256), (5256, 128)])   # heuristic tile, the 128x160 tile (16x16 level), 64x128, row panels, wreg, big
@@ -351,12 +370,15 @@ def test_conv_gemm_geglu(gpu, tile):
     a, gate = h[:, :4 * C], h[:, 4 * C:]
     ref = a * 0.5 * gate * (1 + torch.tanh(gate * 0.7978845608 * (1 + 0.044715 * gate ** 2)))
     wp, bp = packing.pack_geglu(w.numpy(), b.numpy(), gpu)
-    out = torch.full((M, 4 * C), float("nan"), dtype=torch.bfloat16, device=gpu)
+    geo = dict(batch=1, h_in=M, w_in=1, c0=C, N=8 * C, act=ops.ACT_GEGLU)
+    g = G.Guard(gpu, X.conv_gemm(a0=1, w=1, out=1, bias=1, **geo))
+    out = g.out((M, 4 * C), BF16, NAN, "out")        # GEGLU writes N / 2 columns
     wreg = 4000 <= tile[0] < 5000
-    call = ops.conv_gemm(a0=x.to(torch.bfloat16).to(gpu), w=packing.fragment_major(wp) if wreg else wp, w_layout=2 if wreg else 0, out=out, batch=1,
-                         h_in=M, w_in=1, c0=C, N=8 * C, bias=bp, act=ops.ACT_GEGLU, tile_m=tile[0], tile_n=tile[1], stages=3 if wreg else 0)
+    call = ops.conv_gemm(a0=g.inp(x.to(BF16), "a0"), w=g.inp(packing.fragment_major(wp) if wreg else wp, "w"), w_layout=2 if wreg else 0, out=out,
+                         bias=g.inp(bp, "bias"), tile_m=tile[0], tile_n=tile[1], stages=3 if wreg else 0, **geo)
     run_calls(call)
     close(out, ref, what=f"geglu {tile}")
+    g.check()
 
 
 @pytest.mark.parametrize("case", [
@@ -410,9 +432,6 @@ def test_conv_gemm_layer_norm_fold(gpu, case):
     ctm, ctn, cstg = case.get("ctile", (0, 0, 0))
     ckw = dict(tile_m=ctm, tile_n=ctn, stages=cstg)
 
-    def lay(w, tile_m):   # the weight image a launch reads: fragment-major for the wreg form
-        return dict(w=packing.fragment_major(w), w_layout=2) if 4000 <= tile_m < 5000 else dict(w=w)
-
     x = bf(torch.randn(M, C))
     res = bf(torch.randn(M, C) * 2 + 0.5)                      # non-zero row means
     if case.get("nores"):
@@ -423,23 +442,34 @@ def test_conv_gemm_layer_norm_fold(gpu, case):
     gamma, beta = 1 + 0.3 * torch.randn(C), 0.2 * torch.randn(C)
     ln = F.layer_norm(t, (C,), gamma, beta, eps=1e-5)
     d = gpu
-    tdev = torch.full((M, C), float("nan"), dtype=torch.bfloat16, device=d)
     slots = ops.conv_gemm_ln_slots(N=C, tile_n=tn, tile_m=tm)
     assert slots == -(-C // (64 if 3000 <= tm < 4000 else tn))
-    stats = torch.full((M, slots, 2), float("nan"), dtype=torch.float32, device=d)
-    keep = [x.to(torch.bfloat16).to(d), packing.pack_dense(w0.numpy(), d), b0.to(d), res.to(torch.bfloat16).to(d)]   # (Calls hold raw pointers)
-    if case.get("nores"):
-        keep[3] = None
-    keep.append(lay(keep[1], tm))
-    prod = ops.conv_gemm(a0=keep[0], **keep[4], out=tdev, batch=1, h_in=M, w_in=1, c0=C, N=C, bias=keep[2], residual=keep[3],
-                         tile_m=tm, tile_n=tn, stages=stg, ln_out=stats, ln_out_slots=slots)
+    nores = bool(case.get("nores"))
+    pgeo = dict(batch=1, h_in=M, w_in=1, c0=C, N=C, ln_out_slots=slots)
+    g = G.Guard(d)
+    g.bind("prod.", X.conv_gemm(a0=1, w=1, bias=1, residual=None if nores else 1, out=1, ln_out=1, **pgeo))
+    tdev = g.out((M, C), BF16, NAN, "prod.out")
+    stats = g.out((M, slots, 2), torch.float32, NAN, "prod.ln_out")
+    w0d = g.inp(packing.pack_dense(w0.numpy(), d), "prod.w")
+    pin = dict(a0=g.inp(x.to(BF16), "prod.a0"), bias=g.inp(b0, "prod.bias"), residual=None if nores else g.inp(res.to(BF16), "prod.residual"), **pgeo)   # (Calls hold raw pointers)
+
+    def lay(w, tile_m, name):   # the weight image a launch reads: fragment-major for the wreg form
+        return dict(w=g.inp(packing.fragment_major(w), name, label=name + " fragment-major"), w_layout=2) if 4000 <= tile_m < 5000 else dict(w=w)
+
+    prod = ops.conv_gemm(**pin, **lay(w0d, tm, "prod.w"), out=tdev, tile_m=tm, tile_n=tn, stages=stg, ln_out=stats)
     if case.get("psame"):
-        tdev2, stats2 = torch.full_like(tdev, float("nan")), torch.full_like(stats, float("nan"))
-        run_calls([prod, ops.conv_gemm(a0=keep[0], w=keep[1], out=tdev2, batch=1, h_in=M, w_in=1, c0=C, N=C, bias=keep[2], residual=keep[3],
-                                       tile_m=128, tile_n=64, ln_out=stats2, ln_out_slots=slots)])
+        tdev2, stats2 = g.out((M, C), BF16, NAN, "prod.out", label="prod.out 128x64"), g.out((M, slots, 2), torch.float32, NAN, "prod.ln_out", label="prod.ln_out 128x64")
+        run_calls([prod, ops.conv_gemm(**pin, w=w0d, out=tdev2, tile_m=128, tile_n=64, ln_out=stats2)])
         assert torch.equal(tdev.view(torch.int16), tdev2.view(torch.int16)), "row-panel producer changed the output bits"
         assert torch.equal(stats.view(torch.int32), stats2.view(torch.int32)), "row-panel producer changed the row-moment partials"
     mode = case["mode"]
+    Nc = {"geglu": 8 * C, "qkv": 3 * C, "dense": C}[mode]
+    sp = (M + 7) // 8 * 8
+    cgeo = dict(batch=1, h_in=M, w_in=1, c0=C, N=Nc, ln_in_slots=slots, **(dict(act=ops.ACT_GEGLU) if mode == "geglu" else {}))
+    split_dims = (C, C, 1, C, 1, sp) if mode == "qkv" else None
+    g.bind("cons.", X.conv_gemm(a0=1, w=1, bias=1, ln_in=1, ln_colsum=1, out=1, split=split_dims, **cgeo))
+    g.same(tdev, "cons.a0")          # the producer's output is the consumer's input; its partials are the consumer's ln_in
+    g.same(stats, "cons.ln_in")
     if mode == "geglu":
         w1 = bf(torch.randn(C, 8 * C) / math.sqrt(C))
         b1 = torch.randn(8 * C) * 0.1
@@ -448,55 +478,48 @@ def test_conv_gemm_layer_norm_fold(gpu, case):
         ref = a * 0.5 * gate * (1 + torch.tanh(gate * 0.7978845608 * (1 + 0.044715 * gate ** 2)))
         order = torch.from_numpy(packing.geglu_row_order(4 * C))
         wf, cs, cb = packing.fold_layer_norm(w1.t().contiguous()[order], b1.numpy()[order.numpy()], gamma.numpy(), beta.numpy(), d)
-        out = torch.full((M, 4 * C), float("nan"), dtype=torch.bfloat16, device=d)
-        wfl = lay(wf, ctm)
-        cons = ops.conv_gemm(a0=tdev, **wfl, out=out, batch=1, h_in=M, w_in=1, c0=C, N=8 * C, bias=cb, act=ops.ACT_GEGLU,
-                             ln_in=stats, ln_in_slots=slots, ln_colsum=cs, **ckw)
-        run_calls([prod, cons])
-        close(out, ref, atol=2e-2 * float(ref.abs().max()), what=str(case))
-        if case.get("csame"):
-            out2 = torch.full_like(out, float("nan"))
-            run_calls(ops.conv_gemm(a0=tdev, w=wf, out=out2, batch=1, h_in=M, w_in=1, c0=C, N=8 * C, bias=cb, act=ops.ACT_GEGLU,
-                                    ln_in=stats, ln_in_slots=slots, ln_colsum=cs))
-            assert torch.equal(out.view(torch.int16), out2.view(torch.int16)), "row-panel kernel changed the bits"
     elif mode == "qkv":
         w1 = bf(torch.randn(C, 3 * C) / math.sqrt(C))
         ref = ln @ w1
         wf, cs, cb = packing.fold_layer_norm(w1.t().contiguous(), None, gamma.numpy(), beta.numpy(), d)
-        q = torch.full((M, C), float("nan"), dtype=torch.bfloat16, device=d)
-        k = torch.full((M, C), float("nan"), dtype=torch.bfloat16, device=d)
-        sp = (M + 7) // 8 * 8
-        vt = torch.zeros((1, C, sp), dtype=torch.bfloat16, device=d)
-        wfl = lay(wf, ctm)
-        cons = ops.conv_gemm(a0=tdev, **wfl, out=q, batch=1, h_in=M, w_in=1, c0=C, N=3 * C, bias=cb, split=(C, C, k, C, vt, sp),
-                             ln_in=stats, ln_in_slots=slots, ln_colsum=cs, **ckw)
+    else:
+        w1 = bf(torch.randn(C, C) / math.sqrt(C))
+        b1 = torch.randn(C) * 0.1
+        ref = ln @ w1 + b1
+        wf, cs, cb = packing.fold_layer_norm(w1.t().contiguous(), b1.numpy(), gamma.numpy(), beta.numpy(), d)
+    wf = g.inp(wf, "cons.w")
+    cin = dict(a0=tdev, bias=g.inp(cb, "cons.bias"), ln_in=stats, ln_colsum=g.inp(cs, "cons.ln_colsum"), **cgeo)
+    if mode == "qkv":
+        def parts(tag):
+            q = g.out((M, C), BF16, NAN, "cons.out", label="q" + tag)
+            k = g.out((M, C), BF16, NAN, "cons.out1", label="k" + tag)
+            vt = g.out((1, C, sp), BF16, NAN, "cons.out2", label="v^T" + tag)
+            g.gaps(vt, M)                                  # columns [M, sp) of v^T are padding: a canary, never written
+            return q, k, vt
+
+        q, k, vt = parts("")
+        cons = ops.conv_gemm(**cin, **lay(wf, ctm, "cons.w"), out=q, split=(C, C, k, C, vt, sp), **ckw)
         run_calls([prod, cons])
         atol = 2e-2 * float(ref.abs().max())
         close(q, ref[:, :C], atol=atol, what=str(case) + " q")
         close(k, ref[:, C:2 * C], atol=atol, what=str(case) + " k")
         close(vt[0, :, :M].t(), ref[:, 2 * C:], atol=atol, what=str(case) + " v^T")
         if case.get("csame"):
-            q2, k2, vt2 = torch.full_like(q, float("nan")), torch.full_like(k, float("nan")), torch.zeros_like(vt)
-            run_calls(ops.conv_gemm(a0=tdev, w=wf, out=q2, batch=1, h_in=M, w_in=1, c0=C, N=3 * C, bias=cb, split=(C, C, k2, C, vt2, sp),
-                                    ln_in=stats, ln_in_slots=slots, ln_colsum=cs))
+            q2, k2, vt2 = parts(" tile kernel")
+            run_calls(ops.conv_gemm(**cin, w=wf, out=q2, split=(C, C, k2, C, vt2, sp)))
             for a_, b_ in ((q, q2), (k, k2), (vt, vt2)):
                 assert torch.equal(a_.view(torch.int16), b_.view(torch.int16)), "row-panel kernel changed the bits"
     else:
-        w1 = bf(torch.randn(C, C) / math.sqrt(C))
-        b1 = torch.randn(C) * 0.1
-        ref = ln @ w1 + b1
-        wf, cs, cb = packing.fold_layer_norm(w1.t().contiguous(), b1.numpy(), gamma.numpy(), beta.numpy(), d)
-        out = torch.full((M, C), float("nan"), dtype=torch.bfloat16, device=d)
-        wfl = lay(wf, ctm)
-        cons = ops.conv_gemm(a0=tdev, **wfl, out=out, batch=1, h_in=M, w_in=1, c0=C, N=C, bias=cb, ln_in=stats, ln_in_slots=slots,
-                             ln_colsum=cs, **ckw)
+        n_out = 4 * C if mode == "geglu" else C
+        out = g.out((M, n_out), BF16, NAN, "cons.out")
+        cons = ops.conv_gemm(**cin, **lay(wf, ctm, "cons.w"), out=out, **ckw)
         run_calls([prod, cons])
         close(out, ref, atol=2e-2 * float(ref.abs().max()), what=str(case))
         if case.get("csame"):
-            out2 = torch.full_like(out, float("nan"))
-            run_calls(ops.conv_gemm(a0=tdev, w=wf, out=out2, batch=1, h_in=M, w_in=1, c0=C, N=C, bias=cb, ln_in=stats, ln_in_slots=slots,
-                                    ln_colsum=cs))
+            out2 = g.out((M, n_out), BF16, NAN, "cons.out", label="cons.out tile kernel")
+            run_calls(ops.conv_gemm(**cin, w=wf, out=out2))
             assert torch.equal(out.view(torch.int16), out2.view(torch.int16)), "row-panel kernel changed the bits"
+    g.check()
     close(tdev, t, what=str(case) + " producer output")
     # the partials themselves: sum / sum of squares of the stored bf16 values
     tt = tdev.float().cpu()
@@ -518,17 +541,23 @@ def test_conv_gemm_qkv_split(gpu, nq):
     wp = packing.pack_dense_stack([w.numpy() for w in ws], gpu)
     refs = [x @ w for w in ws]
     N = C * (2 + nq)
-    q = torch.full((B * S, C), float("nan"), dtype=torch.bfloat16, device=gpu)
-    k = torch.full((B * S, C), float("nan"), dtype=torch.bfloat16, device=gpu)
-    vt = torch.zeros((B, C, Sp), dtype=torch.bfloat16, device=gpu)
-    call = ops.conv_gemm(a0=x.to(torch.bfloat16).to(gpu), w=wp, out=q, batch=B, h_in=S, w_in=1, c0=Cin, N=N,
-                         split=(C * nq, C, k, C, vt, Sp), out_ld=C)
+    ld = C + 8      # q and k rows inside wider buffers (out_ld, out1_ld > their columns): the gaps hold a canary
+    geo = dict(batch=B, h_in=S, w_in=1, c0=Cin, N=N, out_ld=ld)
+    g = G.Guard(gpu, X.conv_gemm(a0=1, w=1, out=1, split=(C * nq, C, 1, ld, 1, Sp), **geo))
+    # (nq = 0: part 0 has no columns and the header gives it no bytes; the pointer is still passed, as the engine's k | v^T launches do)
+    q = g.out((B * S, C), BF16, NAN, "out" if nq else None, ld=ld, label="q")
+    k = g.out((B * S, C), BF16, NAN, "out1", ld=ld)
+    vt = g.out((B, C, Sp), BF16, NAN, "out2")
+    g.gaps(vt, S)   # columns [S, Sp) of v^T are padding: not written (a canary bit check)
+    call = ops.conv_gemm(a0=g.inp(x.to(BF16), "a0"), w=g.inp(wp, "w"), out=q, split=(C * nq, C, k, ld, vt, Sp), **geo)
     run_calls(call)
     if nq:
         close(q.reshape(B, S, C), refs[0], what="q")
+    else:
+        assert bool(torch.isnan(q.float()).all()), "part 0 has no columns: nothing is written through `out`"
     close(k.reshape(B, S, C), refs[nq], what="k")
     close(vt[:, :, :S].permute(0, 2, 1), refs[nq + 1], what="v^T")
-    assert float(vt[:, :, S:].abs().sum()) == 0.0
+    g.check()
 
 
 @pytest.mark.parametrize("case", [
@@ -570,14 +599,15 @@ def test_conv_direct(gpu, case):
         ref = ref + resid
     outk = case.get("out", "bf16")
     dt = {"bf16": torch.bfloat16, "f32": torch.float32, "u8": torch.uint8}[outk]
-    out = torch.zeros((B, Ho, Wo, cout), dtype=dt, device=gpu)
-    xd = x.to(gpu) if case["in_f32"] else x.to(torch.bfloat16).to(gpu)
-    call = ops.conv_direct(x=xd, w=w.to(gpu), bias=b.to(gpu), out=out, batch=B, in_batch_mod=mod, h_in=H, w_in=W, c_in=cin,
-                           c_out=cout, ksize=ks, stride=stride, in_dtype=ops.OUT_F32 if case["in_f32"] else ops.OUT_BF16,
-                           out_dtype={"bf16": ops.OUT_BF16, "f32": ops.OUT_F32, "u8": ops.OUT_U8}[outk],
-                           act=ops.ACT_SILU if case.get("act") else ops.ACT_NONE, in_scale=scale,
-                           residual=None if resid is None else resid.to(torch.bfloat16).to(gpu))
+    geo = dict(batch=B, in_batch_mod=mod, h_in=H, w_in=W, c_in=cin, c_out=cout, ksize=ks, stride=stride,
+               in_dtype=ops.OUT_F32 if case["in_f32"] else ops.OUT_BF16, out_dtype={"bf16": ops.OUT_BF16, "f32": ops.OUT_F32, "u8": ops.OUT_U8}[outk])
+    g = G.Guard(gpu, X.conv_direct(x=1, w=1, bias=1, residual=resid, out=1, **geo))
+    out = g.out((B, Ho, Wo, cout), dt, 0, "out")
+    xd = g.inp(x if case["in_f32"] else x.to(BF16), "x")
+    call = ops.conv_direct(x=xd, w=g.inp(w, "w"), bias=g.inp(b, "bias"), out=out, act=ops.ACT_SILU if case.get("act") else ops.ACT_NONE, in_scale=scale,
+                           residual=None if resid is None else g.inp(resid.to(BF16), "residual"), **geo)
     run_calls(call)
+    g.check()
     if outk == "u8":
         refu = np.clip(((ref.numpy() + 1.0) * 0.5) * 255.0, 0, 255)
         got = out.cpu().numpy().astype(np.int32)
@@ -623,12 +653,14 @@ def test_group_norm(gpu, case):
     ref = F.group_norm(x.permute(0, 2, 1), 32, gamma, beta, eps=1e-5).permute(0, 2, 1)
     if case["silu"]:
         ref = ref * torch.sigmoid(ref)
-    out = torch.full((B, hw, C), float("nan"), dtype=torch.bfloat16, device=gpu)
-    stats = torch.full((B * 64,), float("nan"), dtype=torch.float32, device=gpu)
-    partials = torch.full((B * ops.GN_MAX_CHUNKS * 64,), float("nan"), dtype=torch.float32, device=gpu)
-    call = ops.group_norm(partials=partials, x0=x0.to(torch.bfloat16).to(gpu), x1=None if x1 is None else x1.to(torch.bfloat16).to(gpu),
-                          gamma=gamma.to(gpu), beta=beta.to(gpu), stats=stats, out=out, batch=B, hw=hw, c0=c0, c1=c1,
-                          silu=case["silu"])
+    geo = dict(batch=B, hw=hw, c0=c0, c1=c1)
+    g = G.Guard(gpu, X.group_norm(x0=1, x1=x1, gamma=1, beta=1, stats=1, partials=1, out=1, **geo))
+    out = g.out((B, hw, C), BF16, NAN, "out")
+    stats = g.out((B, 32, 2), torch.float32, NAN, "stats")                             # exactly batch * 64 floats
+    partials = g.out((B * ops.GN_MAX_CHUNKS, 64), torch.float32, NAN, "partials")
+    gin = dict(partials=partials, x0=g.inp(x0.to(BF16), "x0"), x1=None if x1 is None else g.inp(x1.to(BF16), "x1"), gamma=g.inp(gamma, "gamma"),
+               beta=g.inp(beta, "beta"), stats=stats, silu=case["silu"], **geo)
+    call = ops.group_norm(out=out, **gin)
     try:
         run_calls(call)
     finally:
@@ -639,13 +671,12 @@ def test_group_norm(gpu, case):
     st = stats.cpu().reshape(B, 32, 2)
     np.testing.assert_allclose(st[..., 0].numpy(), xs.mean(-1).numpy(), rtol=1e-3, atol=1e-3)
     np.testing.assert_allclose(st[..., 1].numpy(), (xs.var(-1, unbiased=False) + 1e-5).rsqrt().numpy(), rtol=1e-3)
-    out2 = torch.full_like(out, float("nan"))
-    call2 = ops.group_norm(partials=partials, x0=x0.to(torch.bfloat16).to(gpu), x1=None if x1 is None else x1.to(torch.bfloat16).to(gpu),
-                           gamma=gamma.to(gpu), beta=beta.to(gpu), stats=stats, out=out2, batch=B, hw=hw, c0=c0, c1=c1,
-                           silu=case["silu"])
+    out2 = g.out((B, hw, C), BF16, NAN, "out", label="out again")
+    call2 = ops.group_norm(out=out2, **gin)
     run_calls(call2)
     if case.get("impl", 1) == 1:
         assert torch.equal(out.view(torch.int16), out2.view(torch.int16))   # bit-reproducible run to run
+    g.check()
 
 
 @pytest.mark.parametrize("case", [
@@ -680,10 +711,15 @@ def test_group_norm_cluster(gpu, case, form):
     if case["silu"]:
         ref = ref * torch.sigmoid(ref)
     d = gpu
-    keep = [x0.to(torch.bfloat16).to(d), None if x1 is None else x1.to(torch.bfloat16).to(d), gamma.to(d), beta.to(d)]
-    stats = torch.full((B * 64,), float("nan"), dtype=torch.float32, device=d)
-    partials = torch.full((B * ops.GN_MAX_CHUNKS * 64,), float("nan"), dtype=torch.float32, device=d)
-    sync = torch.zeros(B * ops.GN_SYNC_WORDS_PER_SAMPLE, dtype=torch.int32, device=d)
+    g = G.Guard(d, X.group_norm(x0=1, x1=x1, gamma=1, beta=1, stats=1, partials=1, out=1, sync=1, batch=B, hw=hw, c0=c0, c1=c1))
+    keep = [g.inp(x0.to(BF16), "x0"), None if x1 is None else g.inp(x1.to(BF16), "x1"), g.inp(gamma, "gamma"), g.inp(beta, "beta")]
+    stats = g.out((B, 32, 2), torch.float32, NAN, "stats").view(-1)
+    partials = g.out((B * ops.GN_MAX_CHUNKS, 64), torch.float32, NAN, "partials")
+    # the sync block at exactly batch * MSD_GN_SYNC_WORDS_PER_SAMPLE words, zero when first used; its interior is the kernel's, its bands are not
+    sync = g.out((B * ops.GN_SYNC_WORDS_PER_SAMPLE // 64, 64), torch.int32, 0, "sync").view(-1)
+
+    def fresh(b=B, n=hw, label="out"):
+        return g.out((b, n, C), BF16, NAN, label=f"{label} {len(g.operands)}")
 
     def launch(out, b=B, xs=(keep[0], keep[1]), hw_=hw):
         return ops.group_norm(partials=partials, x0=xs[0], x1=xs[1], gamma=keep[2], beta=keep[3], stats=stats, out=out, batch=b, hw=hw_,
@@ -693,7 +729,7 @@ def test_group_norm_cluster(gpu, case, form):
     lib.msd_set_option(b"gn_cluster", case.get("opt", 256))
     lib.msd_set_option(b"gn_rows", 1 if form == "rows" else 0)
     try:
-        outs = [torch.full((B, hw, C), float("nan"), dtype=torch.bfloat16, device=d) for _ in range(3)]
+        outs = [fresh() for _ in range(3)]
         run_calls([launch(o) for o in outs])                       # three epochs back to back on one stream
         counters = sync.view(-1, 64)[:, 0].clone()
         assert int(counters.max()) > 0, "the cluster form did not run"     # (tickets were taken)
@@ -705,14 +741,14 @@ def test_group_norm_cluster(gpu, case, form):
         np.testing.assert_allclose(st[..., 0].numpy(), xs.mean(-1).numpy(), rtol=1e-3, atol=1e-3)
         np.testing.assert_allclose(st[..., 1].numpy(), (xs.var(-1, unbiased=False) + 1e-5).rsqrt().numpy(), rtol=1e-3)
         # another part count on the same sync block in between (half the pixels -> half the parts where parts follow the size)
-        half = torch.full((B, hw // 2, C), float("nan"), dtype=torch.bfloat16, device=d)
-        x0h = keep[0][:, :hw // 2].contiguous()
-        x1h = None if keep[1] is None else keep[1][:, :hw // 2].contiguous()
-        one = torch.full((1, hw, C), float("nan"), dtype=torch.bfloat16, device=d)
-        again = torch.full((B, hw, C), float("nan"), dtype=torch.bfloat16, device=d)
+        half = fresh(n=hw // 2, label="half")
+        x0h = g.inp(keep[0][:, :hw // 2], label="x0 half")
+        x1h = None if keep[1] is None else g.inp(keep[1][:, :hw // 2], label="x1 half")
+        one = fresh(b=1, label="one")
+        again = fresh()
         last = B - 1   # the LAST sample alone: in a batch of one it uses sample 0's counters, at another epoch than sample 0's
-        x0l = keep[0][last:last + 1].contiguous()
-        x1l = None if keep[1] is None else keep[1][last:last + 1].contiguous()
+        x0l = g.inp(keep[0][last:last + 1], label="x0 last")
+        x1l = None if keep[1] is None else g.inp(keep[1][last:last + 1], label="x1 last")
         run_calls([launch(half, xs=(x0h, x1h), hw_=hw // 2), launch(one, b=1, xs=(x0l, x1l)), launch(again)])
         assert bool(torch.isfinite(half.float()).all())
         assert torch.equal(one[0].view(torch.int16), outs[0][last].view(torch.int16)), "a sample's bits depend on its batch"
@@ -720,14 +756,14 @@ def test_group_norm_cluster(gpu, case, form):
         # the cluster form's workgroups dealt by XCD (norm.hip gn_cluster_kernel xsh, the default) against a group's parts on consecutive
         # workgroup ids: which workgroup works on which (sample, group, part) is placement only
         lib.msd_set_option(b"gn_xmap", 0)
-        plain = torch.full((B, hw, C), float("nan"), dtype=torch.bfloat16, device=d)
+        plain = fresh(label="plain")
         run_calls([launch(plain)])
         assert torch.equal(plain.view(torch.int16), outs[0].view(torch.int16)), "the XCD dealing of the cluster form changed bits"
         # the row-major form's parts shared by CHANNELS among 1 / 2 / 4 workgroups (norm.hip gn_rows_kernel qshift; default: from the launch's
         # size): who computes which of a part's granules is placement only
         for qv in (0, 1, 2):
             lib.msd_set_option(b"gn_rows_q", qv)
-            split = torch.full((B, hw, C), float("nan"), dtype=torch.bfloat16, device=d)
+            split = fresh(label="split")
             st0 = stats.clone()
             stats.fill_(float("nan"))
             run_calls([launch(split)])
@@ -739,6 +775,7 @@ def test_group_norm_cluster(gpu, case, form):
         rows_per_pass = 1024 // (C // 8)     # (eligible: some P in 4 .. 64 leaves a thread at most 6 pixels; the half-size launch counts too)
         fits = any(-(-(-(-n // P)) // rows_per_pass) <= 6 for n in (hw, hw // 2) for P in (4, 8, 16, 32, 64))
         assert rows_ran == (form == "rows" and fits), "which form ran"
+        g.check()
     finally:
         lib.msd_set_option(b"gn_cluster", 256)
         lib.msd_set_option(b"gn_rows", 9216)
@@ -832,33 +869,31 @@ def test_attention_d512(gpu, B, S, spike):
         k = bf(k)
     scale = 1.0 / math.sqrt(d)
     ref = torch.softmax((q @ k.transpose(-1, -2)) * scale, -1) @ v
-    vt = v.permute(0, 2, 1).contiguous().to(torch.bfloat16).to(gpu)
-    out = torch.full((B, S, d), float("nan"), dtype=torch.bfloat16, device=gpu)
-    qd, kd = q.to(torch.bfloat16).to(gpu), k.to(torch.bfloat16).to(gpu)
-    run_calls(ops.attention(q=qd, k=kd, vt=vt, out=out, batch=B, heads=1, head_dim=d,
-                            s=S, t=T, q_ld=d, k_ld=d, vt_ld=T, o_ld=d, scale=scale))
+    # q rows inside a wider buffer and V^T rows with 8 padding keys (q_ld > d, vt_ld > t): both regions hold NaN, then zeros
+    lds = dict(H=1, d=d, q_ld=d + 8, vt_ld=T + 8)
+    a, b = attention_ab(gpu, lambda **o: ops.attention(scale=scale, **o), q, k, v, **lds)
+    out = a[2]
     close(out, ref, rtol=2e-2, atol=1.5e-2 * max(1.0, float(ref.abs().max())), what=f"d512 B={B} S={S}")
-    # with a workspace the key walk is split four ways (t >= 2048, t % 128 == 0) and merged in part order (ABI 9): the fp32 answer
-    # again, and the same bits for a sample whether it runs alone or in a batch (the split follows the key count only)
-    wsf = 4 * B * S * (d + 2)
-    ws = torch.full((wsf,), float("nan"), dtype=torch.float32, device=gpu)
-    out2 = torch.full((B, S, d), float("nan"), dtype=torch.bfloat16, device=gpu)
-    run_calls(ops.attention(q=qd, k=kd, vt=vt, out=out2, batch=B, heads=1, head_dim=d, s=S, t=T, q_ld=d, k_ld=d, vt_ld=T, o_ld=d, scale=scale,
-                            workspace=ws, workspace_floats=wsf))
+    same_bits_whatever_the_padding(a, b, f"d512 B={B} S={S}")
+    # with a workspace (exactly the header's 4 * batch * heads * s * (512 + 2) floats) the key walk is split four ways (t >= 2048,
+    # t % 128 == 0) and merged in part order (ABI 9): the fp32 answer again, and the same bits for a sample whether it runs alone or
+    # in a batch (the split follows the key count only)
+    a2, b2 = attention_ab(gpu, lambda **o: ops.attention(scale=scale, **o), q, k, v, workspace=True, **lds)
+    out2, ws = a2[2], a2[1]["workspace"]
     close(out2, ref, rtol=2e-2, atol=1.5e-2 * max(1.0, float(ref.abs().max())), what=f"d512 split B={B} S={S}")
+    same_bits_whatever_the_padding(a2, b2, f"d512 split B={B} S={S}")
     split_ran = T >= 2048 and T % 128 == 0
     assert bool(torch.isnan(ws).all()) != split_ran, "the key split must run exactly when t >= 2048 and t % 128 == 0"
     if not split_ran:
         assert torch.equal(out.view(torch.int16), out2.view(torch.int16))
     if split_ran and B == 1:
-        q3 = torch.cat([qd, torch.randn(2, S, d, device=gpu).to(torch.bfloat16)])
-        k3 = torch.cat([kd, torch.randn(2, T, d, device=gpu).to(torch.bfloat16)])
-        vt3 = torch.cat([vt, torch.randn(2, d, T, device=gpu).to(torch.bfloat16)])
-        ws3 = torch.empty(3 * wsf, dtype=torch.float32, device=gpu)
-        out3 = torch.full((3, S, d), float("nan"), dtype=torch.bfloat16, device=gpu)
-        run_calls(ops.attention(q=q3, k=k3, vt=vt3, out=out3, batch=3, heads=1, head_dim=d, s=S, t=T, q_ld=d, k_ld=d, vt_ld=T, o_ld=d, scale=scale,
-                                workspace=ws3, workspace_floats=3 * wsf))
+        q3 = torch.cat([q.to(BF16), torch.randn(2, S, d).to(BF16)])
+        k3 = torch.cat([k.to(BF16), torch.randn(2, T, d).to(BF16)])
+        v3 = torch.cat([v.to(BF16), torch.randn(2, T, d).to(BF16)])
+        g3, kw3, out3 = guarded_attention(gpu, q3, k3, v3, poison=True, workspace=True, **lds)
+        run_calls(ops.attention(scale=scale, **kw3))
         assert torch.equal(out3[0].view(torch.int16), out2[0].view(torch.int16)), "the split result of a sample depends on its batch"
+        g3.check()
 
 
 @pytest.mark.parametrize("rows,c", [(256, 320), (100, 640), (64, 1280), (7, 2048)])
@@ -869,9 +904,11 @@ def test_layer_norm(gpu, rows, c):
     x = bf(torch.randn(rows, c) * 3 + 1)
     gamma, beta = torch.randn(c) * 0.2 + 1, torch.randn(c) * 0.2
     ref = F.layer_norm(x, (c,), gamma, beta, eps=1e-5)
-    out = torch.full((rows, c), float("nan"), dtype=torch.bfloat16, device=gpu)
-    run_calls(ops.layer_norm(x=x.to(torch.bfloat16).to(gpu), gamma=gamma.to(gpu), beta=beta.to(gpu), out=out, rows=rows, c=c))
+    g = G.Guard(gpu, X.layer_norm(x=1, gamma=1, beta=1, out=1, rows=rows, c=c))
+    out = g.out((rows, c), BF16, NAN, "out")
+    run_calls(ops.layer_norm(x=g.inp(x.to(BF16), "x"), gamma=g.inp(gamma, "gamma"), beta=g.inp(beta, "beta"), out=out, rows=rows, c=c))
     close(out, ref, atol=2e-2, what=f"ln {rows}x{c}")
+    g.check()
 
 
 def test_attention_partial_round_split(gpu):
@@ -891,19 +928,15 @@ def test_attention_partial_round_split(gpu):
     kh = k.view(B, T, H, d).permute(0, 2, 1, 3)
     vh = v.view(B, T, H, d).permute(0, 2, 1, 3)
     ref = (torch.softmax((qh @ kh.transpose(-1, -2)) * math.log(2.0), -1) @ vh).permute(0, 2, 1, 3).reshape(B, S, C)
-    qd, kd = q.to(torch.bfloat16).to(gpu), k.to(torch.bfloat16).to(gpu)
-    vt = v.permute(0, 2, 1).contiguous().to(torch.bfloat16).to(gpu)
     outs = []
     for qf in (0, 4):   # automatic (splits the partial round) / 256 queries forced (one launch)
-        out = torch.full((B, S, C), float("nan"), dtype=torch.bfloat16, device=gpu)
-        call = ops.attention(q=qd, k=kd, vt=vt, out=out, batch=B, heads=H, head_dim=d, s=S, t=T, q_ld=C, k_ld=C, vt_ld=T, o_ld=C,
-                             scale=scale, q_prescaled=True)
         _lib.load().msd_set_option(b"attn_qf", qf)
-        try:
-            run_calls(call)
+        try:   # q inside a 3C-wide buffer, 8 padding keys behind V^T's rows: NaN there, then zeros
+            a, b = attention_ab(gpu, lambda **o: ops.attention(scale=scale, q_prescaled=True, **o), q, k, v, H=H, d=d, q_ld=3 * C, vt_ld=T + 8)
         finally:
             _lib.load().msd_set_option(b"attn_qf", 0)
-        outs.append(out)
+        same_bits_whatever_the_padding(a, b, f"partial-round split qf={qf}")
+        outs.append(a[2])
     close(outs[0], ref, rtol=2e-2, atol=1.5e-2 * max(1.0, float(ref.abs().max())), what="partial-round split")
     assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16)), "the two-launch form changed the bits"
 
@@ -975,25 +1008,19 @@ def test_attention(gpu, case, qf, presc, form):
     kh = k.view(B, T, H, d).permute(0, 2, 1, 3)
     vh = v.view(B, T, H, d).permute(0, 2, 1, 3)
     ref = (torch.softmax((qh @ kh.transpose(-1, -2)) * score_scale, -1) @ vh).permute(0, 2, 1, 3).reshape(B, S, C)
-    # q lives inside a wider fused buffer (leading dimension 3C) like the QKV GEMM output would
-    qbuf = torch.zeros(B, S, 3 * C, dtype=torch.bfloat16, device=gpu)
-    qbuf[:, :, C:2 * C] = q.to(torch.bfloat16).to(gpu)
-    vt = torch.zeros(B, C, Tp, dtype=torch.bfloat16, device=gpu)
-    vt[:, :, :T] = v.permute(0, 2, 1).to(torch.bfloat16).to(gpu)
-    out = torch.full((B, S, C), float("nan"), dtype=torch.bfloat16, device=gpu)
-    kd = k.to(torch.bfloat16).to(gpu)
-    call = ops.attention(q=qbuf.data_ptr() + 2 * C, k=kd, vt=vt, out=out, batch=B, heads=H,
-                         head_dim=d, s=S, t=T, q_ld=3 * C, k_ld=C, vt_ld=Tp, o_ld=C, scale=scale, q_prescaled=presc)
+    # q lives inside a wider fused buffer (leading dimension 3C) like the QKV GEMM output would; the rest of that buffer and V^T's
+    # padding keys [T, Tp) hold NaN (what the arena's previous tenant may have left), then zeros: the same bits
     _lib.load().msd_set_option(b"attn_qf", qf)
     _lib.load().msd_set_option(b"attn_form", form)
     try:
-        run_calls(call)
+        a, b = attention_ab(gpu, lambda **o: ops.attention(scale=scale, q_prescaled=presc, **o), q, k, v, H=H, d=d, q_ld=3 * C, vt_ld=Tp)
     finally:
         _lib.load().msd_set_option(b"attn_qf", 0)
         _lib.load().msd_set_option(b"attn_form", 2)
     # P is rounded to bf16 before the PV product (relative 2^-9 per term): the error scales with the
     # magnitude of the summed terms, so the absolute floor is 1.5e-2 of max(1, max|O|)
-    close(out, ref, rtol=2e-2, atol=1.5e-2 * max(1.0, float(ref.abs().max())), what=f"{case} qf={qf} presc={presc} form={form}")
+    close(a[2], ref, rtol=2e-2, atol=1.5e-2 * max(1.0, float(ref.abs().max())), what=f"{case} qf={qf} presc={presc} form={form}")
+    same_bits_whatever_the_padding(a, b, f"{case} qf={qf} presc={presc} form={form}")
 
 
 @pytest.mark.parametrize("case", [
@@ -1038,28 +1065,33 @@ def test_cross_attention_q(gpu, case, layout, nw):
     # row-moment partials as a producing GEMM would leave them: (sum, sum of squares) of the stored bf16 row per column group
     edges = [round(i * C / slots) for i in range(slots + 1)]
     st = torch.stack([torch.stack([x[:, a:b_].sum(1), (x[:, a:b_] ** 2).sum(1)], -1) for a, b_ in zip(edges[:-1], edges[1:])], 1)
-    stats = st.to(torch.float32).contiguous().to(dev)
-    xd, kd = x.to(torch.bfloat16).to(dev), k.to(torch.bfloat16).to(dev)
-    vt = torch.full((B, C, Tp), float("nan"), dtype=torch.bfloat16, device=dev)   # (padding keys hold garbage, as in the arena)
-    vt[:, :, :T] = v.permute(0, 2, 1).to(torch.bfloat16).to(dev)
-    out = torch.full((B * S, C), float("nan"), dtype=torch.bfloat16, device=dev)
+    geo = dict(batch=B, heads=H, head_dim=d, s=S, t=T, k_ld=C, vt_ld=Tp, o_ld=C, ln_in_slots=slots)
+    g = G.Guard(dev, X.cross_attention_q(x=1, ln_in=1, wq=1, ln_colsum=1, bias=1, k=1, vt=1, out=1, **geo))
+    stats = g.inp(st.to(torch.float32), "ln_in")
+    xd, kd = g.inp(x.to(BF16), "x"), g.inp(k.to(BF16), "k")
+    wdev, cs, cb = g.inp(wdev, "wq"), g.inp(cs, "ln_colsum"), g.inp(cb, "bias")
+    vtf = torch.zeros(B, C, Tp, dtype=BF16)
+    vtf[:, :, :T] = v.permute(0, 2, 1).to(BF16)
+    vt = g.inp(vtf, "vt")
+    g.gaps(vt, T)                                          # (padding keys hold NaN: garbage, as in the arena)
+    out = g.out((B * S, C), BF16, NAN, "out")
     _lib.load().msd_set_option(b"xattn_nw", nw)
     try:
-        run_calls(ops.cross_attention_q(x=xd, ln_in=stats, ln_in_slots=slots, wq=wdev, ln_colsum=cs, bias=cb, k=kd, vt=vt, out=out, batch=B,
-                                        heads=H, head_dim=d, s=S, t=T, k_ld=C, vt_ld=Tp, o_ld=C, w_layout=layout))
+        run_calls(ops.cross_attention_q(x=xd, ln_in=stats, wq=wdev, ln_colsum=cs, bias=cb, k=kd, vt=vt, out=out, w_layout=layout, **geo))
     finally:
         _lib.load().msd_set_option(b"xattn_nw", 0)
     tol = dict(rtol=2e-2, atol=1.5e-2 * max(1.0, float(ref.abs().max())))
     close(out, ref, what=f"{case} fused", **tol)
     # the two launches it replaces
-    q2 = torch.full((B * S, C), float("nan"), dtype=torch.bfloat16, device=dev)
-    out2 = torch.full_like(out, float("nan"))
+    q2 = g.out((B * S, C), BF16, NAN, label="q of the two launches")
+    out2 = g.out((B * S, C), BF16, NAN, "out", label="out of the two launches")
     run_calls([ops.conv_gemm(a0=xd, w=wdev, out=q2, batch=1, h_in=B * S, w_in=1, c0=C, N=C, bias=cb, ln_in=stats, ln_in_slots=slots,
                              ln_colsum=cs, w_layout=layout),
                ops.attention(q=q2, k=kd, vt=vt, out=out2, batch=B, heads=H, head_dim=d, s=S, t=T, q_ld=C, k_ld=C, vt_ld=Tp, o_ld=C,
                              scale=d ** -0.5, q_prescaled=True)])
     close(out2, ref, what=f"{case} two launches", **tol)
     close(out, out2.float().cpu(), what=f"{case} fused vs two launches", **tol)
+    g.check()
 
 
 def test_softmax_rows(gpu):
@@ -1070,9 +1102,13 @@ def test_softmax_rows(gpu):
     x = torch.randn(rows, cols) * 20
     scale = 1 / math.sqrt(512)
     ref = torch.softmax(x * scale, -1)
-    out = torch.zeros(rows, cols, dtype=torch.bfloat16, device=gpu)
-    run_calls(ops.softmax_rows(x=x.to(gpu), out=out, rows=rows, cols=cols, ld_in=cols, ld_out=cols, scale=scale))
+    ld_in, ld_out = cols + 8, cols + 16     # rows of wider buffers: NaN between the input rows, a canary between the output rows
+    geo = dict(rows=rows, cols=cols, ld_in=ld_in, ld_out=ld_out)
+    g = G.Guard(gpu, X.softmax_rows(x=1, out=1, **geo))
+    out = g.out((rows, cols), BF16, 0, "out", ld=ld_out)
+    run_calls(ops.softmax_rows(x=g.inp(x, "x", ld=ld_in), out=out, scale=scale, **geo))
     close(out, ref, rtol=1e-2, atol=1e-6, what="softmax")
+    g.check()
 
 
 @pytest.mark.parametrize("guidance,rescale", [(7.5, 0.7), (7.5, 0.0), (0.0, 0.0)])
@@ -1089,12 +1125,14 @@ def test_cfg_step(gpu, guidance, rescale, advance, hw):
     B, n, steps = 3, hw * hw * 4, 5
     sch = Scheduler()
     sch.set_timesteps(steps)
-    coef = torch.from_numpy(sch.coefficient_table()).to(gpu)
+    geo = dict(batch=B, n=n, num_steps=steps, guidance=guidance, guidance_rescale=rescale, advance=advance)
+    g = G.Guard(gpu, X.cfg_step(eps=1, latent=1, coef=1, step_ptr=1, **geo))
+    coef = g.inp(torch.from_numpy(sch.coefficient_table()), "coef")
     osch = O.OracleScheduler()
     osch.set_timesteps(steps)
     lat = rng.standard_normal((B, hw, hw, 4)).astype(np.float32)
-    lat_d = torch.from_numpy(lat.reshape(B, n).copy()).to(gpu)
-    step = torch.zeros(2, dtype=torch.int32, device=gpu)   # {step, ticket}
+    lat_d = g.inp(torch.from_numpy(lat.reshape(B, n).copy()), "latent")
+    step = g.inp(torch.zeros(2 if advance == 2 else 1, dtype=torch.int32), "step_ptr")   # {step, ticket}: the ticket only with advance = 2
     ref = lat.astype(np.float64)
     for i, t in enumerate(osch.timesteps):
         u = rng.standard_normal((B, hw, hw, 4)).astype(np.float32)
@@ -1103,17 +1141,17 @@ def test_cfg_step(gpu, guidance, rescale, advance, hw):
             e = u + guidance * (c - u)
             if rescale > 0:
                 e = O.rescale_noise_cfg(e, c, rescale)
-            eps_d = torch.from_numpy(np.concatenate([u, c]).reshape(2 * B, n)).to(gpu)
+            eps_d = g.inp(torch.from_numpy(np.concatenate([u, c]).reshape(2 * B, n)), "eps", label=f"eps of step {i}")
         else:
             e = c
-            eps_d = torch.from_numpy(c.reshape(B, n)).to(gpu)
+            eps_d = g.inp(torch.from_numpy(c.reshape(B, n)), "eps", label=f"eps of step {i}")
         ref = osch.step(e, int(t), ref)
-        run_calls(ops.cfg_step(eps=eps_d, latent=lat_d, coef=coef, step_ptr=step, batch=B, n=n, num_steps=steps,
-                               guidance=guidance, guidance_rescale=rescale, advance=advance))
+        run_calls(ops.cfg_step(eps=eps_d, latent=lat_d, coef=coef, step_ptr=step, **geo))
         got = lat_d.cpu().numpy().reshape(B, hw, hw, 4)
         # fp32 device math vs the reference's float64 numpy path
         np.testing.assert_allclose(got, ref, rtol=2e-4, atol=2e-4 * np.abs(ref).max(), err_msg=f"step {i}")
-        assert step.tolist() == [i + 1, 0]
+        assert step.tolist() == [i + 1, 0][:step.numel()]
+    g.check()
 
 
 def test_elementwise(gpu):
@@ -1121,19 +1159,33 @@ def test_elementwise(gpu):
 
     torch.manual_seed(10)
     a, b = bf(torch.randn(4096)), bf(torch.randn(4096))
-    out = torch.zeros(4096, dtype=torch.bfloat16, device=gpu)
-    run_calls(ops.add_bf16(a=a.to(torch.bfloat16).to(gpu), b=b.to(torch.bfloat16).to(gpu), out=out, n=4096))
+    g = G.Guard(gpu)
+    g.bind("add.", X.add_bf16(n=4096))
+    g.bind("f2b.", X.cast_f32_to_bf16(n=1000))
+    g.bind("b2f.", X.cast_bf16_to_f32(n=1000))
+    g.bind("zero.", X.memset_zero(nbytes=4096))
+    out = g.out((4096,), BF16, 0, "add.out")
+    run_calls(ops.add_bf16(a=g.inp(a.to(BF16), "add.a"), b=g.inp(b.to(BF16), "add.b"), out=out, n=4096))
     assert torch.equal(out.cpu(), (a + b).to(torch.bfloat16))
     x = torch.randn(1000)
-    o = torch.zeros(1000, dtype=torch.bfloat16, device=gpu)
-    run_calls(ops.cast_f32_to_bf16(x=x.to(gpu), out=o, n=1000))
+    o = g.out((1000,), BF16, 0, "f2b.out")
+    run_calls(ops.cast_f32_to_bf16(x=g.inp(x, "f2b.x"), out=o, n=1000))
     assert torch.equal(o.cpu(), x.to(torch.bfloat16))
-    o2 = torch.zeros(1000, dtype=torch.float32, device=gpu)
-    run_calls(ops.cast_bf16_to_f32(x=o, out=o2, n=1000))
+    o2 = g.out((1000,), torch.float32, 0, "b2f.out")
+    run_calls(ops.cast_bf16_to_f32(x=g.same(o, "b2f.x"), out=o2, n=1000))
     assert torch.equal(o2.cpu(), x.to(torch.bfloat16).float())
-    z = torch.ones(1024, dtype=torch.float32, device=gpu)
+    z = g.out((1024,), torch.float32, 1.0, "zero.ptr")
     run_calls(ops.memset_zero(ptr=z, nbytes=4096))
     assert float(z.abs().sum()) == 0
+    # msd_add_f32_bf16, separately and in place (out == a, as the header allows)
+    g.bind("mix.", X.add_f32_bf16(n=4096))
+    c = torch.randn(4096)
+    for in_place in (False, True):
+        ad = g.inp(a.to(BF16), "mix.a", label=f"mix.a in_place={in_place}")
+        od = ad if in_place else g.out((4096,), BF16, 0, "mix.out")
+        run_calls(ops.add_f32_bf16(a=ad, b=g.inp(c, "mix.b", label=f"mix.b in_place={in_place}"), out=od, n=4096))
+        assert torch.equal(od.cpu(), (a + c).to(torch.bfloat16))
+    g.check()
 
 
 def test_argument_errors(gpu):
@@ -1166,12 +1218,16 @@ def test_replicate(gpu):
     from minsdtf_amd import _lib, ops
 
     torch.manual_seed(5)
-    src = torch.randint(0, 2 ** 15, (3, 8, 8, 320), dtype=torch.int16, device=gpu)
+    src = torch.randint(0, 2 ** 15, (3, 8, 8, 320), dtype=torch.int16)
     nbytes = src.numel() * 2
-    dst = torch.full((3 * 3, 8, 8, 320), -1, dtype=torch.int16, device=gpu)
+    g = G.Guard(gpu)
+    g.bind("x3.", X.replicate(src=1, dst=1, nbytes=nbytes, copies=3))
+    g.bind("x2.", X.replicate(src=1, dst=1, nbytes=nbytes, copies=2))
+    src = g.inp(src, "x3.src")
+    dst = g.out((3 * 3, 8, 8, 320), torch.int16, -1, "x3.dst")
     run_calls(ops.replicate(src=src, dst=dst, nbytes=nbytes, copies=3))
     assert torch.equal(dst, src.repeat(3, 1, 1, 1))
-    wide = torch.full((2 * 3, 8, 8, 320), -1, dtype=torch.int16, device=gpu)
+    wide = g.out((2 * 3, 8, 8, 320), torch.int16, -1, "x2.dst")      # in place: the source is the head of the destination
     wide[:3] = src
     run_calls(ops.replicate(src=wide, dst=wide, nbytes=nbytes, copies=2))
     assert torch.equal(wide, src.repeat(2, 1, 1, 1))
@@ -1181,6 +1237,7 @@ def test_replicate(gpu):
     assert lib.msd_replicate(src.data_ptr(), dst.data_ptr(), nbytes + 8, 3, st) == -1       # not whole 16-byte vectors
     assert lib.msd_replicate(src.data_ptr(), dst.data_ptr(), nbytes, 0, st) == -1
     torch.cuda.synchronize()
+    g.check()
 
 
 @pytest.mark.parametrize("hw,C,sync_on,rows", [(64, 1280, False, 0), (1024, 640, True, 0), (4096, 320, True, 0), (4096, 320, True, 4096), (16384, 128, False, 0)])
@@ -1227,14 +1284,12 @@ def test_attention_of_zero_queries_is_the_mean_of_v(gpu, d, S, T, presc):
     C = H * d
     Tp = (T + 7) // 8 * 8
     dev = gpu
-    q = torch.zeros(B, S, C, dtype=torch.bfloat16, device=dev)
-    k = (bf(torch.randn(B, T, C)) * 30.0).to(torch.bfloat16).to(dev)
+    q = torch.zeros(B, S, C)
+    k = bf(torch.randn(B, T, C)) * 30.0
     v = bf(torch.randn(B, T, C))
-    vt = torch.full((B, C, Tp), float("nan"), dtype=torch.bfloat16, device=dev)
-    vt[:, :, :T] = v.permute(0, 2, 1).to(torch.bfloat16).to(dev)
-    out = torch.full((B, S, C), float("nan"), dtype=torch.bfloat16, device=dev)
-    run_calls(ops.attention(q=q, k=k, vt=vt, out=out, batch=B, heads=H, head_dim=d, s=S, t=T, q_ld=C, k_ld=C, vt_ld=Tp, o_ld=C,
-                            scale=d ** -0.5, q_prescaled=presc))
+    # the zero queries as rows of a 3C-wide buffer whose other columns hold NaN, like V^T's padding keys; then zeros in both
+    a, b = attention_ab(dev, lambda **o: ops.attention(scale=d ** -0.5, q_prescaled=presc, **o), q, k, v, H=H, d=d, q_ld=3 * C, vt_ld=Tp)
     ref = v.mean(dim=1, keepdim=True).expand(B, S, C)
     # (P = 1 exactly, so the only rounding is the fp32 sum over the keys and the bf16 store)
-    close(out, ref, rtol=1e-2, atol=4e-3, what=f"d={d} S={S} T={T} presc={presc}")
+    close(a[2], ref, rtol=1e-2, atol=4e-3, what=f"d={d} S={S} T={T} presc={presc}")
+    same_bits_whatever_the_padding(a, b, f"d={d} S={S} T={T} presc={presc}")

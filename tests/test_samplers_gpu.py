@@ -53,12 +53,18 @@ def test_sampler_step(gpu, extra, guidance, rescale, advance, hw):
     rng = np.random.default_rng(19)
     B, n, steps = 3, hw * hw * 4, 5
     name = "dpmpp_2m" if extra == "plain" else "dpmpp_2m_sde_karras"
+    import _extents as X
+    import _guard as G
+
     tab = _rows(name, steps)
-    coef = torch.from_numpy(tab.astype(np.float32)).to(gpu)
+    geo = dict(batch=B, n=n, num_steps=steps, guidance=guidance, guidance_rescale=rescale, advance=advance)
+    more = dict(step_noise=1, inpaint_init=1, inpaint_noise=1, inpaint_mask=1) if extra != "plain" else {}
+    g = G.Guard(gpu, X.sampler_step(eps=1, latent=1, coef=1, step_ptr=1, denoised_prev=1, **more, **geo))   # every operand between guard bands
+    coef = g.inp(torch.from_numpy(tab.astype(np.float32)), "coef")
     lat = rng.standard_normal((B, n)).astype(np.float32)
-    lat_d = torch.from_numpy(lat.copy()).to(gpu)
-    prev_d = torch.full((B, n), float("nan"), dtype=torch.float32, device=gpu)
-    step = torch.zeros(2, dtype=torch.int32, device=gpu)
+    lat_d = g.inp(torch.from_numpy(lat.copy()), "latent")
+    prev_d = g.out((B, n), torch.float32, float("nan"), "denoised_prev")
+    step = g.inp(torch.zeros(2 if advance == 2 else 1, dtype=torch.int32), "step_ptr")   # {step, ticket}: the ticket only with advance = 2
     kw = {}
     z = ip_init = ip_noise = ip_mask = None
     if extra != "plain":
@@ -66,8 +72,8 @@ def test_sampler_step(gpu, extra, guidance, rescale, advance, hw):
         ip_init = rng.standard_normal(n).astype(np.float32)
         ip_noise = rng.standard_normal((B, n)).astype(np.float32)
         ip_mask = np.repeat((rng.random((hw * hw, 1)) > 0.4).astype(np.float32), 4, axis=1).reshape(-1)
-        kw = dict(step_noise=torch.from_numpy(z).to(gpu), inpaint_init=torch.from_numpy(ip_init).to(gpu),
-                  inpaint_noise=torch.from_numpy(ip_noise).to(gpu), inpaint_mask=torch.from_numpy(ip_mask).to(gpu))
+        kw = dict(step_noise=g.inp(torch.from_numpy(z), "step_noise"), inpaint_init=g.inp(torch.from_numpy(ip_init), "inpaint_init"),
+                  inpaint_noise=g.inp(torch.from_numpy(ip_noise), "inpaint_noise"), inpaint_mask=g.inp(torch.from_numpy(ip_mask), "inpaint_mask"))
     ref, P = lat.astype(np.float64), None
     for i in range(steps):
         u = rng.standard_normal((B, n)).astype(np.float32)
@@ -76,10 +82,10 @@ def test_sampler_step(gpu, extra, guidance, rescale, advance, hw):
             e = u + guidance * (c - u)
             if rescale > 0:
                 e = O.rescale_noise_cfg(e, c, rescale)
-            eps_d = torch.from_numpy(np.concatenate([u, c])).to(gpu)
+            eps_d = g.inp(torch.from_numpy(np.concatenate([u, c])), "eps", label=f"eps of step {i}")
         else:
             e = c
-            eps_d = torch.from_numpy(c).to(gpu)
+            eps_d = g.inp(torch.from_numpy(c), "eps", label=f"eps of step {i}")
         a, s, cx, cd, cp, cz = tab[i, :6].astype(np.float32).astype(np.float64)
         D = (ref - s * e) / a
         x = cx * ref + cd * D + (cp * P if cp != 0 else 0.0) + (cz * z[i] if z is not None else 0.0)
@@ -87,12 +93,12 @@ def test_sampler_step(gpu, extra, guidance, rescale, advance, hw):
             org = a * ip_init[None] + s * ip_noise
             x = org * (1.0 - ip_mask[None]) + x * ip_mask[None]
         ref, P = x, D
-        run_calls(ops.sampler_step(eps=eps_d, latent=lat_d, coef=coef, step_ptr=step, denoised_prev=prev_d, batch=B, n=n,
-                                   num_steps=steps, guidance=guidance, guidance_rescale=rescale, advance=advance, **kw))
+        run_calls(ops.sampler_step(eps=eps_d, latent=lat_d, coef=coef, step_ptr=step, denoised_prev=prev_d, **geo, **kw))
         got = lat_d.cpu().numpy()
         np.testing.assert_allclose(got, ref, rtol=2e-4, atol=2e-4 * np.abs(ref).max(), err_msg=f"step {i}")
         np.testing.assert_allclose(prev_d.cpu().numpy(), D, rtol=2e-4, atol=2e-4 * np.abs(D).max(), err_msg=f"P after step {i}")
-        assert step.tolist() == [i + 1, 0]
+        assert step.tolist() == [i + 1, 0][:step.numel()]
+    g.check()
 
 
 def test_sampler_step_argument_errors(gpu):

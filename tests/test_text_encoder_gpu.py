@@ -7,7 +7,10 @@ import numpy as np
 import pytest
 import torch
 
+import _extents as X
+import _guard as G
 from conftest import run_calls
+from test_ops_gpu import attention_ab, same_bits_whatever_the_padding
 
 pytestmark = pytest.mark.gpu
 PSNR_MIN = 40.0
@@ -29,18 +32,22 @@ def test_causal_attention_d64(gpu, B, S):
     mask = torch.triu(torch.full((S, S), float("-inf")), diagonal=1)
     ref = (torch.softmax(qh @ kh.transpose(-1, -2) * d ** -0.5 + mask, -1) @ vh).permute(0, 2, 1, 3).reshape(B, S, H * d)
     Sp = (S + 7) // 8 * 8
-    vt = torch.full((B, H * d, Sp), float("nan"), dtype=torch.bfloat16, device=gpu)   # padding columns are unspecified
-    vt[:, :, :S] = v.permute(0, 2, 1).to(torch.bfloat16).to(gpu)
-    out = torch.full((B, S, H * d), float("nan"), dtype=torch.bfloat16, device=gpu)
-    run_calls(ops.attention(q=q.to(torch.bfloat16).to(gpu), k=k.to(torch.bfloat16).to(gpu), vt=vt, out=out, batch=B, heads=H,
-                            head_dim=d, s=S, t=S, q_ld=H * d, k_ld=H * d, vt_ld=Sp, o_ld=H * d, scale=d ** -0.5, causal=True))
+    # every operand between guard bands; V^T's padding columns [S, Sp) and the columns of the 3C-wide q buffer outside the head block are
+    # unspecified: NaN, then zeros - the same bits
+    lds = dict(H=H, d=d, q_ld=3 * H * d, vt_ld=Sp)
+    a, b = attention_ab(gpu, lambda **o: ops.attention(scale=d ** -0.5, causal=True, **o), q, k, v, **lds)
+    out = a[2]
+    assert bool(torch.isfinite(out.float()).all())
     err = (out.float().cpu() - ref).abs().max()
     assert float(err) <= 2e-2 * float(ref.abs().max()) + 1e-3, float(err)
+    same_bits_whatever_the_padding(a, b, "causal")
     # without the mask the same call is plain attention
-    run_calls(ops.attention(q=q.to(torch.bfloat16).to(gpu), k=k.to(torch.bfloat16).to(gpu), vt=vt, out=out, batch=B, heads=H,
-                            head_dim=d, s=S, t=S, q_ld=H * d, k_ld=H * d, vt_ld=Sp, o_ld=H * d, scale=d ** -0.5))
+    a, b = attention_ab(gpu, lambda **o: ops.attention(scale=d ** -0.5, **o), q, k, v, **lds)
+    out = a[2]
+    assert bool(torch.isfinite(out.float()).all())
     ref2 = (torch.softmax(qh @ kh.transpose(-1, -2) * d ** -0.5, -1) @ vh).permute(0, 2, 1, 3).reshape(B, S, H * d)
     assert float((out.float().cpu() - ref2).abs().max()) <= 2e-2 * float(ref2.abs().max()) + 1e-3
+    same_bits_whatever_the_padding(a, b, "plain")
 
 
 def test_quick_gelu_epilogue(gpu):
@@ -53,22 +60,27 @@ def test_quick_gelu_epilogue(gpu):
     b = torch.randn(N) * 0.3
     h = x @ w + b
     ref = h * torch.sigmoid(1.702 * h)
-    out = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=gpu)
-    run_calls(ops.conv_gemm(a0=x.to(torch.bfloat16).to(gpu), w=packing.pack_dense(w.numpy(), gpu), out=out, batch=2, h_in=77, w_in=1,
-                            c0=C, N=N, bias=b.to(gpu), act=ops.ACT_QUICK_GELU))
+    geo = dict(batch=2, h_in=77, w_in=1, c0=C, N=N, act=ops.ACT_QUICK_GELU)
+    g = G.Guard(gpu, X.conv_gemm(a0=1, w=1, out=1, bias=1, **geo))
+    out = g.out((M, N), torch.bfloat16, float("nan"), "out")
+    run_calls(ops.conv_gemm(a0=g.inp(x.to(torch.bfloat16), "a0"), w=g.inp(packing.pack_dense(w.numpy(), gpu), "w"), out=out,
+                            bias=g.inp(b, "bias"), **geo))
+    assert bool(torch.isfinite(out.float()).all())
     assert float((out.float().cpu() - ref).abs().max()) <= 1e-2 * float(ref.abs().max()) + 1e-2
+    g.check()
 
 
 def test_embedding_sum(gpu):
     from minsdtf_amd import ops
 
     rng = np.random.default_rng(13)
-    tok_t = torch.from_numpy(rng.standard_normal((1000, 768)).astype(np.float32)).to(gpu)
-    pos_t = torch.from_numpy(rng.standard_normal((77, 768)).astype(np.float32)).to(gpu)
-    tokens = torch.from_numpy(rng.integers(0, 1000, (2, 77)).astype(np.int32)).to(gpu)
-    positions = torch.arange(77, dtype=torch.int32, device=gpu).repeat(2, 1)
-    out = torch.zeros(2 * 77, 768, dtype=torch.bfloat16, device=gpu)
-    status = torch.zeros(1, dtype=torch.int32, device=gpu)
+    g = G.Guard(gpu, X.embedding_sum(tokens=1, positions=1, tok_table=1, pos_table=1, out=1, status=1, rows=154, dim=768, vocab=1000, max_len=77))
+    tok_t = g.inp(torch.from_numpy(rng.standard_normal((1000, 768)).astype(np.float32)), "tok_table")
+    pos_t = g.inp(torch.from_numpy(rng.standard_normal((77, 768)).astype(np.float32)), "pos_table")
+    tokens = g.inp(torch.from_numpy(rng.integers(0, 1000, (2, 77)).astype(np.int32)), "tokens")
+    positions = g.inp(torch.arange(77, dtype=torch.int32).repeat(2, 1), "positions")
+    out = g.out((2 * 77, 768), torch.bfloat16, 0, "out")
+    status = g.inp(torch.zeros(1, dtype=torch.int32), "status")
     run_calls(ops.embedding_sum(tokens=tokens, positions=positions, tok_table=tok_t, pos_table=pos_t, out=out, rows=154, dim=768,
                                 vocab=1000, max_len=77, status=status))
     ref = (tok_t[tokens.long().view(-1)] + pos_t[positions.long().view(-1)]).to(torch.bfloat16)
@@ -77,6 +89,7 @@ def test_embedding_sum(gpu):
     run_calls(ops.embedding_sum(tokens=tokens, positions=positions, tok_table=tok_t, pos_table=pos_t, out=out, rows=154, dim=768,
                                 vocab=1000, max_len=77, status=status))
     assert int(status.item()) == 1
+    g.check()
 
 
 @pytest.mark.parametrize("clip_skip,B", [(-1, 1), (-2, 2)])
