@@ -616,6 +616,52 @@ typedef struct MsdAttentionIdentity {
 
 MSD_API int msd_attention_identity(const MsdAttentionIdentity* p, msd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * msd_region_attention — regional prompting inside cross-attention ("attention couple"; minsdtf_amd/regions.py; DESIGN.md
+ * §4.10): the conditional rows of an attn2 layer attend to every region's text context and mix the results per query, so the
+ * UNet runs the plain job's rows whatever the number of regions.  An addition to ABI 12: nothing else changed.
+ *
+ *   q:   bf16 [batch][s][q_ld], head h at columns [h * d, (h + 1) * d), d = head_dim; q MUST carry scale * log2(e) (the
+ *        q_prescaled form of msd_attention, as msd_cross_attention_q requires of its weights); q_ld >= heads * d
+ *   k:   bf16 [regions * batch][t][k_ld], row r * batch + b (region-major, like msd_region_combine); k_ld >= heads * d
+ *   vt:  bf16 [regions * batch][heads * d][vt_ld], key index contiguous; vt_ld % 8 == 0, vt_ld >= t; columns >= t are
+ *        padding, whatever they hold (NaN included) never reaches out
+ *   w:   fp32 [regions][w_ld]; w[r][i] = the weight of region r at query i, i < s; >= 0 and normalised by the host
+ *        (regions.Resolved.level_weights), shared by the batch and the heads - the kernel does not divide by their sum
+ *   out: bf16 [batch][s][o_ld]; columns >= heads * d of a row are not written
+ *
+ * head_dim is 40, 80 or 160; 1 <= t <= 96 (all keys are one tile); 1 <= regions <= MSD_REGION_MAX.
+ *
+ * Per sample, head, query i and channel c, the regions in ascending order (pinned; fp32):
+ *   m_r = max_key q.k_r[key]        P_r[key] = bf16(exp2(q.k_r[key] - m_r))        l_r = sum_key P_r[key]
+ *   O_r = (sum_key P_r[key] * v_r[key][c]) * (1 / l_r)
+ *   acc = w[r][i] * O_r                      at the first region with w[r][i] > 0
+ *   acc = fma(w[r][i], O_r, acc)             at each later region with w[r][i] > 0
+ *   out = bf16(acc)                          (0 where no region is positive)
+ * A region whose weight at a query is exactly 0 is NOT accumulated for that query: acc keeps its bits.  So a query that one
+ * region covers alone (weight exactly 1.0, the others 0.0) gets that region's attention bit for bit - what a launch with that
+ * region alone and w = 1 writes - and the K / V^T of a region that is nowhere positive may hold anything, NaN included.  A
+ * workgroup (64 queries of one sample and head) skips a region whose weights are 0 at all of its queries without reading its
+ * K / V^T; by the rule above that changes no bit.
+ *
+ * Both products run on MFMAs with K / V^T staged in LDS per region; plain vector loads and stores, no atomics; nothing couples
+ * two samples, so a sample's bits do not depend on its batch.  Checked on the host, without a device: q / k / vt / w / out
+ * non-NULL and 16-byte aligned; head_dim, t and regions in range; batch and heads in 1 .. 65535; s >= 1; w_ld >= s; q_ld, k_ld,
+ * vt_ld and o_ld multiples of 8; q_ld, k_ld, o_ld >= heads * head_dim; vt_ld >= t; fewer than 2^31 workgroups; the extent of
+ * out apart from the extent of every input.  Argument errors return MSD_E_ARG without launching.  Nothing is allocated; the
+ * launch is stream-ordered and capturable. */
+typedef struct MsdRegionAttention {
+    const void* q;
+    const void* k;
+    const void* vt;
+    const float* w;
+    void* out;
+    int32_t batch, heads, head_dim, s, t, regions;
+    int32_t q_ld, k_ld, vt_ld, w_ld, o_ld;
+} MsdRegionAttention;
+
+MSD_API int msd_region_attention(const MsdRegionAttention* p, msd_stream_t stream);
+
 /* msd_add_bf16 — out = a + b elementwise on bf16. n % 8 == 0. */
 MSD_API int msd_add_bf16(const void* a, const void* b, void* out, int64_t n, msd_stream_t stream);
 /* msd_add_f32_bf16 — out = bf16(a + b), a / out bf16, b fp32, summed in fp32 (may run in place, out == a).  The ControlNet

@@ -149,6 +149,15 @@ class MsdRegionCombine(C.Structure):
     ]
 
 
+class MsdRegionAttention(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("vt", C.c_void_p), ("w", C.c_void_p), ("out", C.c_void_p),
+        ("batch", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("s", C.c_int32), ("t", C.c_int32),
+        ("regions", C.c_int32), ("q_ld", C.c_int32), ("k_ld", C.c_int32), ("vt_ld", C.c_int32), ("w_ld", C.c_int32),
+        ("o_ld", C.c_int32),   # regional prompting inside cross-attention (an addition to ABI 12)
+    ]
+
+
 class MsdAttentionIdentity(C.Structure):
     _fields_ = [
         ("vt", C.c_void_p), ("out", C.c_void_p),
@@ -185,6 +194,7 @@ SYMBOLS = {
     "msd_latent_resample": (C.c_int, [C.POINTER(MsdLatentResample), C.c_void_p]),
     "msd_tile_consensus": (C.c_int, [C.POINTER(MsdTileConsensus), C.c_void_p]),
     "msd_region_combine": (C.c_int, [C.POINTER(MsdRegionCombine), C.c_void_p]),
+    "msd_region_attention": (C.c_int, [C.POINTER(MsdRegionAttention), C.c_void_p]),
     "msd_attention_identity": (C.c_int, [C.POINTER(MsdAttentionIdentity), C.c_void_p]),
     "msd_add_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_add_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -527,14 +527,20 @@ class Emitter:
                 p.free(a)
         return out
 
-    def attentions(self, x: Act, name, ctx_kv, ctx_len, heads=8, free_input=False, shared: int = 1, perturbed: int = 0) -> Act:
+    def attentions(self, x: Act, name, ctx_kv, ctx_len, heads=8, free_input=False, shared: int = 1, perturbed: int = 0,
+                   regions: int = 0, region_rows: int = 0, region_w=None) -> Act:
         """Attentions / TransformerBlock / CrossAttention / GEGLU (diffusion_model.py:54-153).  shared > 1 (SHARE_CFG_PREFIX): `x` holds
         `shared` identical copies of x.B / shared samples (the cond and uncond halves in front of the first cross-attention): norm,
         proj_in, q|k|v, the self-attention and its to_out run on ONE copy, their result (rows + LayerNorm partials) is replicated, and the
         block continues on the whole batch from attn2 on, where the halves' text contexts differ.
         perturbed (perturbed-attention guidance, minsdtf_amd/pag.py): the number of TRAILING batch rows whose attn1 uses the identity
         attention map - their output is V itself (msd_attention_identity, the transpose of V^T), the rows in front of them take
-        msd_attention as always.  Not with shared > 1: the copies are no longer identical behind this attn1."""
+        msd_attention as always.  Not with shared > 1: the copies are no longer identical behind this attn1.
+        regions = R (regional prompting inside cross-attention, minsdtf_amd/regions.py mode "attention"): the TRAILING `region_rows`
+        rows of the batch are the conditional rows and ctx_kv holds B_u + R * region_rows context rows - the unconditional rows'
+        first, then the regions', region-major.  attn2 then takes the unfused route: q from attn2.to_q, msd_attention for the
+        unconditional rows, ONE msd_region_attention launch for the conditional rows with the weight plane `region_w`
+        (fp32 [R][H * W], this level's).  regions = 0 records exactly the plain block."""
         p = self.p
         x_all = x
         if not 0 <= perturbed <= x.B or (perturbed and shared > 1):
@@ -588,7 +594,25 @@ class Emitter:
         # cross-attention over the text context (k, v^T precomputed once per prompt)
         kc, vtc, tp = ctx_kv[tb + ".attn2"]
         a2 = p.act(B, H, Wd, C)
-        if fold and XATTN_FUSED and heads == 8 and (d in (40, 80) or (d == 160 and XATTN_FUSED_D160)) and ctx_len <= 96:
+        if regions:
+            bu = B - region_rows   # unconditional rows in front
+            if not 1 <= region_rows <= B or region_w is None or ctx_len > 96 or d not in (40, 80, 160):
+                raise ValueError(f"{name}: {regions} regions over {region_rows} of {B} rows, {ctx_len} context tokens, head size {d}")
+            if fold:
+                q2 = self.conv(t1, tb + ".attn2.to_q", C, bias=False, ln_in=t1.ln)
+                p.free(t1.ln[0])
+            else:
+                n2 = self.layer_norm(t1, tb + ".norm2")
+                q2 = self.conv(n2, tb + ".attn2.to_q", C, bias=False)
+                p.free(n2)
+            if bu:
+                p.rec(ops.attention, q=q2.buf, k=kc, vt=vtc, out=a2.buf, batch=bu, heads=heads, head_dim=d, s=S, t=ctx_len, q_ld=C,
+                      k_ld=C, vt_ld=tp, o_ld=C, scale=d ** -0.5, q_prescaled=True, name=tb + ".attn2")
+            p.rec(ops.region_attention, q=q2.buf.at(bu * S * C * 2), k=kc.at(bu * ctx_len * C * 2), vt=vtc.at(bu * C * tp * 2),
+                  w=region_w, out=a2.buf.at(bu * S * C * 2), batch=region_rows, heads=heads, head_dim=d, s=S, t=ctx_len,
+                  regions=regions, q_ld=C, k_ld=C, vt_ld=tp, w_ld=S, o_ld=C, name=tb + ".attn2.regions")
+            p.free(q2)
+        elif fold and XATTN_FUSED and heads == 8 and (d in (40, 80) or (d == 160 and XATTN_FUSED_D160)) and ctx_len <= 96:
             # norm2 -> to_q -> attention over the 77 context tokens as ONE launch (msd_cross_attention_q)
             wn = tb + ".attn2.to_q"
             p.rec(ops.cross_attention_q, x=t1.buf, ln_in=t1.ln[0], ln_in_slots=t1.ln[1], wq=self.W[wn + ".lnw"],
@@ -708,8 +732,24 @@ def temb_columns(encoder_only: bool) -> Dict[str, int]:
     return cols
 
 
+def unet_levels(h: int, w: int) -> List[Tuple[int, int]]:
+    """(h_l, w_l) of the UNet's four resolution levels for a latent of (h, w): every stride-2 downsampler halves, rounding up."""
+    out = [(int(h), int(w))]
+    for _ in range(3):
+        out.append(((out[-1][0] + 1) // 2, (out[-1][1] + 1) // 2))
+    return out
+
+
+def _region_kw(region_attn, x: Act) -> dict:
+    """Emitter.attentions' regional keywords for a block at x's resolution; region_attn = (R, conditional rows, {(h_l, w_l): plane})."""
+    if not region_attn:
+        return {}
+    R, rows, planes = region_attn
+    return dict(regions=R, region_rows=rows, region_w=planes[(x.H, x.W)])
+
+
 def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1,
-                  pag_layers=frozenset(), perturbed: int = 0) -> Act:
+                  pag_layers=frozenset(), perturbed: int = 0, region_attn=None) -> Act:
     """Down path + mid block shared by the UNet (diffusion_model.py:193-229) and the ControlNet.  shared > 1: `x` (conv_in's output) is
     `shared` identical copies of x.B / shared samples - the first ResBlock and the front of the first transformer block run on one.
     pag_layers / perturbed: the attention blocks (by name) whose attn1 is the identity for the last `perturbed` rows."""
@@ -722,26 +762,32 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
             if shared > 1 and lvl == 0 and r == 0:
                 one = Act(x.buf, x.B // shared, x.H, x.W, x.C)
                 x = e.res_block(one, name, ch, temb=temb_of(name), out_copies=shared)
-                x = e.attentions(x, f"down_blocks.{lvl}.attentions.{r}", ctx_kv, ctx_len, free_input=True, shared=shared)
+                x = e.attentions(x, f"down_blocks.{lvl}.attentions.{r}", ctx_kv, ctx_len, free_input=True, shared=shared,
+                                 **_region_kw(region_attn, x))
                 outputs.append(x)
                 continue
             x = e.res_block(x, name, ch, temb=temb_of(name))
             if lvl < 3:
                 blk = f"down_blocks.{lvl}.attentions.{r}"
-                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=pert(blk))
+                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=pert(blk), **_region_kw(region_attn, x))
             outputs.append(x)
         if lvl < 3:
             x = e.conv(x, f"down_blocks.{lvl}.downsamplers.0.conv", ch, ksize=3, stride=2)
             outputs.append(x)
     x = e.res_block(x, "mid_block.resnets.0", 1280, temb=temb_of("mid_block.resnets.0"))
-    x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True, perturbed=pert("mid_block.attentions.0"))
+    x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True, perturbed=pert("mid_block.attentions.0"),
+                     **_region_kw(region_attn, x))
     x = e.res_block(x, "mid_block.resnets.1", 1280, temb=temb_of("mid_block.resnets.1"), free_input=True)
     return x
 
 
 def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w: int, temb, ctx_kv, ctx_len: int,
-              eps_out_f32, controls=None, control_taps=None, pag_layers=None, perturbed: int = 0) -> None:
+              eps_out_f32, controls=None, control_taps=None, pag_layers=None, perturbed: int = 0, region_attn=None) -> None:
     """DiffusionModel graph (diffusion_model.py:184-279).
+
+    region_attn = (R, rows, {(h_l, w_l): fp32 plane [R][h_l * w_l]}) (regional prompting inside cross-attention): the last `rows` of
+    the NB rows are conditional rows whose every attn2 mixes R region contexts (Emitter.attentions); ctx_kv then holds
+    NB - rows + R * rows context rows.  None records exactly the plain forward.
 
     pag_layers (a set of attention block names, PAG_LAYERS) / perturbed: the last `perturbed` of the NB rows run those blocks'
     self-attention with the identity map (Emitter.attentions); perturbed = 0 records exactly the plain forward.
@@ -776,7 +822,8 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
         # the first block's front is no longer identical across the copies: nothing is shared (exact either way - a sample's bits
         # do not depend on its batch)
         shared = 1
-    x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared, pag_layers=pag_layers, perturbed=perturbed)
+    x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared, pag_layers=pag_layers, perturbed=perturbed,
+                      region_attn=region_attn)
     p.mark("controls")   # everything above is independent of the ControlNet (its encoder may run beside it on another stream)
     if control_taps is not None:
         e_c, feats = control_taps
@@ -797,7 +844,8 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
             x = e.res_block((x, skip), name, ch, temb=temb_of(name), free_input=True)
             if lvl < 3:
                 blk = f"up_blocks.{ui}.attentions.{r}"
-                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=perturbed if blk in pag_layers else 0)
+                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=perturbed if blk in pag_layers else 0,
+                                 **_region_kw(region_attn, x))
         if lvl > 0:
             y = e.conv(x, f"up_blocks.{ui}.upsamplers.0.conv", ch, ksize=3, upsample=True)
             p.free(x)

@@ -254,14 +254,27 @@ class DiffusionModel(HipModel):
         self.apply_control_net = apply_control_net
         self._maybe_load(ckpt_path, lora_dict)
 
-    def _build(self, B: int, T: int, with_controls: bool, pag_layers=None) -> _BoundPlan:
-        """pag_layers: the attention blocks whose self-attention is the identity map for ALL B rows (predict_perturbed)."""
+    def _build(self, B: int, T: int, with_controls: bool, pag_layers=None, regions: int = 0) -> _BoundPlan:
+        """pag_layers: the attention blocks whose self-attention is the identity map for ALL B rows (predict_perturbed).
+        regions = R: all B rows are conditional rows over R region contexts (predict_regional): the context input is
+        (R * B, T, 768), region-major, and `region_w` the four levels' weight planes (regions.pack_levels)."""
         h, w = self.h, self.w
         plan = engine.Plan(self.device)
         e = engine.Emitter(plan, self._W)
-        ins = _stage_inputs(plan, dict(latent=(B, h, w, 4), t_emb=(B, 320), context=(B, T, 768)))
-        ctx16 = engine.Act(plan.alloc(B * T * 768 * 2), B, T, 1, 768)
-        plan.rec(ops.cast_f32_to_bf16, x=ins["context"], out=ctx16.buf, n=B * T * 768, name="context.bf16")
+        CB = (regions or 1) * B   # context rows
+        shapes = dict(latent=(B, h, w, 4), t_emb=(B, 320), context=(CB, T, 768))
+        region_attn = None
+        if regions:
+            from . import regions as regions_mod
+
+            levels = engine.unet_levels(h, w)
+            offs = regions_mod.level_offsets(regions, levels)
+            shapes["region_w"] = (offs[-1],)
+        ins = _stage_inputs(plan, shapes)
+        if regions:
+            region_attn = (regions, B, {lv: ins["region_w"].at(o * 4) for lv, o in zip(levels, offs)})
+        ctx16 = engine.Act(plan.alloc(CB * T * 768 * 2), CB, T, 1, 768)
+        plan.rec(ops.cast_f32_to_bf16, x=ins["context"], out=ctx16.buf, n=CB * T * 768, name="context.bf16")
         ctx_kv = engine.emit_context_kv(e, ctx16, engine.UNET_ATTN_LAYERS, plan)
         cols = engine.temb_columns(False)
         total = sum(c for _, c in engine.resblock_names(False))
@@ -277,11 +290,10 @@ class DiffusionModel(HipModel):
                 controls.append(st)
         eps = plan.alloc(B * h * w * 4 * 4)
         engine.emit_unet(e, ins["latent"], B, B, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls,
-                         pag_layers=pag_layers, perturbed=B if pag_layers else 0)
+                         pag_layers=pag_layers, perturbed=B if pag_layers else 0, region_attn=region_attn)
         plan.finalize()
         bp = _BoundPlan(plan, self._use_graph)
-        bp.io = {k: b.tensor(torch.float32, s) for (k, b), s in
-                 zip(ins.items(), [(B, h, w, 4), (B, 320), (B, T, 768)])}
+        bp.io = {k: b.tensor(torch.float32, shapes[k]) for k, b in ins.items()}
         bp.io["eps"] = eps.tensor(torch.float32, (B, h, w, 4))
         for i, (st, shp) in enumerate(cstage):
             bp.io[f"control.{i}"] = st.tensor(torch.float32, shp)
@@ -301,6 +313,35 @@ class DiffusionModel(HipModel):
         if len(x) != 3:
             raise ValueError("predict_perturbed takes [latent, t_emb, context] (no control tensors)")
         return self._predict(x, layers)
+
+    def predict_regional(self, x, contexts, level_weights):
+        """predict_on_batch([latent, t_emb]) with every attn2 mixing the R region `contexts` (each (B, T, 768), T <= 96) per query by
+        `level_weights` (Resolved.level_weights(engine.unet_levels(h, w)): one fp32 (R, h_l, w_l) per level) - one
+        msd_region_attention launch per layer (regions.py, mode "attention"); a bound plan of its own per (B, T, R)."""
+        from . import regions as regions_mod
+
+        if len(x) != 2:
+            raise ValueError("predict_regional takes [latent, t_emb] (the contexts are its second argument; no control tensors)")
+        latent, t_emb = _np32(x[0]), _np32(x[1])
+        ctx = [_np32(c) for c in contexts]
+        R, B = len(ctx), latent.shape[0]
+        planes = [np.asarray(p, dtype=np.float32) for p in level_weights]
+        levels = engine.unet_levels(self.h, self.w)
+        if not 1 <= R <= regions_mod.MAX_REGIONS or any(c.shape != ctx[0].shape for c in ctx) or ctx[0].shape[0] != B or ctx[0].shape[1] > 96:
+            raise ValueError(f"predict_regional: {R} contexts of shapes {[c.shape for c in ctx]} for a batch of {B} (1 .. "
+                             f"{regions_mod.MAX_REGIONS} contexts of (B, T <= 96, 768))")
+        if [p.shape for p in planes] != [(R,) + lv for lv in levels]:
+            raise ValueError(f"predict_regional: level weights of shapes {[p.shape for p in planes]}, expected {[(R,) + lv for lv in levels]}")
+        if latent.shape[1:] != (self.h, self.w, 4):
+            raise ValueError(f"latent shape {latent.shape} does not match the model ({self.h},{self.w},4)")
+        T = ctx[0].shape[1]
+        bp = self._bound((B, T, False, ("regions", R)), lambda: self._build(B, T, False, regions=R))
+        bp.io["latent"].copy_(torch.from_numpy(latent))
+        bp.io["t_emb"].copy_(torch.from_numpy(t_emb))
+        bp.io["context"].copy_(torch.from_numpy(np.concatenate(ctx, axis=0)))
+        bp.io["region_w"].copy_(torch.from_numpy(regions_mod.pack_levels(planes)))
+        bp.run()
+        return bp.host("eps")
 
     def _predict(self, x, pag_layers):
         latent, t_emb, context = _np32(x[0]), _np32(x[1]), _np32(x[2])

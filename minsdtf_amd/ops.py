@@ -228,6 +228,20 @@ def region_combine(*, eps, w, out, regions, batch, n, name="region_combine") -> 
     return Call(lib.msd_region_combine, (C.byref(s),), name, keep=s)
 
 
+def region_attention(*, q, k, vt, w, out, batch, heads, head_dim, s, t, regions, q_ld, k_ld, vt_ld, w_ld, o_ld,
+                     name="region_attention") -> Call:
+    """msd_region_attention: out[b] = sum_r w[r] * softmax(q[b] k[r * batch + b]^T) v[r * batch + b] per query, r ascending, a
+    weight of exactly 0 not accumulated.  q bf16 [batch][s][q_ld] carrying scale * log2(e), k bf16 [regions * batch][t][k_ld],
+    vt bf16 [regions * batch][heads * head_dim][vt_ld], w fp32 [regions][w_ld] (regions.Resolved.level_weights), out bf16
+    [batch][s][o_ld]."""
+    lib = _lib.load()
+    a = _lib.MsdRegionAttention()
+    a.q, a.k, a.vt, a.w, a.out = _p(q), _p(k), _p(vt), _p(w), _p(out)
+    a.batch, a.heads, a.head_dim, a.s, a.t, a.regions = int(batch), int(heads), int(head_dim), int(s), int(t), int(regions)
+    a.q_ld, a.k_ld, a.vt_ld, a.w_ld, a.o_ld = int(q_ld), int(k_ld), int(vt_ld), int(w_ld), int(o_ld)
+    return Call(lib.msd_region_attention, (C.byref(a),), name, keep=a)
+
+
 def attention_identity(*, vt, out, batch, channels, s, vt_ld, o_ld, name="attention_identity") -> Call:
     """msd_attention_identity: out[b][k][c] = vt[b][c][k] - self-attention with the identity map (the perturbed rows of a PAG job).
     vt bf16 [batch][channels][vt_ld] (msd_attention's operand), out bf16 [batch][s][o_ld]."""

@@ -12,6 +12,12 @@ Weights: w_r = weight_r * mask_r / sum_q weight_q * mask_q per latent pixel, com
 a pixel covered by one region alone has exactly 1.0 there and 0.0 elsewhere, and the kernel copies that region's eps bit for bit.
 With ``base_weight`` > 0 the job's own prompt joins as region 0 with the constant mask ``base_weight``; with 0 it is not
 evaluated at all.
+
+``mode="attention"`` ("attention couple") applies the masks where the prompts enter the network instead: the UNet runs the plain
+job's rows, and in every attn2 the conditional rows compute out(q) = sum_r w_r(q) softmax(q K_r^T) V_r in one launch
+(``msd_region_attention``).  Its host side is here too: the weight planes of the UNet's four resolution levels
+(``Resolved.level_weights``: float64 block means of the weighted masks, normalised over the regions, rounded once), their packing
+into the one array an engine uploads (``pack_levels``) and a float64 statement of the kernel (``attention_reference``).
 """
 from __future__ import annotations
 
@@ -37,6 +43,7 @@ class Regions:
     """A regional job: the RegionSpecs in order and the weight of the job's own prompt (0: it is not evaluated)."""
     regions: Sequence[RegionSpec] = field(default_factory=list)
     base_weight: float = 0.0
+    mode: str = "latent"   # "latent": one UNet row per region, msd_region_combine; "attention": the masks applied in every attn2
 
 
 @dataclass(frozen=True)
@@ -46,6 +53,7 @@ class Resolved:
     prompts: Tuple[Any, ...]
     masks: np.ndarray
     base_weight: float
+    mode: str = "latent"
 
     @property
     def count(self) -> int:
@@ -58,6 +66,48 @@ class Resolved:
         if self.base_weight > 0.0:
             m = np.concatenate([np.full((1,) + m.shape[1:], self.base_weight, dtype=np.float64), m], axis=0)
         return _normalise(m)
+
+    def level_weights(self, levels) -> List[np.ndarray]:
+        """The weight planes of an attention-mode job: one fp32 (count, h_l, w_l) per UNet resolution level, ``levels`` being the
+        (h_l, w_l) of the levels as the engine records them ((h, w) of the latent first, every further level ceil-halved).
+        Pixel (y, x) of level l stands for the latent pixels [y 2^l, min((y + 1) 2^l, h)) x [x 2^l, min((x + 1) 2^l, w)): its
+        weights are the float64 means of the weighted masks over that (clipped) block - the base prompt's plane is the
+        constant base_weight - normalised over the regions and rounded once to fp32.  Level 0 is weights() bit for bit."""
+        h, w = self.masks.shape[1:]
+        out = []
+        for l, (hl, wl) in enumerate(levels):
+            f = 1 << l
+            hl, wl = int(hl), int(wl)
+            if (hl, wl) != (-(-h // f), -(-w // f)):
+                raise ValueError(f"regions: level {l} is {(hl, wl)}, expected {(-(-h // f), -(-w // f))} for a latent of {(h, w)}")
+            pad = np.zeros((self.masks.shape[0], hl * f, wl * f), dtype=np.float64)
+            pad[:, :h, :w] = self.masks
+            rows = np.minimum(f, h - f * np.arange(hl)).astype(np.float64)   # latent rows / columns of each (clipped) block
+            cols = np.minimum(f, w - f * np.arange(wl)).astype(np.float64)
+            m = pad.reshape(-1, hl, f, wl, f).sum(axis=(2, 4)) / (rows[:, None] * cols[None, :])[None]
+            if self.base_weight > 0.0:
+                m = np.concatenate([np.full((1, hl, wl), self.base_weight, dtype=np.float64), m], axis=0)
+            out.append(_normalise(m))
+        return out
+
+
+def pack_levels(planes) -> np.ndarray:
+    """The level planes of level_weights() as the ONE flat fp32 array an attention-mode engine uploads: level l's (count, h_l, w_l)
+    row-major at level_offsets()[l], every level starting on a multiple of 4 floats (16 bytes)."""
+    planes = [np.ascontiguousarray(p, dtype=np.float32) for p in planes]
+    offs = level_offsets(planes[0].shape[0], [p.shape[1:] for p in planes])
+    out = np.zeros(offs[-1], dtype=np.float32)
+    for p, o in zip(planes, offs):
+        out[o:o + p.size] = p.reshape(-1)
+    return out
+
+
+def level_offsets(count: int, levels) -> List[int]:
+    """Float offsets of the levels' planes in pack_levels' array, and behind them its length."""
+    offs = [0]
+    for hl, wl in levels:
+        offs.append(offs[-1] + (int(count) * int(hl) * int(wl) + 3) // 4 * 4)
+    return offs
 
 
 def boxes(h: int, w: int, rows: int, cols: int) -> List[np.ndarray]:
@@ -113,7 +163,12 @@ def weights(masks, region_weights=None, base_weight: float = 0.0, h: Optional[in
     return _resolve([RegionSpec(None, m, v) for m, v in zip(masks, ws)], base_weight, int(h), int(w)).weights()
 
 
-def _resolve(specs, base_weight, h: int, w: int) -> Resolved:
+MODES = ("latent", "attention")
+
+
+def _resolve(specs, base_weight, h: int, w: int, mode: str = "latent") -> Resolved:
+    if mode not in MODES:
+        raise ValueError(f"regions: mode = {mode!r}: one of {MODES}")
     base_weight = float(base_weight)
     if not np.isfinite(base_weight) or base_weight < 0.0:
         raise ValueError(f"regions: base_weight = {base_weight!r} must be a finite float >= 0")
@@ -131,23 +186,26 @@ def _resolve(specs, base_weight, h: int, w: int) -> Resolved:
         if s.mask is None:
             raise ValueError(f"regions: region {i} has no mask")
         out.append(wt * latent_mask(s.mask, h, w, f"the mask of region {i}"))
-    res = Resolved(tuple(s.prompt for s in specs), np.stack(out, axis=0), base_weight)
+    res = Resolved(tuple(s.prompt for s in specs), np.stack(out, axis=0), base_weight, mode)
     res.weights()   # (ValueError for an uncovered pixel, now rather than in the middle of the job)
     return res
 
 
 def parse(regions, img_height: int, img_width: int) -> Optional[Resolved]:
-    """None -> None; a Regions object or a dict {"regions": [RegionSpec or dict of its fields, ...], "base_weight": 0.0} -> the
-    description resolved at the pipeline's size.  ValueError for an unknown field, a bad mask or weight, a pixel no region covers,
+    """None -> None; a Regions object or a dict {"regions": [RegionSpec or dict of its fields, ...], "base_weight": 0.0,
+    "mode": "latent" or "attention"} -> the description resolved at the pipeline's size.  ValueError for an unknown field or
+    mode, a bad mask or weight, a pixel no region covers,
     more than MAX_REGIONS evaluated prompts."""
     if regions is None:
         return None
     if isinstance(regions, Resolved):
+        if regions.mode not in MODES:
+            raise ValueError(f"regions: mode = {regions.mode!r}: one of {MODES}")
         if tuple(regions.masks.shape[1:]) != (img_height // 8, img_width // 8):
             raise ValueError(f"regions: masks of {tuple(regions.masks.shape[1:])} on a latent of {(img_height // 8, img_width // 8)}")
         return regions
     if isinstance(regions, dict):
-        unknown = set(regions) - {"regions", "base_weight"}
+        unknown = set(regions) - {"regions", "base_weight", "mode"}
         if unknown:
             raise ValueError(f"regions: unknown field(s) {sorted(unknown)}")
         regions = Regions(**regions)
@@ -167,7 +225,7 @@ def parse(regions, img_height: int, img_width: int) -> Optional[Resolved]:
         if s.prompt is None:
             raise ValueError(f"regions: region {i} has no prompt")
         specs.append(s)
-    return _resolve(specs, regions.base_weight, img_height // 8, img_width // 8)
+    return _resolve(specs, regions.base_weight, img_height // 8, img_width // 8, regions.mode)
 
 
 def combine_reference(eps, w) -> np.ndarray:
@@ -194,3 +252,29 @@ def combine_host(eps_list, w) -> np.ndarray:
         prod = w[r].astype(np.float64)[None, :, :, None] * np.asarray(eps_list[r], dtype=np.float32).astype(np.float64)
         v = (prod + v.astype(np.float64)).astype(np.float32)
     return v
+
+
+def attention_reference(q, k, v, w, heads: int) -> np.ndarray:
+    """float64 statement of msd_region_attention: q (B, S, C) carrying scale * log2(e), k and v (R * B, T, C) region-major (row
+    r * B + b), w (R, S), C = heads * d -> (B, S, C) = sum_r w[r][i] * softmax2(q_h k_rh^T) v_rh per head h, the softmax to base
+    2.  A region takes part at a query only where its weight is positive, so the K / V of a region that is nowhere positive may
+    hold anything."""
+    q, k, v, w = (np.asarray(x, dtype=np.float64) for x in (q, k, v, w))
+    R = w.shape[0]
+    if q.ndim != 3 or k.ndim != 3 or k.shape != v.shape or w.ndim != 2 or k.shape[0] != R * q.shape[0] or w.shape[1] != q.shape[1] \
+            or q.shape[2] != k.shape[2] or q.shape[2] % heads:
+        raise ValueError(f"regions: q {q.shape}, k {k.shape}, v {v.shape}, w {w.shape}, {heads} heads")
+    B, S, C = q.shape
+    d = C // heads
+    out = np.zeros((B, S, C), dtype=np.float64)
+    for r in range(R):
+        on = w[r] > 0.0
+        if not on.any():
+            continue
+        for b in range(B):
+            for h in range(heads):
+                c = slice(h * d, (h + 1) * d)
+                s = q[b, on, c] @ k[r * B + b, :, c].T
+                p = np.exp2(s - s.max(axis=1, keepdims=True))
+                out[b, on, c] += w[r, on, None] * ((p / p.sum(axis=1, keepdims=True)) @ v[r * B + b, :, c])
+    return out

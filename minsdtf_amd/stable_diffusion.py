@@ -73,11 +73,11 @@ class DenoiseEngine:
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
-                 sampler=None, tiled=None, regions: int = 0, pag=None):
+                 sampler=None, tiled=None, regions: int = 0, pag=None, region_mode: str = "latent"):
         unet._require_weights()
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
-        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag)
+        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag, region_mode)
         self.use_graph = use_graph
         self.guidance = float(guidance)
         self.cfg = cfg = guidance > 0.0
@@ -92,7 +92,8 @@ class DenoiseEngine:
         self.dual = bool(cfg and streams == 2)
         fuse = cfg and (t_cond == t_uncond) and not self.dual
         # passes: list of (rows in eps, NB, context length); fused = uncond rows then cond rows
-        RC = self.regions or (2 if self.pag else 1)   # conditional copies of the batch (a PAG job: the c rows, then the p rows)
+        # (regions in attention mode: the masks act inside every attn2 - the UNet runs the plain job's rows, only the CONTEXT rows grow)
+        RC = 1 if self.region_attn else (self.regions or (2 if self.pag else 1))   # conditional copies of the batch (a PAG job: the c rows, then the p rows)
         if not cfg:
             passes = [(0, RC * B, t_cond, "cond")]
         elif fuse:
@@ -120,7 +121,7 @@ class DenoiseEngine:
         self._warmed = False
         _lib.track_graph_owner(self)
 
-    def _check_options(self, control_net, streams, inpaint, tcd, sampler, tiled, regions, pag=None) -> None:
+    def _check_options(self, control_net, streams, inpaint, tcd, sampler, tiled, regions, pag=None, region_mode="latent") -> None:
         """The option combinations an engine refuses (generate_image refuses them earlier, by argument name: _REFUSED; these guard
         direct construction).  Sets `sampler`, `tiled`, `regions` and `pag`."""
         # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
@@ -139,7 +140,14 @@ class DenoiseEngine:
         # regions (R, the number of evaluated region prompts, or 0): the conditional half is R * B rows, region-major (row
         # r * B + b) behind the unconditional rows; one msd_region_combine launch in front of the guidance / sampler step sums them
         # per pixel with the weights of `region_w` into the first B of those rows, in place (minsdtf_amd/regions.py)
+        # region_mode "attention": the UNet keeps the plain job's rows; every attn2 gives the conditional rows ONE msd_region_attention
+        # launch over the R region contexts with the level's weight plane (`region_w`: the four levels' planes, regions.pack_levels),
+        # and there is no combine in the tail
         self.regions = R = int(regions or 0)
+        if region_mode not in regions_mod.MODES:
+            raise ValueError(f"regions: mode = {region_mode!r}: one of {regions_mod.MODES}")
+        self.region_mode = region_mode if R else "latent"
+        self.region_attn = bool(R) and region_mode == "attention"
         if R:
             if not 1 <= R <= regions_mod.MAX_REGIONS:
                 raise ValueError(f"regions: {R} region prompts (1 .. {regions_mod.MAX_REGIONS})")
@@ -188,6 +196,8 @@ class DenoiseEngine:
             table_c = prep_t.alloc(num_steps * total_c * 4)
             engine.emit_time_embedding(engine.Emitter(prep_t, control_net._W), self.temb_in, num_steps, table_c, encoder_only=True)
         for (_row0, nb, t, tag) in passes:
+            if self.region_attn and tag != "uncond":   # context rows, not UNet rows: the B conditional rows read R * B contexts
+                nb = nb + (self.regions - 1) * B
             st = torch.zeros(nb, t, 768, dtype=torch.float32, device=dev)
             self.ctx_in[tag] = st
             c16 = engine.Act(prep.alloc(nb * t * 768 * 2), nb, t, 1, 768)
@@ -216,9 +226,15 @@ class DenoiseEngine:
         unet, B, h, w, R, passes = self.unet, self.B, self.h, self.w, self.regions, self.passes
         dev = unet.device
         n = h * w * 4
-        RC = R or (2 if self.pag else 1)
+        RC = 1 if self.region_attn else (R or (2 if self.pag else 1))
         self.eps = torch.zeros(((1 + RC) * B if self.cfg else RC * B), n, dtype=torch.float32, device=dev)
         self.region_w = torch.zeros(R, h, w, dtype=torch.float32, device=dev) if R else None
+        region_planes = None
+        if self.region_attn:   # one buffer for the four levels' planes [R][h_l * w_l] (regions.pack_levels)
+            levels = engine.unet_levels(h, w)
+            offs = regions_mod.level_offsets(R, levels)
+            self.region_w = torch.zeros(offs[-1], dtype=torch.float32, device=dev)
+            region_planes = {lv: _Ptr(self.region_w.data_ptr() + o * 4) for lv, o in zip(levels, offs)}
         self.pag_w = torch.zeros(2, h, w, dtype=torch.float32, device=dev) if self.pag else None
         self.branches = []
         step = None
@@ -246,8 +262,10 @@ class DenoiseEngine:
                 taps = (s_c, feats)
             eps_view = _Ptr(self.eps.data_ptr() + row0 * n * 4)
             # (a PAG job: the p rows are the last B rows of the pass that holds the conditional rows)
-            pert = dict(pag_layers=self.pag, perturbed=B) if self.pag and tag != "uncond" else {}
-            engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps, **pert)
+            extra = dict(pag_layers=self.pag, perturbed=B) if self.pag and tag != "uncond" else {}
+            if self.region_attn and tag != "uncond":   # the conditional rows are the last B rows of their pass
+                extra = dict(region_attn=(R, B, region_planes))
+            engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps, **extra)
         return step
 
     def _build_tail(self, step, guidance, guidance_rescale, inpaint, tcd) -> "engine.Plan":
@@ -269,7 +287,7 @@ class DenoiseEngine:
         self.step_noise = torch.zeros(num_steps, B, n, dtype=torch.float32, device=dev) if stochastic else None
         self.noise_coef = torch.zeros(num_steps, dtype=torch.float32, device=dev) if tcd else None
         self.denoised_prev = None
-        if R:
+        if R and not self.region_attn:
             # (R == 1 too: a weight of all ones copies the row bit for bit)  Behind it the step kernels read [2B][n] (or [B][n])
             cond = _Ptr(self.eps.data_ptr() + (B if self.cfg else 0) * n * 4)
             tail.rec(ops.region_combine, eps=cond, w=self.region_w, out=cond, regions=R, batch=B, n=n)
@@ -432,7 +450,8 @@ class DenoiseEngine:
         draws for the global batch) instead of the draws made here.  An engine built with a sampler takes its
         samplers.Schedule as `sampler` (the coefficient rows are built here for `start_index`) and, for the stochastic samplers,
         its draws as `step_noise` (B, num_steps, ...) (drawn here from numpy's global stream when None).
-        regions = the normalised weights (R, h, w) of a regional engine (regions.weights): a per-call upload, like the inpaint mask.
+        regions = the normalised weights (R, h, w) of a regional engine (regions.weights): a per-call upload, like the inpaint mask;
+        an attention-mode engine takes the four levels' planes as one flat array (regions.pack_levels of Resolved.level_weights).
         pag_scale = the scale s of a PAG engine: the two planes fp32(1 + k), fp32(-k) (pag.weights, k from s and the engine's
         guidance in float64) are a per-call upload too, so another scale needs no other engine."""
         if (pag_scale is None) != (self.pag_w is None):
@@ -820,7 +839,10 @@ class StableDiffusionBase:
         engine) and one msd_region_combine launch sums the predictions per latent pixel with the normalised mask weights in front
         of the guidance / sampler step.  With base_weight > 0 `encoded_text` joins as region 0 with that constant mask; with 0 it is
         not evaluated.  The region contexts share one token length.  At most 2 * tiled.MAX_VIEW_BATCH UNet rows
-        ((1 + R) * batch_size).  Works with host_loop=True too.
+        ((1 + R) * batch_size).  Works with host_loop=True too.  With the further key "mode": "attention" the masks act inside every
+        attn2 instead (one msd_region_attention launch per layer over the R region contexts, the masks reduced to each level by
+        regions.Resolved.level_weights): the UNet runs the plain job's rows, so the cap is 2 * batch_size rows against the same
+        constant whatever R is; contexts of at most 96 tokens (ValueError naming mode="latent" otherwise).
         ``pag`` (a pag.PagSpec or a dict {"scale": 3.0, "layers": "mid"}; txt2img only): perturbed-attention guidance - every step the
         UNet evaluates the conditional context once more with the self-attention of the selected blocks replaced by the identity map
         (further batch rows of the one engine, msd_attention_identity in those blocks) and eps = u + g (c - u) + s (c - p); one
@@ -842,7 +864,11 @@ class StableDiffusionBase:
         reg = regions_mod.parse(regions, self.img_height, self.img_width)   # (ValueError for a bad description)
         if reg is not None:
             self._refuse_combinations("regions", given, host_loop)
-            if (1 + reg.count) * int(batch_size) > 2 * tiled_mod.MAX_VIEW_BATCH:
+            if reg.mode == "attention":   # the UNet runs the plain job's rows whatever the number of regions
+                if 2 * int(batch_size) > 2 * tiled_mod.MAX_VIEW_BATCH:
+                    raise ValueError(f'regions: {batch_size} image(s) in mode="attention" are {2 * int(batch_size)} UNet rows per step, more '
+                                     f"than 2 * tiled.MAX_VIEW_BATCH = {2 * tiled_mod.MAX_VIEW_BATCH}: use a smaller batch")
+            elif (1 + reg.count) * int(batch_size) > 2 * tiled_mod.MAX_VIEW_BATCH:
                 raise ValueError(f"regions: {batch_size} image(s) of 1 + {reg.count} prompts are {(1 + reg.count) * int(batch_size)} UNet "
                                  f"rows per step, more than 2 * tiled.MAX_VIEW_BATCH = {2 * tiled_mod.MAX_VIEW_BATCH}: use fewer regions "
                                  "or a smaller batch")
@@ -910,6 +936,12 @@ class StableDiffusionBase:
         region_ctx = region_w = None
         if reg is not None:
             region_ctx, region_w = self._region_inputs(reg, context)   # (R', T, 768) without the base prompt, (R, h, w)
+            if reg.mode == "attention":
+                if region_ctx.shape[1] > 96:
+                    raise ValueError(f'regions: mode="attention" takes contexts of at most 96 tokens, got {region_ctx.shape[1]}: use '
+                                     'mode="latent"')
+                region_w = reg.level_weights(engine.unet_levels(noise.shape[1], noise.shape[2]))
+                region_w = region_w if host_loop else regions_mod.pack_levels(region_w)
             if host_loop:   # the conditional context becomes the list of region contexts, each (B, T, 768)
                 context = ([context] if reg.base_weight > 0.0 else []) + [np.repeat(rc[None], B, axis=0) for rc in region_ctx]
 
@@ -959,7 +991,8 @@ class StableDiffusionBase:
                 rep = (lambda x: x.unsqueeze(0).expand(b, -1, -1)) if isinstance(rc, torch.Tensor) else (lambda x: np.repeat(x[None], b, axis=0))
                 c = ([c] if reg.base_weight > 0.0 else []) + [rep(rc[i]) for i in range(rc.shape[0])]
             eng = self._denoise_pass(u, c, z, num_steps, g, phi, start_index, run_steps, callback,
-                                     dict(sampler=sname, regions=None if reg is None else len(c), pag=None if pg is None else pg.key),
+                                     dict(sampler=sname, regions=None if reg is None else len(c), pag=None if pg is None else pg.key,
+                                          region_mode="attention" if reg is not None and reg.mode == "attention" else None),
                                      dict(hint_image=a.get("hint"), inpaint=(a["encoded"], a["noise"], a["mask"]) if inpainting else None,
                                           step_noise=a.get("tcd") if spec is None else a.get("sampler_z"), sampler=sched,
                                           regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale))
@@ -1177,7 +1210,7 @@ class StableDiffusionBase:
         key = key if unet is base else key + ((unet.h, unet.w),)   # (a hires job's second size: a view of the same weights)
         key = key if tiled is None else key + (tiled.key,)         # (a tiled job: B counts views)
         # (a regional job: the NUMBER of evaluated region prompts only - masks, weights and prompts are per-call uploads)
-        key = key if not regions else key + (("regions", int(regions)),)
+        key = key if not regions else key + (("regions", int(regions)) + (("attention",) if opts.get("region_mode") == "attention" else ()),)
         # (a PAG job: the selected blocks only - the scale is a per-call upload)
         return key if not opts.get("pag") else key + (("pag", tuple(sorted(opts["pag"]))),)
 
@@ -1188,7 +1221,7 @@ class StableDiffusionBase:
         alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is
         built: a re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than
         the job's own engines - one for a plain job, two for a hires job."""
-        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag"}:
+        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode"}:
             raise TypeError(f"_engine: unknown option among {sorted(opts)}")
         key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, **opts)
         keep = {key} | set(job_keys or ())
@@ -1207,7 +1240,8 @@ class StableDiffusionBase:
                                 control_net=self.control_net if control else None,
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
                                 streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=opts.get("sampler"),
-                                tiled=opts.get("tiled"), regions=opts.get("regions") or 0, pag=opts.get("pag"))
+                                tiled=opts.get("tiled"), regions=opts.get("regions") or 0, pag=opts.get("pag"),
+                                region_mode=opts.get("region_mode") or "latent")
             self._engines[key] = eng
         return eng
 
@@ -1237,7 +1271,8 @@ class StableDiffusionBase:
     def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None):
         """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
         A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
-        predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host).  A PAG job passes
+        predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host); in mode "attention"
+        `region_w` is the list of the four levels' planes and the conditional prediction is ONE predict_regional.  A PAG job passes
         its pag.Resolved: the conditional prediction becomes c' = (1 + k) c - k p, p from predict_perturbed (pag.combine_host)."""
         def predict(ctx):
             """The UNet's prediction for one context, through the ControlNet if there is a hint."""
@@ -1247,7 +1282,10 @@ class StableDiffusionBase:
             return self.diffusion_model.predict_on_batch([latent, t_emb, ctx] + list(controls))
 
         regional = isinstance(context, (list, tuple))   # (its region prompts run in front of the unconditional one)
-        c = regions_mod.combine_host([predict(rc) for rc in context], region_w) if regional else None
+        if regional and isinstance(region_w, (list, tuple)):   # mode "attention": the level planes, one forward for all regions
+            c = self.diffusion_model.predict_regional([latent, t_emb], context, region_w)
+        else:
+            c = regions_mod.combine_host([predict(rc) for rc in context], region_w) if regional else None
         u = predict(unconditional_context) if g > 0.0 else None
         c = c if regional else predict(context)
         if pag is not None:
