@@ -662,6 +662,78 @@ typedef struct MsdRegionAttention {
 
 MSD_API int msd_region_attention(const MsdRegionAttention* p, msd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * msd_attention_joint — self-attention over the row's own keys AND the keys of one shared reference row: "reference-only"
+ * control (minsdtf_amd/reference.py).  softmax(own ‖ ref) is not a sum of two softmaxes, so this is one flash
+ * kernel that walks two key segments; the blend with the plain self-attention (diffusers' style_fidelity) is the online
+ * softmax's state at the segment boundary, kept for later.  An addition to ABI 12: nothing else changed.
+ *
+ *   q:      bf16 [batch][s][q_ld], head h at columns [h * d, (h + 1) * d), d = head_dim; q MUST carry scale * log2(e) (the
+ *           q_prescaled form of msd_attention); q_ld >= heads * d
+ *   k:      bf16 [batch][t][k_ld]                the row's own keys; k_ld >= heads * d
+ *   vt:     bf16 [batch][heads * d][vt_ld]       its own V^T, key index contiguous; columns >= t are padding
+ *   k_ref:  bf16 [t_ref][k_ld]                   ONE row, shared by the batch (same leading dimension as k)
+ *   vt_ref: bf16 [heads * d][vt_ld]              columns >= t_ref are padding
+ *   mix:    fp32 [batch] in [0, 1], or NULL = all 0: the share of the plain self-attention in the sample's output
+ *   out:    bf16 [batch][s][o_ld]; columns >= heads * d of a row are not written
+ *
+ * head_dim is 40, 80 or 160; s, t, t_ref >= 1; vt_ld % 8 == 0 and vt_ld >= max(t, t_ref).  Padding columns of vt / vt_ref,
+ * whatever they hold (NaN included), never reach out.
+ *
+ * Per sample b, head, query and channel (pinned; fp32).  The own keys are walked in ascending tiles of 64 keys, then the
+ * reference keys the same way; a segment's last tile may be partial, the own segment's too (in the middle of the walk).  With
+ * the state m = -1e30, l = 0, O = 0, every tile does
+ *   m' = max(m, max_key score[key])      a = exp2(m - m')      l = l * a      O = O * a      m = m'
+ *   P[key] = bf16(exp2(score[key] - m))  l += sum_key P[key]   O += sum_key P[key] * v[key][c]
+ * (P rounded to bf16 is both the operand of the second product and what the row sum adds; the rescale is applied at every
+ * tile, never deferred).  Then
+ *   after the last own tile:        plain = O * (1 / l)
+ *   after the last reference tile:  joint = O * (1 / l)
+ *   f = mix[b] (0 when mix is NULL):
+ *     f == 0:     out = bf16(joint)                                    the bits of a launch with mix = NULL
+ *     f == 1:     out = bf16(plain)                                    the reference segment is NOT read for that sample:
+ *                                                                      k_ref / vt_ref may hold anything, NaN included
+ *     otherwise:  out = bf16(fma(f, plain, (1.0f - f) * joint))
+ * plain depends on the own segment alone: nothing the reference keys do to the running maximum afterwards moves it.  A
+ * workgroup is 64 queries of one sample and head, so the branch on f is uniform over it.
+ *
+ * Both products run on MFMAs with K / V^T tiles staged in LDS; plain vector loads and stores, no atomics, no scratch buffer;
+ * nothing couples two samples, so a sample's bits do not depend on its batch.  Checked on the host, without a device: q / k /
+ * vt / k_ref / vt_ref / out non-NULL and 16-byte aligned; mix NULL or 16-byte aligned (its values are not checked); head_dim in
+ * range; batch and heads in 1 .. 65535; s, t, t_ref >= 1; q_ld, k_ld, vt_ld and o_ld multiples of 8; q_ld, k_ld, o_ld >= heads *
+ * head_dim; vt_ld >= max(t, t_ref); fewer than 2^31 workgroups; the extent of out apart from the extent of every input.
+ * Argument errors return MSD_E_ARG without launching.  Nothing is allocated; the launch is stream-ordered and capturable. */
+typedef struct MsdAttentionJoint {
+    const void* q;
+    const void* k;
+    const void* vt;
+    const void* k_ref;
+    const void* vt_ref;
+    const float* mix;
+    void* out;
+    int32_t batch, heads, head_dim, s, t, t_ref;
+    int32_t q_ld, k_ld, vt_ld, o_ld;
+} MsdAttentionJoint;
+
+MSD_API int msd_attention_joint(const MsdAttentionJoint* p, msd_stream_t stream);
+
+/* msd_reference_latent — the reference row's UNet input of the current step (reference-only control):
+ *   out[i] = fma(coef[step][1], noise[i], coef[step][0] * z[i])          fp32, i < n, on float4s
+ * z / noise / out: fp32 [n], 16-byte aligned, pairwise distinct; n a positive multiple of 4.  coef: fp32 [num_steps][2], the
+ * signal and noise rate at which each step's UNet evaluation sees its latent (reference.rates).  step = *step_ptr (0 when
+ * step_ptr is NULL), clamped to 0 .. num_steps - 1 like msd_cfg_step's.  Argument errors return MSD_E_ARG without launching;
+ * nothing is allocated; the launch is stream-ordered and capturable. */
+typedef struct MsdReferenceLatent {
+    const float* z;
+    const float* noise;
+    const float* coef;
+    const int32_t* step_ptr;
+    float* out;
+    int32_t n, num_steps;
+} MsdReferenceLatent;
+
+MSD_API int msd_reference_latent(const MsdReferenceLatent* p, msd_stream_t stream);
+
 /* msd_add_bf16 — out = a + b elementwise on bf16. n % 8 == 0. */
 MSD_API int msd_add_bf16(const void* a, const void* b, void* out, int64_t n, msd_stream_t stream);
 /* msd_add_f32_bf16 — out = bf16(a + b), a / out bf16, b fp32, summed in fp32 (may run in place, out == a).  The ControlNet

@@ -166,6 +166,23 @@ class MsdAttentionIdentity(C.Structure):
     ]
 
 
+class MsdAttentionJoint(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("vt", C.c_void_p), ("k_ref", C.c_void_p), ("vt_ref", C.c_void_p),
+        ("mix", C.c_void_p), ("out", C.c_void_p),
+        ("batch", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("s", C.c_int32), ("t", C.c_int32),
+        ("t_ref", C.c_int32), ("q_ld", C.c_int32), ("k_ld", C.c_int32), ("vt_ld", C.c_int32),
+        ("o_ld", C.c_int32),   # reference-only control (an addition to ABI 12)
+    ]
+
+
+class MsdReferenceLatent(C.Structure):
+    _fields_ = [
+        ("z", C.c_void_p), ("noise", C.c_void_p), ("coef", C.c_void_p), ("step_ptr", C.c_void_p), ("out", C.c_void_p),
+        ("n", C.c_int32), ("num_steps", C.c_int32),   # reference-only control (an addition to ABI 12)
+    ]
+
+
 LORA_ROWS_PER_BLOCK = 8  # csrc/lora.hip LR_ROWS: MsdLoraJob.first_block counts workgroups of this many rows
 
 # every symbol include/minsdtf_hip.h declares: name -> (restype, argtypes)
@@ -196,6 +213,8 @@ SYMBOLS = {
     "msd_region_combine": (C.c_int, [C.POINTER(MsdRegionCombine), C.c_void_p]),
     "msd_region_attention": (C.c_int, [C.POINTER(MsdRegionAttention), C.c_void_p]),
     "msd_attention_identity": (C.c_int, [C.POINTER(MsdAttentionIdentity), C.c_void_p]),
+    "msd_attention_joint": (C.c_int, [C.POINTER(MsdAttentionJoint), C.c_void_p]),
+    "msd_reference_latent": (C.c_int, [C.POINTER(MsdReferenceLatent), C.c_void_p]),
     "msd_add_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_add_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -528,7 +528,7 @@ class Emitter:
         return out
 
     def attentions(self, x: Act, name, ctx_kv, ctx_len, heads=8, free_input=False, shared: int = 1, perturbed: int = 0,
-                   regions: int = 0, region_rows: int = 0, region_w=None) -> Act:
+                   regions: int = 0, region_rows: int = 0, region_w=None, reference: int = 0, mix=None) -> Act:
         """Attentions / TransformerBlock / CrossAttention / GEGLU (diffusion_model.py:54-153).  shared > 1 (SHARE_CFG_PREFIX): `x` holds
         `shared` identical copies of x.B / shared samples (the cond and uncond halves in front of the first cross-attention): norm,
         proj_in, q|k|v, the self-attention and its to_out run on ONE copy, their result (rows + LayerNorm partials) is replicated, and the
@@ -540,9 +540,16 @@ class Emitter:
         rows of the batch are the conditional rows and ctx_kv holds B_u + R * region_rows context rows - the unconditional rows'
         first, then the regions', region-major.  attn2 then takes the unfused route: q from attn2.to_q, msd_attention for the
         unconditional rows, ONE msd_region_attention launch for the conditional rows with the weight plane `region_w`
-        (fp32 [R][H * W], this level's).  regions = 0 records exactly the plain block."""
+        (fp32 [R][H * W], this level's).  regions = 0 records exactly the plain block.
+        reference = 1 (reference-only control, minsdtf_amd/reference.py): the LAST row of `x` is the reference row.  attn1 of the
+        rows in front of it is ONE msd_attention_joint launch - own keys, then the reference row's (k_ref / vt_ref are views of the
+        same k / vt buffers at row B - 1), blended with the plain result by `mix` (fp32 [B - 1], or None) - and the reference row
+        takes one msd_attention with batch = 1 at the offset pointers.  Not with shared > 1, perturbed or regions.  reference = 0
+        records exactly the plain block."""
         p = self.p
         x_all = x
+        if reference not in (0, 1) or (reference and (shared > 1 or perturbed or regions or x.B < 2)):
+            raise ValueError(f"{name}: reference = {reference} with {x.B} rows (shared = {shared}, perturbed = {perturbed}, regions = {regions})")
         if not 0 <= perturbed <= x.B or (perturbed and shared > 1):
             raise ValueError(f"{name}: {perturbed} perturbed rows of {x.B} (shared = {shared})")
         if shared > 1:
@@ -568,7 +575,17 @@ class Emitter:
             self.conv(n1, tb + ".attn1.qkv", 3 * C, bias=False, split=(C, C, q.buf, k.buf, vt, sp))
             p.free(n1)
         a1 = p.act(B, H, Wd, C)
-        if perturbed < B:
+        if reference:
+            if d not in (40, 80, 160):
+                raise ValueError(f"{name}: reference-only attention at head size {d}")
+            g_rows = B - 1   # the generated rows; row B - 1 is the reference
+            p.rec(ops.attention_joint, q=q.buf, k=k.buf, vt=vt, k_ref=k.buf.at(g_rows * S * C * 2), vt_ref=vt.at(g_rows * C * sp * 2),
+                  mix=mix, out=a1.buf, batch=g_rows, heads=heads, head_dim=d, s=S, t=S, t_ref=S, q_ld=C, k_ld=C, vt_ld=sp, o_ld=C,
+                  name=tb + ".attn1.joint")
+            p.rec(ops.attention, q=q.buf.at(g_rows * S * C * 2), k=k.buf.at(g_rows * S * C * 2), vt=vt.at(g_rows * C * sp * 2),
+                  out=a1.buf.at(g_rows * S * C * 2), batch=1, heads=heads, head_dim=d, s=S, t=S, q_ld=C, k_ld=C, vt_ld=sp, o_ld=C,
+                  scale=d ** -0.5, q_prescaled=True, name=tb + ".attn1")
+        elif perturbed < B:
             p.rec(ops.attention, q=q.buf, k=k.buf, vt=vt, out=a1.buf, batch=B - perturbed, heads=heads, head_dim=d, s=S, t=S, q_ld=C,
                   k_ld=C, vt_ld=sp, o_ld=C, scale=d ** -0.5, q_prescaled=True, name=tb + ".attn1")
         if perturbed:   # the last `perturbed` rows: out = V
@@ -749,12 +766,15 @@ def _region_kw(region_attn, x: Act) -> dict:
 
 
 def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1,
-                  pag_layers=frozenset(), perturbed: int = 0, region_attn=None) -> Act:
+                  pag_layers=frozenset(), perturbed: int = 0, region_attn=None, ref_kw=None) -> Act:
     """Down path + mid block shared by the UNet (diffusion_model.py:193-229) and the ControlNet.  shared > 1: `x` (conv_in's output) is
     `shared` identical copies of x.B / shared samples - the first ResBlock and the front of the first transformer block run on one.
-    pag_layers / perturbed: the attention blocks (by name) whose attn1 is the identity for the last `perturbed` rows."""
+    pag_layers / perturbed: the attention blocks (by name) whose attn1 is the identity for the last `perturbed` rows.
+    ref_kw: block name -> Emitter.attentions' reference keywords (emit_unet's `reference`; shared is 1 then)."""
     def pert(block):
         return perturbed if block in pag_layers else 0
+
+    ref_kw = ref_kw or (lambda block: {})
 
     for lvl, ch in enumerate(wtab.UNET_CH):
         for r in range(2):
@@ -769,20 +789,21 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
             x = e.res_block(x, name, ch, temb=temb_of(name))
             if lvl < 3:
                 blk = f"down_blocks.{lvl}.attentions.{r}"
-                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=pert(blk), **_region_kw(region_attn, x))
+                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=pert(blk), **_region_kw(region_attn, x), **ref_kw(blk))
             outputs.append(x)
         if lvl < 3:
             x = e.conv(x, f"down_blocks.{lvl}.downsamplers.0.conv", ch, ksize=3, stride=2)
             outputs.append(x)
     x = e.res_block(x, "mid_block.resnets.0", 1280, temb=temb_of("mid_block.resnets.0"))
     x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True, perturbed=pert("mid_block.attentions.0"),
-                     **_region_kw(region_attn, x))
+                     **_region_kw(region_attn, x), **ref_kw("mid_block.attentions.0"))
     x = e.res_block(x, "mid_block.resnets.1", 1280, temb=temb_of("mid_block.resnets.1"), free_input=True)
     return x
 
 
 def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w: int, temb, ctx_kv, ctx_len: int,
-              eps_out_f32, controls=None, control_taps=None, pag_layers=None, perturbed: int = 0, region_attn=None) -> None:
+              eps_out_f32, controls=None, control_taps=None, pag_layers=None, perturbed: int = 0, region_attn=None, *,
+              reference=None) -> None:
     """DiffusionModel graph (diffusion_model.py:184-279).
 
     region_attn = (R, rows, {(h_l, w_l): fp32 plane [R][h_l * w_l]}) (regional prompting inside cross-attention): the last `rows` of
@@ -791,6 +812,12 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
 
     pag_layers (a set of attention block names, PAG_LAYERS) / perturbed: the last `perturbed` of the NB rows run those blocks'
     self-attention with the identity map (Emitter.attentions); perturbed = 0 records exactly the plain forward.
+
+    reference = (layers, ref_latent_f32, mix) (reference-only control, minsdtf_amd/reference.py): the LAST of the NB rows is the
+    reference row - conv_in reads it from ref_latent_f32 (fp32 [1][h][w][4]) in a launch of its own - and in the attention blocks
+    named in `layers` the rows in front of it attend to its keys too (Emitter.attentions; mix: fp32 [NB - 1] or None).  Nothing is
+    shared across the copies of such a job.  Not with pag_layers, region_attn or ControlNet residuals.  None records exactly the
+    plain forward.
 
     latent_f32: fp32 [latent_batch_mod][h][w][4] (sample b reads row b % latent_batch_mod);
     temb = (table, step_stride, batch_stride, {resblock: column}); eps_out_f32: fp32 [NB][h][w][4].
@@ -808,10 +835,23 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
     def temb_of(name):
         return (table.at(cols[name] * 4), sstride, bstride)
 
+    ref_layers = frozenset()
+    if reference is not None:
+        ref_layers, ref_latent, ref_mix = reference
+        ref_layers = frozenset(ref_layers)
+        if not ref_layers or ref_layers - set(PAG_LAYERS):
+            raise ValueError(f"emit_unet: reference layers {sorted(ref_layers)} (a non-empty subset of PAG_LAYERS)")
+        if NB < 2 or perturbed or region_attn or controls is not None or control_taps is not None:
+            raise ValueError("emit_unet: a reference row goes with at least one generated row and not with pag, regions or a ControlNet")
     x = p.act(NB, h, w, 320)
-    p.rec(ops.conv_direct, x=latent_f32, w=e.W["conv_in.w"], bias=e.W["conv_in.b"], out=x.buf, batch=NB,
+    gen = NB - 1 if reference is not None else NB   # the rows conv_in reads from latent_f32
+    p.rec(ops.conv_direct, x=latent_f32, w=e.W["conv_in.w"], bias=e.W["conv_in.b"], out=x.buf, batch=gen,
           in_batch_mod=latent_batch_mod, h_in=h, w_in=w, c_in=4, c_out=320, ksize=3, in_dtype=ops.OUT_F32,
           out_dtype=ops.OUT_BF16, name="conv_in")
+    if reference is not None:
+        p.rec(ops.conv_direct, x=ref_latent, w=e.W["conv_in.w"], bias=e.W["conv_in.b"], out=x.buf.at(gen * h * w * 320 * 2), batch=1,
+              in_batch_mod=1, h_in=h, w_in=w, c_in=4, c_out=320, ksize=3, in_dtype=ops.OUT_F32, out_dtype=ops.OUT_BF16,
+              name="conv_in.reference")
     outputs: List[Act] = [x]
     # (conv_in itself stays on the whole batch: every row reads latent row b % latent_batch_mod, a 10-us launch whose output is skip 0)
     shared = NB // latent_batch_mod if (SHARE_CFG_PREFIX and latent_batch_mod > 0 and NB % latent_batch_mod == 0) else 1
@@ -822,8 +862,14 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
         # the first block's front is no longer identical across the copies: nothing is shared (exact either way - a sample's bits
         # do not depend on its batch)
         shared = 1
+    if reference is not None:
+        shared = 1   # the reference row is no copy of anything
+
+    def ref_kw(block):
+        return dict(reference=1, mix=ref_mix) if block in ref_layers else {}
+
     x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared, pag_layers=pag_layers, perturbed=perturbed,
-                      region_attn=region_attn)
+                      region_attn=region_attn, ref_kw=ref_kw)
     p.mark("controls")   # everything above is independent of the ControlNet (its encoder may run beside it on another stream)
     if control_taps is not None:
         e_c, feats = control_taps
@@ -845,7 +891,7 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
             if lvl < 3:
                 blk = f"up_blocks.{ui}.attentions.{r}"
                 x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=perturbed if blk in pag_layers else 0,
-                                 **_region_kw(region_attn, x))
+                                 **_region_kw(region_attn, x), **ref_kw(blk))
         if lvl > 0:
             y = e.conv(x, f"up_blocks.{ui}.upsamplers.0.conv", ch, ksize=3, upsample=True)
             p.free(x)

@@ -254,15 +254,20 @@ class DiffusionModel(HipModel):
         self.apply_control_net = apply_control_net
         self._maybe_load(ckpt_path, lora_dict)
 
-    def _build(self, B: int, T: int, with_controls: bool, pag_layers=None, regions: int = 0) -> _BoundPlan:
+    def _build(self, B: int, T: int, with_controls: bool, pag_layers=None, regions: int = 0, reference=None) -> _BoundPlan:
         """pag_layers: the attention blocks whose self-attention is the identity map for ALL B rows (predict_perturbed).
         regions = R: all B rows are conditional rows over R region contexts (predict_regional): the context input is
-        (R * B, T, 768), region-major, and `region_w` the four levels' weight planes (regions.pack_levels)."""
+        (R * B, T, 768), region-major, and `region_w` the four levels' weight planes (regions.pack_levels).
+        reference = the attention blocks of a reference-only forward (predict_reference): the plan runs B + 1 rows, the last one the
+        reference row read from `ref_latent`; `t_emb` and `context` carry its row last, `ref_mix` is fp32 [B]; eps keeps B rows."""
         h, w = self.h, self.w
+        NB = B + 1 if reference else B
         plan = engine.Plan(self.device)
         e = engine.Emitter(plan, self._W)
-        CB = (regions or 1) * B   # context rows
-        shapes = dict(latent=(B, h, w, 4), t_emb=(B, 320), context=(CB, T, 768))
+        CB = (regions or 1) * B + (1 if reference else 0)   # context rows
+        shapes = dict(latent=(B, h, w, 4), t_emb=(NB, 320), context=(CB, T, 768))
+        if reference:
+            shapes.update(ref_latent=(1, h, w, 4), ref_mix=(B,))
         region_attn = None
         if regions:
             from . import regions as regions_mod
@@ -278,8 +283,8 @@ class DiffusionModel(HipModel):
         ctx_kv = engine.emit_context_kv(e, ctx16, engine.UNET_ATTN_LAYERS, plan)
         cols = engine.temb_columns(False)
         total = sum(c for _, c in engine.resblock_names(False))
-        table = plan.alloc(B * total * 4)
-        engine.emit_time_embedding(e, ins["t_emb"], B, table, encoder_only=False)
+        table = plan.alloc(NB * total * 4)
+        engine.emit_time_embedding(e, ins["t_emb"], NB, table, encoder_only=False)
         controls, cstage = None, []
         if with_controls:   # fp32 staging buffers; emit_unet adds them to the skips in fp32 (one add-and-round launch each)
             controls = []
@@ -288,13 +293,14 @@ class DiffusionModel(HipModel):
                 st = plan.alloc(B * hh * ww * ch * 4)
                 cstage.append((st, (B, hh, ww, ch)))
                 controls.append(st)
-        eps = plan.alloc(B * h * w * 4 * 4)
-        engine.emit_unet(e, ins["latent"], B, B, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls,
-                         pag_layers=pag_layers, perturbed=B if pag_layers else 0, region_attn=region_attn)
+        eps = plan.alloc(NB * h * w * 4 * 4)
+        extra = dict(reference=(reference, ins["ref_latent"], ins["ref_mix"])) if reference else {}
+        engine.emit_unet(e, ins["latent"], B, NB, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls,
+                         pag_layers=pag_layers, perturbed=B if pag_layers else 0, region_attn=region_attn, **extra)
         plan.finalize()
         bp = _BoundPlan(plan, self._use_graph)
         bp.io = {k: b.tensor(torch.float32, shapes[k]) for k, b in ins.items()}
-        bp.io["eps"] = eps.tensor(torch.float32, (B, h, w, 4))
+        bp.io["eps"] = eps.tensor(torch.float32, (NB, h, w, 4))
         for i, (st, shp) in enumerate(cstage):
             bp.io[f"control.{i}"] = st.tensor(torch.float32, shp)
         return bp
@@ -342,6 +348,38 @@ class DiffusionModel(HipModel):
         bp.io["region_w"].copy_(torch.from_numpy(regions_mod.pack_levels(planes)))
         bp.run()
         return bp.host("eps")
+
+    def predict_reference(self, x, ref_latent_t, layers, mix, ref_context=None):
+        """predict_on_batch([latent, t_emb, context]) with one more row, the reference latent `ref_latent_t` (1, h, w, 4) ALREADY
+        noised to this step's level, whose keys the self-attention of the attention blocks `layers` (names of engine.PAG_LAYERS)
+        also attends to (msd_attention_joint; minsdtf_amd/reference.py).  `mix`: the share of the plain self-attention in each
+        row's result, a float or (B,) values in [0, 1].  The reference row takes t_emb[0] and `ref_context` (T, 768) or (1, T, 768)
+        (default: context[0]).  Returns the B rows' prediction; a bound plan of its own per (rows, T, layer set)."""
+        layers = frozenset([layers] if isinstance(layers, str) else layers)
+        if not layers or layers - set(engine.PAG_LAYERS):
+            raise ValueError(f"predict_reference: layers {sorted(layers)} (a non-empty subset of engine.PAG_LAYERS)")
+        if len(x) != 3:
+            raise ValueError("predict_reference takes [latent, t_emb, context] (no control tensors)")
+        latent, t_emb, context = _np32(x[0]), _np32(x[1]), _np32(x[2])
+        ref = _np32(ref_latent_t)
+        B, T = latent.shape[0], context.shape[1]
+        if latent.shape[1:] != (self.h, self.w, 4) or ref.shape != (1, self.h, self.w, 4):
+            raise ValueError(f"latent shape {latent.shape} / reference latent shape {ref.shape} do not match the model ({self.h},{self.w},4)")
+        rc = context[:1] if ref_context is None else _np32(ref_context).reshape(1, -1, 768)
+        if rc.shape[1] != T:
+            raise ValueError(f"predict_reference: the reference row's context has {rc.shape[1]} tokens, the rows' {T}")
+        m = np.broadcast_to(np.asarray(mix, dtype=np.float32), (B,))
+        if not ((m >= 0.0) & (m <= 1.0)).all():
+            raise ValueError("predict_reference: mix in [0, 1]")
+        key = (B + 1, T, False, ("reference", tuple(sorted(layers))))
+        bp = self._bound(key, lambda: self._build(B, T, False, reference=layers))
+        bp.io["latent"].copy_(torch.from_numpy(latent))
+        bp.io["t_emb"].copy_(torch.from_numpy(np.concatenate([t_emb, t_emb[:1]], axis=0)))
+        bp.io["context"].copy_(torch.from_numpy(np.concatenate([context, rc], axis=0)))
+        bp.io["ref_latent"].copy_(torch.from_numpy(ref))
+        bp.io["ref_mix"].copy_(torch.from_numpy(np.ascontiguousarray(m)))
+        bp.run()
+        return bp.host("eps")[:B]
 
     def _predict(self, x, pag_layers):
         latent, t_emb, context = _np32(x[0]), _np32(x[1]), _np32(x[2])

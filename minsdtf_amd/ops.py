@@ -252,6 +252,30 @@ def attention_identity(*, vt, out, batch, channels, s, vt_ld, o_ld, name="attent
     return Call(lib.msd_attention_identity, (C.byref(a),), name, keep=a)
 
 
+def attention_joint(*, q, k, vt, k_ref, vt_ref, out, batch, heads, head_dim, s, t, t_ref, q_ld, k_ld, vt_ld, o_ld, mix=None,
+                    name="attention_joint") -> Call:
+    """msd_attention_joint: out[b] = mix[b] * softmax(q[b] k[b]^T) v[b] + (1 - mix[b]) * softmax(q[b] [k[b] ; k_ref]^T) [v[b] ; v_ref]
+    - the generated rows of a reference-only job.  q bf16 [batch][s][q_ld] carrying scale * log2(e), k bf16 [batch][t][k_ld], vt bf16
+    [batch][heads * head_dim][vt_ld], k_ref bf16 [t_ref][k_ld] and vt_ref bf16 [heads * head_dim][vt_ld] (ONE row, shared by the
+    batch), mix fp32 [batch] or None (all 0), out bf16 [batch][s][o_ld]."""
+    lib = _lib.load()
+    a = _lib.MsdAttentionJoint()
+    a.q, a.k, a.vt, a.k_ref, a.vt_ref, a.mix, a.out = _p(q), _p(k), _p(vt), _p(k_ref), _p(vt_ref), _p(mix), _p(out)
+    a.batch, a.heads, a.head_dim, a.s, a.t, a.t_ref = int(batch), int(heads), int(head_dim), int(s), int(t), int(t_ref)
+    a.q_ld, a.k_ld, a.vt_ld, a.o_ld = int(q_ld), int(k_ld), int(vt_ld), int(o_ld)
+    return Call(lib.msd_attention_joint, (C.byref(a),), name, keep=a)
+
+
+def reference_latent(*, z, noise, coef, out, n, num_steps, step_ptr=None, name="reference_latent") -> Call:
+    """msd_reference_latent: out = coef[step][0] * z + coef[step][1] * noise (one fp32 FMA per element), step = *step_ptr.  z / noise /
+    out fp32 [n], coef fp32 [num_steps][2] (reference.rates)."""
+    lib = _lib.load()
+    r = _lib.MsdReferenceLatent()
+    r.z, r.noise, r.coef, r.step_ptr, r.out = _p(z), _p(noise), _p(coef), _p(step_ptr), _p(out)
+    r.n, r.num_steps = int(n), int(num_steps)
+    return Call(lib.msd_reference_latent, (C.byref(r),), name, keep=r)
+
+
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:
     lib = _lib.load()
     return Call(lib.msd_add_bf16, (_p(a), _p(b), _p(out), n), name)

@@ -35,6 +35,7 @@ import torch
 from . import _lib, engine, ops
 from . import hires as hires_mod
 from . import pag as pag_mod
+from . import reference as reference_mod
 from . import regions as regions_mod
 from . import samplers as smp
 from . import tiled as tiled_mod
@@ -73,11 +74,14 @@ class DenoiseEngine:
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
-                 sampler=None, tiled=None, regions: int = 0, pag=None, region_mode: str = "latent"):
+                 sampler=None, tiled=None, regions: int = 0, pag=None, region_mode: str = "latent", reference=None):
         unet._require_weights()
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
-        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag, region_mode)
+        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag, region_mode, reference)
+        if self.reference and guidance > 0.0 and t_cond != t_uncond:
+            raise ValueError("reference_only: the negative prompt must have the conditional context's token length "
+                             f"({t_uncond} != {t_cond} tokens): the reference row rides in the one fused pass")
         self.use_graph = use_graph
         self.guidance = float(guidance)
         self.cfg = cfg = guidance > 0.0
@@ -100,6 +104,9 @@ class DenoiseEngine:
             passes = [(0, (1 + RC) * B, t_cond, "both")]
         else:
             passes = [(0, B, t_uncond, "uncond"), (B, RC * B, t_cond, "cond")]
+        if self.reference:   # one more row, the reference, last in the one pass
+            (row0, nb, t, tag), = passes
+            passes = [(row0, nb + 1, t, tag)]
         self.passes = passes
         self.has_control = control_net is not None
         prep = self._build_prep(control_net, hint_net)
@@ -121,9 +128,10 @@ class DenoiseEngine:
         self._warmed = False
         _lib.track_graph_owner(self)
 
-    def _check_options(self, control_net, streams, inpaint, tcd, sampler, tiled, regions, pag=None, region_mode="latent") -> None:
+    def _check_options(self, control_net, streams, inpaint, tcd, sampler, tiled, regions, pag=None, region_mode="latent",
+                       reference=None) -> None:
         """The option combinations an engine refuses (generate_image refuses them earlier, by argument name: _REFUSED; these guard
-        direct construction).  Sets `sampler`, `tiled`, `regions` and `pag`."""
+        direct construction).  Sets `sampler`, `tiled`, `regions`, `pag` and `reference`."""
         # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
         # the 8-wide coefficient rows, the previous denoised estimate and (stochastic samplers) per-step draws on the device
         self.sampler = smp.parse(sampler)
@@ -164,6 +172,18 @@ class DenoiseEngine:
                 raise ValueError(f"pag: unknown layer(s) {sorted(unknown)}")
             if control_net is not None or inpaint or tiled is not None or R or streams == 2:
                 raise ValueError("pag: text-to-image on one stream only (no ControlNet, inpainting, tiled, regions, denoise_streams = 2)")
+        # reference (the set of attention blocks of a reference-only job, or None): the one fused pass carries one more row behind
+        # the u and c rows, the reference latent noised to the step's level (msd_reference_latent at the head of the step plan);
+        # in the selected blocks the rows in front of it attend to its keys too (msd_attention_joint, `ref_mix` per row).  The step
+        # kernels still read eps as [2B][n]: the reference row's prediction is written and never read (minsdtf_amd/reference.py)
+        self.reference = frozenset(reference) if reference else None
+        if self.reference:
+            unknown = self.reference - set(engine.PAG_LAYERS)
+            if unknown:
+                raise ValueError(f"reference_only: unknown layer(s) {sorted(unknown)}")
+            if control_net is not None or inpaint or tcd or tiled is not None or R or self.pag or streams == 2:
+                raise ValueError("reference_only: text-to-image on one stream only (no ControlNet, inpainting, TCD, tiled, regions, pag, "
+                                 "denoise_streams = 2)")
 
     def _build_prep(self, control_net, hint_net) -> dict:
         """The preparation plans: per SCHEDULE the time-embedding tables (timestep -> MLP -> every ResBlock's projection: they do
@@ -227,7 +247,12 @@ class DenoiseEngine:
         dev = unet.device
         n = h * w * 4
         RC = 1 if self.region_attn else (R or (2 if self.pag else 1))
-        self.eps = torch.zeros(((1 + RC) * B if self.cfg else RC * B), n, dtype=torch.float32, device=dev)
+        self.eps = torch.zeros(((1 + RC) * B if self.cfg else RC * B) + (1 if self.reference else 0), n, dtype=torch.float32, device=dev)
+        self.ref_z = self.ref_noise = self.ref_latent = self.ref_coef = self.ref_mix = None
+        if self.reference:
+            self.ref_z, self.ref_noise, self.ref_latent = (torch.zeros(1, h, w, 4, dtype=torch.float32, device=dev) for _ in range(3))
+            self.ref_coef = torch.zeros(self.num_steps, 2, dtype=torch.float32, device=dev)
+            self.ref_mix = torch.zeros((2 if self.cfg else 1) * B, dtype=torch.float32, device=dev)
         self.region_w = torch.zeros(R, h, w, dtype=torch.float32, device=dev) if R else None
         region_planes = None
         if self.region_attn:   # one buffer for the four levels' planes [R][h_l * w_l] (regions.pack_levels)
@@ -265,6 +290,10 @@ class DenoiseEngine:
             extra = dict(pag_layers=self.pag, perturbed=B) if self.pag and tag != "uncond" else {}
             if self.region_attn and tag != "uncond":   # the conditional rows are the last B rows of their pass
                 extra = dict(region_attn=(R, B, region_planes))
+            if self.reference:   # x_r of this step first, then the forward whose last row reads it
+                step.rec(ops.reference_latent, z=self.ref_z, noise=self.ref_noise, coef=self.ref_coef, step_ptr=self.step_ptr,
+                         out=self.ref_latent, n=n, num_steps=self.num_steps)
+                extra = dict(reference=(self.reference, self.ref_latent, self.ref_mix))
             engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps, **extra)
         return step
 
@@ -353,6 +382,8 @@ class DenoiseEngine:
                 context = np.concatenate([np.asarray(c, dtype=np.float32) for c in context], axis=0)
         if getattr(self, "pag", None):   # the p rows read the conditional context again
             context = torch.cat([context, context], dim=0) if isinstance(context, torch.Tensor) else np.concatenate([context, context], axis=0)
+        if getattr(self, "reference", None):   # the reference row reads the conditional context of sample 0
+            context = torch.cat([context, context[:1]], dim=0) if isinstance(context, torch.Tensor) else np.concatenate([context, context[:1]], axis=0)
         if not self.cfg:
             return {"cond": context}
         if len(self.passes) == 1:
@@ -441,7 +472,7 @@ class DenoiseEngine:
 
     def prepare(self, contexts: Dict[str, np.ndarray], noise: np.ndarray, scheduler: Scheduler, timesteps,
                 start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None,
-                regions=None, pag_scale=None) -> None:
+                regions=None, pag_scale=None, reference=None) -> None:
         """Upload the per-call inputs and run the preparation plan.  Every array may be a host array or a (device) tensor.
         noise = None: the start latent is already in `self.latent` (written there by stream-ordered device work queued before
         this call: the hand-off of a hires job), nothing is uploaded for it.
@@ -453,7 +484,19 @@ class DenoiseEngine:
         regions = the normalised weights (R, h, w) of a regional engine (regions.weights): a per-call upload, like the inpaint mask;
         an attention-mode engine takes the four levels' planes as one flat array (regions.pack_levels of Resolved.level_weights).
         pag_scale = the scale s of a PAG engine: the two planes fp32(1 + k), fp32(-k) (pag.weights, k from s and the engine's
-        guidance in float64) are a per-call upload too, so another scale needs no other engine."""
+        guidance in float64) are a per-call upload too, so another scale needs no other engine.
+        reference = (z_ref (1, h, w, 4), n_ref (1, h, w, 4), fidelity) of an engine built with reference=<layers>: the two latents,
+        the rate table of this schedule and start index (reference.rates) and mix = [fidelity] * B + [0] * B are per-call uploads."""
+        if (reference is None) != (self.ref_mix is None):
+            raise ValueError("prepare: `reference` goes with an engine built with reference=<layers>, and only with one")
+        if self.ref_mix is not None:
+            z_ref, n_ref, fidelity = reference
+            self.ref_z.copy_(_f32_tensor(z_ref).reshape(self.ref_z.shape))
+            self.ref_noise.copy_(_f32_tensor(n_ref).reshape(self.ref_noise.shape))
+            rates = reference_mod.rates(sampler if self.sampler is not None else scheduler, int(start_index))
+            self.ref_coef.copy_(torch.from_numpy(rates.astype(np.float32)))
+            mix = [float(fidelity)] * self.B + [0.0] * self.B if self.cfg else [0.0] * self.B
+            self.ref_mix.copy_(torch.tensor(mix, dtype=torch.float32))
         if (pag_scale is None) != (self.pag_w is None):
             raise ValueError("prepare: `pag_scale` goes with an engine built with pag=<layers>, and only with one")
         if self.pag_w is not None:
@@ -575,17 +618,17 @@ class StableDiffusionBase:
     # ---- public entry points (reference :84-139)
     def text_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                       embedding=None, negative_embedding=None, seed=None, control_net_image=None, guidance_rescale=0.7,
-                      callback=None, hires=None, tiled=None, regions=None, pag=None, **kw):
+                      callback=None, hires=None, tiled=None, regions=None, pag=None, reference_only=None, **kw):
         """``hires``: None, or a hires.HiresSpec / dict for the two-pass hires fix; ``tiled``: None, or a tiled.TiledSpec / dict
         for tiled diffusion on a canvas larger than the pipeline's size; ``regions``: None, or a regions.Regions / dict for
         regional prompting, `prompt` being the base prompt; ``pag``: None, or a pag.PagSpec / dict for perturbed-attention
-        guidance (see generate_image)."""
+        guidance; ``reference_only``: None, or a reference.ReferenceSpec / dict for reference-only control (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
                                    negative_embedding=negative_embedding, control_net_image=control_net_image,
                                    guidance_rescale=guidance_rescale, callback=callback, hires=hires, tiled=tiled, regions=regions,
-                                   pag=pag, **kw)
+                                   pag=pag, reference_only=reference_only, **kw)
 
     def image_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
@@ -818,7 +861,7 @@ class StableDiffusionBase:
                        diffusion_noise=None, seed=None, negative_embedding=None, control_net_image=None, inpaint_mask=None,
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
                        callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None,
-                       tiled=None, regions=None, pag=None):
+                       tiled=None, regions=None, pag=None, reference_only=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
@@ -849,9 +892,23 @@ class StableDiffusionBase:
         msd_region_combine launch writes c' = (1 + k) c - k p over the conditional rows (k = s / g, or s without guidance) in front of
         the guidance / sampler step, so `guidance_rescale` takes its reference std from c'.  ``layers``: "mid" or names of
         engine.PAG_LAYERS.  scale = 0 is the plain job.  Works with every sampler, on a TCD pipeline, with shard_batch and with
-        host_loop=True; at most 2 * tiled.MAX_VIEW_BATCH UNet rows (3 * batch_size with guidance, 2 * batch_size without)."""
+        host_loop=True; at most 2 * tiled.MAX_VIEW_BATCH UNet rows (3 * batch_size with guidance, 2 * batch_size without).
+        ``reference_only`` (a reference.ReferenceSpec or a dict {"image" or "latent", "fidelity": 0.5, "layers": "all", "noise"}; txt2img
+        only): reference-only control - the picture follows the subject / style of a reference image with no extra network.  Every
+        step the UNet runs one more row, the reference latent noised to the step's level, and in the selected attention blocks the
+        generated rows' self-attention also attends to that row's keys (one msd_attention_joint launch per block); ``fidelity`` is
+        the share of the plain self-attention in the unconditional rows (diffusers' style_fidelity).  (`reference_image` is
+        image_to_image's start picture, another thing.)  Works with every sampler, with shard_batch and with host_loop=True; at most
+        2 * tiled.MAX_VIEW_BATCH UNet rows (2 * batch_size + 1); the negative prompt has the prompt's token length."""
         given = dict(tiled=tiled, hires=hires, control_net_image=control_net_image, reference_image=reference_image,
-                     inpaint_mask=inpaint_mask, regions=regions)
+                     inpaint_mask=inpaint_mask, regions=regions, pag=pag)
+        ref = reference_mod.parse(reference_only)   # (ValueError for a bad description)
+        if ref is not None:
+            self._refuse_combinations("reference_only", given, host_loop)
+            rows = 2 * int(batch_size) + 1
+            if rows > 2 * tiled_mod.MAX_VIEW_BATCH:
+                raise ValueError(f"reference_only: {batch_size} image(s) are {rows} UNet rows per step, more than 2 * tiled.MAX_VIEW_BATCH "
+                                 f"= {2 * tiled_mod.MAX_VIEW_BATCH}: use a smaller batch")
         pg = pag_mod.parse(pag)   # (ValueError for a bad description)
         if pg is not None and pg.scale == 0.0:
             pg = None   # (c' = c: the plain job, on the plain engine)
@@ -933,6 +990,12 @@ class StableDiffusionBase:
             start_latent = sched.entry_latent(start_index, encoded, noise)
         hint = self._hint_batch(control_net_image, B)
         g, phi = float(unconditional_guidance_scale), float(guidance_rescale)
+        ref_in = None
+        if ref is not None:
+            if g > 0.0 and unconditional_context.shape[1] != context.shape[1]:
+                raise ValueError("reference_only: the negative prompt must have the conditional context's token length "
+                                 f"({unconditional_context.shape[1]} != {context.shape[1]} tokens)")
+            ref_in = self._reference_inputs(ref, noise.shape[1], noise.shape[2], seed)   # (z_ref, n_ref), each (1, h, w, 4)
         region_ctx = region_w = None
         if reg is not None:
             region_ctx, region_w = self._region_inputs(reg, context)   # (R', T, 768) without the base prompt, (R, h, w)
@@ -956,10 +1019,12 @@ class StableDiffusionBase:
             ip = (encoded, noise, latent_mask[0]) if inpainting else None
             if spec is not None:
                 latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
-                                                 sampler_z, ip, region_w=region_w, pag=pg)
+                                                 sampler_z, ip, region_w=region_w, pag=pg,
+                                                 reference=None if ref is None else (ref, ref_in, reference_mod.rates(sched, start_index)))
             else:
                 latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending, ip,
-                                         region_w=region_w, pag=pg)
+                                         region_w=region_w, pag=pg,
+                                         reference=None if ref is None else (ref, ref_in, reference_mod.rates(self.scheduler, start_index)))
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
             return finish(self.image_decoder.predict_on_batch(latent))
@@ -981,6 +1046,8 @@ class StableDiffusionBase:
             per_sample["sampler_z"] = sampler_z.reshape(B, num_steps, -1)
         if reg is not None:   # one context per region and the weights: whole on every rank
             shared["region_ctx"], shared["region_w"] = region_ctx, region_w
+        if ref is not None:   # the reference latent and its draw: whole on every rank, every rank runs its own reference row
+            shared["ref_z"], shared["ref_noise"] = ref_in
         sname = None if spec is None else spec.name
 
         def local(c, u, z, a):
@@ -992,10 +1059,12 @@ class StableDiffusionBase:
                 c = ([c] if reg.base_weight > 0.0 else []) + [rep(rc[i]) for i in range(rc.shape[0])]
             eng = self._denoise_pass(u, c, z, num_steps, g, phi, start_index, run_steps, callback,
                                      dict(sampler=sname, regions=None if reg is None else len(c), pag=None if pg is None else pg.key,
-                                          region_mode="attention" if reg is not None and reg.mode == "attention" else None),
+                                          region_mode="attention" if reg is not None and reg.mode == "attention" else None,
+                                          reference=None if ref is None else ref.key),
                                      dict(hint_image=a.get("hint"), inpaint=(a["encoded"], a["noise"], a["mask"]) if inpainting else None,
                                           step_noise=a.get("tcd") if spec is None else a.get("sampler_z"), sampler=sched,
-                                          regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale))
+                                          regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale,
+                                          reference=None if ref is None else (a["ref_z"], a["ref_noise"], ref.fidelity)))
             if return_latent:
                 return eng.latent
             if blend_pixels:   # pixel blend in fp32 before the uint8 cast
@@ -1015,6 +1084,9 @@ class StableDiffusionBase:
                   ("host_loop=True", "a TCD pipeline (active_tcd=True)")),
         "pag": ("text-to-image on one stream only", ("regions", "tiled", "hires", "control_net_image", "reference_image", "inpaint_mask"),
                 ("denoise_streams = 2",)),
+        "reference_only": ("text-to-image on one stream only",
+                           ("regions", "pag", "tiled", "hires", "control_net_image", "reference_image", "inpaint_mask"),
+                           ("a TCD pipeline (active_tcd=True)", "denoise_streams = 2")),
     }
 
     def _refuse_combinations(self, kind, given: dict, host_loop) -> None:
@@ -1025,6 +1097,21 @@ class StableDiffusionBase:
         refused = [n for n in arguments if given[n] is not None] + [s for s in states if holds[s]]
         if refused:
             raise ValueError(f"{kind} is {what}: it cannot be combined with {', '.join(refused)}")
+
+    def _reference_inputs(self, ref, h, w, seed):
+        """(z_ref, n_ref) of a reference-only job, each (1, h, w, 4) float32: the given latent, or the picture through the VAE
+        encoder; the given draw, or reference.draw_noise (default_rng([seed, 3]), numpy's global stream without a seed)."""
+        if ref.latent is not None:
+            z = ref.latent
+        else:
+            _p01, picture11 = self.preprocessed_image(ref.image)
+            z = np.asarray(self.image_encoder.predict_on_batch(picture11), dtype=np.float32)
+        if tuple(z.shape) != (1, h, w, 4):
+            raise ValueError(f"reference_only: the reference latent has shape {tuple(z.shape)}, this job's is {(1, h, w, 4)}")
+        n = ref.noise if ref.noise is not None else reference_mod.draw_noise(h, w, seed)
+        if tuple(n.shape) != (1, h, w, 4):
+            raise ValueError(f"reference_only: noise has shape {tuple(n.shape)}, this job's reference latent is {(1, h, w, 4)}")
+        return np.ascontiguousarray(z, dtype=np.float32), np.ascontiguousarray(n, dtype=np.float32)
 
     def _sampler_inputs(self, spec, B, steps, h, w, seed, stream_key=1):
         """(the sampler's Schedule over `steps`, a stochastic sampler's per-step draws of the GLOBAL batch (B, steps, h, w, 4),
@@ -1212,7 +1299,9 @@ class StableDiffusionBase:
         # (a regional job: the NUMBER of evaluated region prompts only - masks, weights and prompts are per-call uploads)
         key = key if not regions else key + (("regions", int(regions)) + (("attention",) if opts.get("region_mode") == "attention" else ()),)
         # (a PAG job: the selected blocks only - the scale is a per-call upload)
-        return key if not opts.get("pag") else key + (("pag", tuple(sorted(opts["pag"]))),)
+        key = key if not opts.get("pag") else key + (("pag", tuple(sorted(opts["pag"]))),)
+        # (a reference-only job: the selected blocks only - the image, the draw and the fidelity are per-call uploads)
+        return key if not opts.get("reference") else key + (("reference", tuple(sorted(opts["reference"]))),)
 
     def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> DenoiseEngine:
         """The resident engine of this shape, built if need be.  `opts` are DenoiseEngine's: `sampler`; `unet`: the UNet of another
@@ -1221,7 +1310,7 @@ class StableDiffusionBase:
         alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is
         built: a re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than
         the job's own engines - one for a plain job, two for a hires job."""
-        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode"}:
+        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode", "reference"}:
             raise TypeError(f"_engine: unknown option among {sorted(opts)}")
         key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, **opts)
         keep = {key} | set(job_keys or ())
@@ -1241,22 +1330,25 @@ class StableDiffusionBase:
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
                                 streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=opts.get("sampler"),
                                 tiled=opts.get("tiled"), regions=opts.get("regions") or 0, pag=opts.get("pag"),
-                                region_mode=opts.get("region_mode") or "latent")
+                                region_mode=opts.get("region_mode") or "latent", reference=opts.get("reference"))
             self._engines[key] = eng
         return eng
 
     def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None,
-                   region_w=None, pag=None):
+                   region_w=None, pag=None, reference=None):
         """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479)."""
         if timesteps is None:
             timesteps = self.scheduler.timesteps[::-1]
         batch_size = latent.shape[0]
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
         iteration = 0
+        n_sched = len(self.scheduler.timesteps)
         for _index, timestep in list(enumerate(timesteps))[::-1]:
             latent_prev = latent
             t_emb = get_timestep_embedding(timestep, batch_size)
-            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag)
+            # (a reference-only job: the position of this evaluation in the descending schedule indexes its rate table)
+            ref_step = None if reference is None else reference + (n_sched - 1 - _index,)
+            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag, ref_step)
             latent = self.scheduler.step(latent, timestep, latent_prev)
             if inpaint is not None:   # reference :469-475
                 init_latent, noise, latent_mask = inpaint
@@ -1268,12 +1360,25 @@ class StableDiffusionBase:
                 callback(iteration)
         return latent
 
-    def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None):
+    def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None, reference=None):
         """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
         A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
         predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host); in mode "attention"
         `region_w` is the list of the four levels' planes and the conditional prediction is ONE predict_regional.  A PAG job passes
         its pag.Resolved: the conditional prediction becomes c' = (1 + k) c - k p, p from predict_perturbed (pag.combine_host)."""
+        if reference is not None:
+            # reference-only control: (reference.Resolved, (z_ref, n_ref), rate table, evaluation index).  x_r in the device kernel's
+            # arithmetic, then one predict_reference for the u rows (mix = fidelity) and one for the c rows (mix = 0)
+            ref, (z_ref, n_ref), rates, i = reference
+            x_r = reference_mod.reference_latent_host(z_ref, n_ref, rates[i])
+            rc = np.asarray(context[:1], dtype=np.float32)
+            c = self.diffusion_model.predict_reference([latent, t_emb, context], x_r, ref.layers, 0.0, ref_context=rc)
+            if g <= 0.0:
+                return c
+            u = self.diffusion_model.predict_reference([latent, t_emb, unconditional_context], x_r, ref.layers, ref.fidelity, ref_context=rc)
+            e = u + g * (c - u)
+            return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
+
         def predict(ctx):
             """The UNet's prediction for one context, through the ControlNet if there is a hint."""
             if hint is None:
@@ -1297,7 +1402,7 @@ class StableDiffusionBase:
         return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
 
     def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
-                           inpaint=None, region_w=None, pag=None):
+                           inpaint=None, region_w=None, pag=None, reference=None):
         """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`."""
         batch_size = latent.shape[0]
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
@@ -1306,7 +1411,8 @@ class StableDiffusionBase:
         prev = None
         for iteration, i in enumerate(range(start, sched.num_steps), start=1):
             t_emb = get_timestep_embedding(float(sched.timesteps[i]), batch_size)
-            e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint, region_w, pag)
+            e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint, region_w, pag,
+                                 None if reference is None else reference + (i,))
             z = step_noise[:, i] if step_noise is not None else None
             x, prev = smp.host_step(tab[i], x, e, prev, z)
             if inpaint is not None:   # the row's own alpha / sigma, as in the device kernel
