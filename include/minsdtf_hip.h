@@ -734,6 +734,50 @@ typedef struct MsdReferenceLatent {
 
 MSD_API int msd_reference_latent(const MsdReferenceLatent* p, msd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * msd_attention_windowed — HyperTile: self-attention inside non-overlapping rectangular windows of the h x w feature map
+ * (minsdtf_amd/hypertile.py).  The operands are those of msd_attention in its q_prescaled form, over the whole
+ * image, where the q|k|v GEMM wrote them: nothing is gathered.  An addition to ABI 12: nothing else changed.
+ *
+ *   q:   bf16 [batch][s][q_ld], s = h * w, head hd at columns [hd * d, (hd + 1) * d), d = head_dim; q MUST carry
+ *        scale * log2(e); q_ld >= heads * d
+ *   k:   bf16 [batch][s][k_ld]; k_ld >= heads * d
+ *   vt:  bf16 [batch][heads * d][vt_ld], key (token) index contiguous; vt_ld >= s; columns >= s are padding
+ *   out: bf16 [batch][s][o_ld]; columns >= heads * d of a row are not written
+ *
+ * Geometry: h % wh == 0, w % ww == 0, ww % 8 == 0; head_dim is 40, 80 or 160.  Token (y, x) (row y * w + x) belongs to window
+ * (y / wh, x / ww); inside a window queries and keys are numbered row-major, j -> (j / ww, j % ww), j < wh * ww.  Per sample,
+ * head and window
+ *   out = softmax(q k^T) v        over that window's wh * ww keys only
+ * in msd_attention_joint's pinned arithmetic with one key segment: the window's keys in ascending window-linear tiles of 64
+ * (the last tile partial when wh * ww % 64 != 0: its missing keys are staged as zeros and their scores masked); state m = -1e30,
+ * l = 0, O = 0; per tile m' = max(m, max score), a = exp2(m - m'), l = l * a, O = O * a, P = bf16(exp2(score - m')),
+ * l += sum P, O += sum P * v; out = bf16(O * (1 / l)).  A workgroup is 64 window-linear queries of one (sample, head, window).
+ *
+ * Pinned properties (tests/test_hypertile_gpu.py):
+ *   - The arithmetic of a window depends only on that window's tokens in window-linear order: a launch on the image gives, for
+ *     every window, bit for bit what a launch with h = wh, w = ww on that window's gathered tokens gives.
+ *   - Nothing outside a window is addressed for it: what other windows hold in q / k / vt, NaN included, never reaches a
+ *     window's output, and columns >= s of vt never reach any output.
+ *   - Nothing couples two samples: a sample's bits do not depend on its batch, and runs repeat.
+ *
+ * Both products run on MFMAs with K / V^T tiles staged in LDS; plain vector loads and stores, no atomics, no scratch buffer.
+ * Checked on the host, without a device: q / k / vt / out non-NULL and 16-byte aligned; head_dim in range; h, w, wh, ww >= 1
+ * with the three divisibilities above; batch and heads in 1 .. 65535; q_ld, k_ld, vt_ld and o_ld multiples of 8; q_ld, k_ld,
+ * o_ld >= heads * head_dim; vt_ld >= s; fewer than 2^31 workgroups; the extent of out apart from the extent of every input.
+ * Argument errors return MSD_E_ARG without launching.  Nothing is allocated; the launch is stream-ordered and capturable. */
+typedef struct MsdAttentionWindowed {
+    const void* q;
+    const void* k;
+    const void* vt;
+    void* out;
+    int32_t batch, heads, head_dim;
+    int32_t h, w, wh, ww;
+    int32_t q_ld, k_ld, vt_ld, o_ld;
+} MsdAttentionWindowed;
+
+MSD_API int msd_attention_windowed(const MsdAttentionWindowed* p, msd_stream_t stream);
+
 /* msd_add_bf16 — out = a + b elementwise on bf16. n % 8 == 0. */
 MSD_API int msd_add_bf16(const void* a, const void* b, void* out, int64_t n, msd_stream_t stream);
 /* msd_add_f32_bf16 — out = bf16(a + b), a / out bf16, b fp32, summed in fp32 (may run in place, out == a).  The ControlNet

@@ -176,6 +176,16 @@ class MsdAttentionJoint(C.Structure):
     ]
 
 
+class MsdAttentionWindowed(C.Structure):
+    _fields_ = [
+        ("q", C.c_void_p), ("k", C.c_void_p), ("vt", C.c_void_p), ("out", C.c_void_p),
+        ("batch", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32),
+        ("h", C.c_int32), ("w", C.c_int32), ("wh", C.c_int32), ("ww", C.c_int32),
+        ("q_ld", C.c_int32), ("k_ld", C.c_int32), ("vt_ld", C.c_int32),
+        ("o_ld", C.c_int32),   # HyperTile (an addition to ABI 12)
+    ]
+
+
 class MsdReferenceLatent(C.Structure):
     _fields_ = [
         ("z", C.c_void_p), ("noise", C.c_void_p), ("coef", C.c_void_p), ("step_ptr", C.c_void_p), ("out", C.c_void_p),
@@ -215,6 +225,7 @@ SYMBOLS = {
     "msd_attention_identity": (C.c_int, [C.POINTER(MsdAttentionIdentity), C.c_void_p]),
     "msd_attention_joint": (C.c_int, [C.POINTER(MsdAttentionJoint), C.c_void_p]),
     "msd_reference_latent": (C.c_int, [C.POINTER(MsdReferenceLatent), C.c_void_p]),
+    "msd_attention_windowed": (C.c_int, [C.POINTER(MsdAttentionWindowed), C.c_void_p]),
     "msd_add_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_add_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_cast_f32_to_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

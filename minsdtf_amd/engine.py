@@ -528,7 +528,7 @@ class Emitter:
         return out
 
     def attentions(self, x: Act, name, ctx_kv, ctx_len, heads=8, free_input=False, shared: int = 1, perturbed: int = 0,
-                   regions: int = 0, region_rows: int = 0, region_w=None, reference: int = 0, mix=None) -> Act:
+                   regions: int = 0, region_rows: int = 0, region_w=None, reference: int = 0, mix=None, window=None) -> Act:
         """Attentions / TransformerBlock / CrossAttention / GEGLU (diffusion_model.py:54-153).  shared > 1 (SHARE_CFG_PREFIX): `x` holds
         `shared` identical copies of x.B / shared samples (the cond and uncond halves in front of the first cross-attention): norm,
         proj_in, q|k|v, the self-attention and its to_out run on ONE copy, their result (rows + LayerNorm partials) is replicated, and the
@@ -545,9 +545,20 @@ class Emitter:
         rows in front of it is ONE msd_attention_joint launch - own keys, then the reference row's (k_ref / vt_ref are views of the
         same k / vt buffers at row B - 1), blended with the plain result by `mix` (fp32 [B - 1], or None) - and the reference row
         takes one msd_attention with batch = 1 at the offset pointers.  Not with shared > 1, perturbed or regions.  reference = 0
-        records exactly the plain block."""
+        records exactly the plain block.
+        window = (nh, nw) (HyperTile, minsdtf_amd/hypertile.py): attn1 is ONE msd_attention_windowed launch in place of msd_attention -
+        the attention is taken inside nh x nw non-overlapping windows of H / nh x W / nw tokens, on the operands where the q|k|v GEMM
+        wrote them.  Also with shared > 1 (the launch runs on the one copy); not with perturbed or reference.  None records exactly
+        the plain block."""
         p = self.p
         x_all = x
+        if window is not None:
+            nh, nw = (int(v) for v in window)
+            if perturbed or reference:
+                raise ValueError(f"{name}: window = {window} with perturbed = {perturbed}, reference = {reference}")
+            if nh < 1 or nw < 1 or x.H % nh or x.W % nw or (x.W // nw) % 8 or x.C // heads not in (40, 80, 160):
+                raise ValueError(f"{name}: {nh} x {nw} windows of a {x.H} x {x.W} map at head size {x.C // heads} "
+                                 "(whole windows whose width is a multiple of 8 tokens; head size 40, 80 or 160)")
         if reference not in (0, 1) or (reference and (shared > 1 or perturbed or regions or x.B < 2)):
             raise ValueError(f"{name}: reference = {reference} with {x.B} rows (shared = {shared}, perturbed = {perturbed}, regions = {regions})")
         if not 0 <= perturbed <= x.B or (perturbed and shared > 1):
@@ -585,6 +596,9 @@ class Emitter:
             p.rec(ops.attention, q=q.buf.at(g_rows * S * C * 2), k=k.buf.at(g_rows * S * C * 2), vt=vt.at(g_rows * C * sp * 2),
                   out=a1.buf.at(g_rows * S * C * 2), batch=1, heads=heads, head_dim=d, s=S, t=S, q_ld=C, k_ld=C, vt_ld=sp, o_ld=C,
                   scale=d ** -0.5, q_prescaled=True, name=tb + ".attn1")
+        elif window is not None:
+            p.rec(ops.attention_windowed, q=q.buf, k=k.buf, vt=vt, out=a1.buf, batch=B, heads=heads, head_dim=d, h=H, w=Wd, wh=H // nh,
+                  ww=Wd // nw, q_ld=C, k_ld=C, vt_ld=sp, o_ld=C, name=tb + ".attn1.windowed")
         elif perturbed < B:
             p.rec(ops.attention, q=q.buf, k=k.buf, vt=vt, out=a1.buf, batch=B - perturbed, heads=heads, head_dim=d, s=S, t=S, q_ld=C,
                   k_ld=C, vt_ld=sp, o_ld=C, scale=d ** -0.5, q_prescaled=True, name=tb + ".attn1")
@@ -770,7 +784,8 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
     """Down path + mid block shared by the UNet (diffusion_model.py:193-229) and the ControlNet.  shared > 1: `x` (conv_in's output) is
     `shared` identical copies of x.B / shared samples - the first ResBlock and the front of the first transformer block run on one.
     pag_layers / perturbed: the attention blocks (by name) whose attn1 is the identity for the last `perturbed` rows.
-    ref_kw: block name -> Emitter.attentions' reference keywords (emit_unet's `reference`; shared is 1 then)."""
+    ref_kw: block name -> Emitter.attentions' reference keywords (emit_unet's `reference`; shared is 1 then) or its window
+    keywords (emit_unet's `window`; also on the one copy of a shared first block)."""
     def pert(block):
         return perturbed if block in pag_layers else 0
 
@@ -783,7 +798,7 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
                 one = Act(x.buf, x.B // shared, x.H, x.W, x.C)
                 x = e.res_block(one, name, ch, temb=temb_of(name), out_copies=shared)
                 x = e.attentions(x, f"down_blocks.{lvl}.attentions.{r}", ctx_kv, ctx_len, free_input=True, shared=shared,
-                                 **_region_kw(region_attn, x))
+                                 **_region_kw(region_attn, x), **ref_kw(f"down_blocks.{lvl}.attentions.{r}"))
                 outputs.append(x)
                 continue
             x = e.res_block(x, name, ch, temb=temb_of(name))
@@ -803,8 +818,13 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
 
 def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w: int, temb, ctx_kv, ctx_len: int,
               eps_out_f32, controls=None, control_taps=None, pag_layers=None, perturbed: int = 0, region_attn=None, *,
-              reference=None) -> None:
+              reference=None, window=None, window_depth: int = 0) -> None:
     """DiffusionModel graph (diffusion_model.py:184-279).
+
+    window = (nh, nw) / window_depth = D (HyperTile, minsdtf_amd/hypertile.py): the self-attention of the attention blocks of levels
+    0 .. D (level 0: down_blocks.0 / up_blocks.3, d = 40; 1: d = 80; 2: d = 160) is taken inside nh x nw windows, the same number
+    at every selected level (Emitter.attentions); deeper levels and the mid block stay plain.  Not with pag_layers, region_attn or
+    reference.  None records exactly the plain forward.
 
     region_attn = (R, rows, {(h_l, w_l): fp32 plane [R][h_l * w_l]}) (regional prompting inside cross-attention): the last `rows` of
     the NB rows are conditional rows whose every attn2 mixes R region contexts (Emitter.attentions); ctx_kv then holds
@@ -865,7 +885,19 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
     if reference is not None:
         shared = 1   # the reference row is no copy of anything
 
+    win_levels = {}
+    if window is not None:
+        if perturbed or region_attn or reference is not None:
+            raise ValueError("emit_unet: window does not go with pag, regions or a reference row")
+        if window_depth not in (0, 1, 2):
+            raise ValueError(f"emit_unet: window_depth = {window_depth} (0, 1 or 2)")
+        for lvl in range(window_depth + 1):
+            for blk in [f"down_blocks.{lvl}.attentions.{r}" for r in range(2)] + [f"up_blocks.{3 - lvl}.attentions.{r}" for r in range(3)]:
+                win_levels[blk] = tuple(window)
+
     def ref_kw(block):
+        if block in win_levels:
+            return dict(window=win_levels[block])
         return dict(reference=1, mix=ref_mix) if block in ref_layers else {}
 
     x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared, pag_layers=pag_layers, perturbed=perturbed,

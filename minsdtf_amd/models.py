@@ -254,12 +254,13 @@ class DiffusionModel(HipModel):
         self.apply_control_net = apply_control_net
         self._maybe_load(ckpt_path, lora_dict)
 
-    def _build(self, B: int, T: int, with_controls: bool, pag_layers=None, regions: int = 0, reference=None) -> _BoundPlan:
+    def _build(self, B: int, T: int, with_controls: bool, pag_layers=None, regions: int = 0, reference=None, window=None) -> _BoundPlan:
         """pag_layers: the attention blocks whose self-attention is the identity map for ALL B rows (predict_perturbed).
         regions = R: all B rows are conditional rows over R region contexts (predict_regional): the context input is
         (R * B, T, 768), region-major, and `region_w` the four levels' weight planes (regions.pack_levels).
         reference = the attention blocks of a reference-only forward (predict_reference): the plan runs B + 1 rows, the last one the
-        reference row read from `ref_latent`; `t_emb` and `context` carry its row last, `ref_mix` is fp32 [B]; eps keeps B rows."""
+        reference row read from `ref_latent`; `t_emb` and `context` carry its row last, `ref_mix` is fp32 [B]; eps keeps B rows.
+        window = (nh, nw, depth) of a HyperTile forward (predict_windowed): emit_unet's window / window_depth."""
         h, w = self.h, self.w
         NB = B + 1 if reference else B
         plan = engine.Plan(self.device)
@@ -295,6 +296,8 @@ class DiffusionModel(HipModel):
                 controls.append(st)
         eps = plan.alloc(NB * h * w * 4 * 4)
         extra = dict(reference=(reference, ins["ref_latent"], ins["ref_mix"])) if reference else {}
+        if window is not None:
+            extra = dict(window=(window[0], window[1]), window_depth=window[2])
         engine.emit_unet(e, ins["latent"], B, NB, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls,
                          pag_layers=pag_layers, perturbed=B if pag_layers else 0, region_attn=region_attn, **extra)
         plan.finalize()
@@ -319,6 +322,19 @@ class DiffusionModel(HipModel):
         if len(x) != 3:
             raise ValueError("predict_perturbed takes [latent, t_emb, context] (no control tensors)")
         return self._predict(x, layers)
+
+    def predict_windowed(self, x, windows, depth=0):
+        """predict_on_batch([latent, t_emb, context]) with the self-attention of the attention blocks of levels 0 .. `depth` taken
+        inside `windows` = (nh, nw) non-overlapping windows of the feature map (msd_attention_windowed; minsdtf_amd/hypertile.py).
+        The forward of a HyperTile job's host loop; a bound plan of its own per (B, T, nh, nw, depth)."""
+        from . import hypertile as hypertile_mod
+
+        if len(x) != 3:
+            raise ValueError("predict_windowed takes [latent, t_emb, context] (no control tensors)")
+        nh, nw = (int(v) for v in windows)
+        depth = int(depth)
+        hypertile_mod.level_geometry(self.h, self.w, nh, nw, depth)   # (ValueError for windows the levels cannot take)
+        return self._predict(x, None, window=(nh, nw, depth))
 
     def predict_regional(self, x, contexts, level_weights):
         """predict_on_batch([latent, t_emb]) with every attn2 mixing the R region `contexts` (each (B, T, 768), T <= 96) per query by
@@ -381,7 +397,7 @@ class DiffusionModel(HipModel):
         bp.run()
         return bp.host("eps")[:B]
 
-    def _predict(self, x, pag_layers):
+    def _predict(self, x, pag_layers, window=None):
         latent, t_emb, context = _np32(x[0]), _np32(x[1]), _np32(x[2])
         controls = [_np32(c) for c in x[3:]]
         if controls and len(controls) != 13:
@@ -390,7 +406,9 @@ class DiffusionModel(HipModel):
         if latent.shape[1:] != (self.h, self.w, 4):
             raise ValueError(f"latent shape {latent.shape} does not match the model ({self.h},{self.w},4)")
         key = (B, T, bool(controls)) if pag_layers is None else (B, T, False, ("pag", tuple(sorted(pag_layers))))
-        bp = self._bound(key, lambda: self._build(B, T, bool(controls), pag_layers))
+        if window is not None:
+            key = (B, T, False, ("hypertile",) + tuple(window))
+        bp = self._bound(key, lambda: self._build(B, T, bool(controls), pag_layers, window=window))
         bp.io["latent"].copy_(torch.from_numpy(latent))
         bp.io["t_emb"].copy_(torch.from_numpy(t_emb))
         bp.io["context"].copy_(torch.from_numpy(context))

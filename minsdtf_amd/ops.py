@@ -266,6 +266,19 @@ def attention_joint(*, q, k, vt, k_ref, vt_ref, out, batch, heads, head_dim, s, 
     return Call(lib.msd_attention_joint, (C.byref(a),), name, keep=a)
 
 
+def attention_windowed(*, q, k, vt, out, batch, heads, head_dim, h, w, wh, ww, q_ld, k_ld, vt_ld, o_ld, name="attention_windowed") -> Call:
+    """msd_attention_windowed (HyperTile): per sample, head and window of wh x ww tokens of the h x w feature map, out = softmax(q k^T) v
+    over that window's keys only.  q bf16 [batch][h * w][q_ld] carrying scale * log2(e), k bf16 [batch][h * w][k_ld], vt bf16
+    [batch][heads * head_dim][vt_ld], out bf16 [batch][h * w][o_ld]: msd_attention's operands in image order, nothing gathered."""
+    lib = _lib.load()
+    a = _lib.MsdAttentionWindowed()
+    a.q, a.k, a.vt, a.out = _p(q), _p(k), _p(vt), _p(out)
+    a.batch, a.heads, a.head_dim = int(batch), int(heads), int(head_dim)
+    a.h, a.w, a.wh, a.ww = int(h), int(w), int(wh), int(ww)
+    a.q_ld, a.k_ld, a.vt_ld, a.o_ld = int(q_ld), int(k_ld), int(vt_ld), int(o_ld)
+    return Call(lib.msd_attention_windowed, (C.byref(a),), name, keep=a)
+
+
 def reference_latent(*, z, noise, coef, out, n, num_steps, step_ptr=None, name="reference_latent") -> Call:
     """msd_reference_latent: out = coef[step][0] * z + coef[step][1] * noise (one fp32 FMA per element), step = *step_ptr.  z / noise /
     out fp32 [n], coef fp32 [num_steps][2] (reference.rates)."""

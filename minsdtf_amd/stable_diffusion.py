@@ -34,6 +34,7 @@ import torch
 
 from . import _lib, engine, ops
 from . import hires as hires_mod
+from . import hypertile as hypertile_mod
 from . import pag as pag_mod
 from . import reference as reference_mod
 from . import regions as regions_mod
@@ -74,11 +75,11 @@ class DenoiseEngine:
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
-                 sampler=None, tiled=None, regions: int = 0, pag=None, region_mode: str = "latent", reference=None):
+                 sampler=None, tiled=None, regions: int = 0, pag=None, region_mode: str = "latent", reference=None, hypertile=None):
         unet._require_weights()
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
-        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag, region_mode, reference)
+        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag, region_mode, reference, hypertile)
         if self.reference and guidance > 0.0 and t_cond != t_uncond:
             raise ValueError("reference_only: the negative prompt must have the conditional context's token length "
                              f"({t_uncond} != {t_cond} tokens): the reference row rides in the one fused pass")
@@ -129,9 +130,9 @@ class DenoiseEngine:
         _lib.track_graph_owner(self)
 
     def _check_options(self, control_net, streams, inpaint, tcd, sampler, tiled, regions, pag=None, region_mode="latent",
-                       reference=None) -> None:
+                       reference=None, hypertile=None) -> None:
         """The option combinations an engine refuses (generate_image refuses them earlier, by argument name: _REFUSED; these guard
-        direct construction).  Sets `sampler`, `tiled`, `regions`, `pag` and `reference`."""
+        direct construction).  Sets `sampler`, `tiled`, `regions`, `pag`, `reference` and `hypertile`."""
         # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
         # the 8-wide coefficient rows, the previous denoised estimate and (stochastic samplers) per-step draws on the device
         self.sampler = smp.parse(sampler)
@@ -184,6 +185,18 @@ class DenoiseEngine:
             if control_net is not None or inpaint or tcd or tiled is not None or R or self.pag or streams == 2:
                 raise ValueError("reference_only: text-to-image on one stream only (no ControlNet, inpainting, TCD, tiled, regions, pag, "
                                  "denoise_streams = 2)")
+
+        # hypertile ((nh, nw, depth) of a HyperTile job, or None): the self-attention of the attention blocks of levels 0 .. depth
+        # is taken inside nh x nw windows (msd_attention_windowed in place of msd_attention, every row of every pass); nothing else
+        # in the step changes and nothing is uploaded per call (minsdtf_amd/hypertile.py)
+        self.hypertile = None if hypertile is None else tuple(int(v) for v in hypertile)
+        if self.hypertile is not None:
+            if len(self.hypertile) != 3:
+                raise ValueError(f"hypertile: {hypertile!r} is not (nh, nw, depth)")
+            hypertile_mod.level_geometry(self.h, self.w, *self.hypertile)   # (ValueError for windows the levels cannot take)
+            if control_net is not None or inpaint or tiled is not None or R or self.pag or self.reference or streams == 2:
+                raise ValueError("hypertile: text-to-image on one stream only (no ControlNet, inpainting, tiled, regions, pag, "
+                                 "reference_only, denoise_streams = 2)")
 
     def _build_prep(self, control_net, hint_net) -> dict:
         """The preparation plans: per SCHEDULE the time-embedding tables (timestep -> MLP -> every ResBlock's projection: they do
@@ -294,6 +307,8 @@ class DenoiseEngine:
                 step.rec(ops.reference_latent, z=self.ref_z, noise=self.ref_noise, coef=self.ref_coef, step_ptr=self.step_ptr,
                          out=self.ref_latent, n=n, num_steps=self.num_steps)
                 extra = dict(reference=(self.reference, self.ref_latent, self.ref_mix))
+            if self.hypertile is not None:
+                extra = dict(window=self.hypertile[:2], window_depth=self.hypertile[2])
             engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps, **extra)
         return step
 
@@ -618,17 +633,18 @@ class StableDiffusionBase:
     # ---- public entry points (reference :84-139)
     def text_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                       embedding=None, negative_embedding=None, seed=None, control_net_image=None, guidance_rescale=0.7,
-                      callback=None, hires=None, tiled=None, regions=None, pag=None, reference_only=None, **kw):
+                      callback=None, hires=None, tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, **kw):
         """``hires``: None, or a hires.HiresSpec / dict for the two-pass hires fix; ``tiled``: None, or a tiled.TiledSpec / dict
         for tiled diffusion on a canvas larger than the pipeline's size; ``regions``: None, or a regions.Regions / dict for
         regional prompting, `prompt` being the base prompt; ``pag``: None, or a pag.PagSpec / dict for perturbed-attention
-        guidance; ``reference_only``: None, or a reference.ReferenceSpec / dict for reference-only control (see generate_image)."""
+        guidance; ``reference_only``: None, or a reference.ReferenceSpec / dict for reference-only control; ``hypertile``: None, or a
+        hypertile.HypertileSpec / dict for windowed self-attention (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
                                    negative_embedding=negative_embedding, control_net_image=control_net_image,
                                    guidance_rescale=guidance_rescale, callback=callback, hires=hires, tiled=tiled, regions=regions,
-                                   pag=pag, reference_only=reference_only, **kw)
+                                   pag=pag, reference_only=reference_only, hypertile=hypertile, **kw)
 
     def image_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
@@ -861,7 +877,7 @@ class StableDiffusionBase:
                        diffusion_noise=None, seed=None, negative_embedding=None, control_net_image=None, inpaint_mask=None,
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
                        callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None,
-                       tiled=None, regions=None, pag=None, reference_only=None):
+                       tiled=None, regions=None, pag=None, reference_only=None, hypertile=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
@@ -899,9 +915,18 @@ class StableDiffusionBase:
         generated rows' self-attention also attends to that row's keys (one msd_attention_joint launch per block); ``fidelity`` is
         the share of the plain self-attention in the unconditional rows (diffusers' style_fidelity).  (`reference_image` is
         image_to_image's start picture, another thing.)  Works with every sampler, with shard_batch and with host_loop=True; at most
-        2 * tiled.MAX_VIEW_BATCH UNet rows (2 * batch_size + 1); the negative prompt has the prompt's token length."""
+        2 * tiled.MAX_VIEW_BATCH UNet rows (2 * batch_size + 1); the negative prompt has the prompt's token length.
+        ``hypertile`` (a hypertile.HypertileSpec or a dict {"tile": 512, "depth": 0}; txt2img only): HyperTile - the self-attention of
+        the attention blocks of the UNet levels 0 .. depth is taken inside non-overlapping windows of `tile` picture pixels (an int
+        or (height, width), a multiple of 64 * 2**depth that divides the picture), one msd_attention_windowed launch per block in
+        place of msd_attention: with nh x nw windows the attention FLOPs fall by nh * nw.  The tile is fixed, never drawn.  With
+        ``hires`` the spec applies to the second pass only, its geometry taken from the target size - the use it is for; one window
+        is the plain job.  Works with every sampler, on a TCD pipeline, with shard_batch and with host_loop=True."""
         given = dict(tiled=tiled, hires=hires, control_net_image=control_net_image, reference_image=reference_image,
-                     inpaint_mask=inpaint_mask, regions=regions, pag=pag)
+                     inpaint_mask=inpaint_mask, regions=regions, pag=pag, reference_only=reference_only)
+        ht = hypertile_mod.parse(hypertile)   # (ValueError for a bad description)
+        if ht is not None:
+            self._refuse_combinations("hypertile", given, host_loop)
         ref = reference_mod.parse(reference_only)   # (ValueError for a bad description)
         if ref is not None:
             self._refuse_combinations("reference_only", given, host_loop)
@@ -941,6 +966,13 @@ class StableDiffusionBase:
             raise ValueError("`hires_noise` without `hires`")
         if job is not None:
             self._refuse_combinations("hires", given, host_loop)
+        ht_key = None
+        if ht is not None:   # (nh, nw, depth) on the picture the windowed pass produces; one window: the plain job, on the plain engine
+            size = (job.height, job.width) if job is not None else (self.img_height, self.img_width)
+            ht_key = ht.key(*size)   # (ValueError naming the nearest valid tiles)
+            hypertile_mod.level_geometry(size[0] // 8, size[1] // 8, *ht_key)
+            if ht_key[:2] == (1, 1):
+                ht_key = None
         if diffusion_noise is not None and seed is not None:
             raise ValueError("`diffusion_noise` and `seed` should not both be passed to `generate_image`. `seed` is only "
                              "used to generate diffusion noise when it's not already user-specified.")
@@ -961,7 +993,8 @@ class StableDiffusionBase:
         noise = self._get_initial_diffusion_noise(B, seed) if diffusion_noise is None else self._batch_of(diffusion_noise, B, 3)
         if job is not None:
             return self._generate_hires(job, spec, context, unconditional_context, noise, hires_noise, num_steps,
-                                        float(unconditional_guidance_scale), float(guidance_rescale), seed, callback, return_latent)
+                                        float(unconditional_guidance_scale), float(guidance_rescale), seed, callback, return_latent,
+                                        hypertile=ht_key)
         self.scheduler.set_timesteps(num_steps)
 
         # image_to_image (reference :410-418,559-568): encode the picture, run only the last int(n*strength+0.5) steps,
@@ -1019,11 +1052,11 @@ class StableDiffusionBase:
             ip = (encoded, noise, latent_mask[0]) if inpainting else None
             if spec is not None:
                 latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
-                                                 sampler_z, ip, region_w=region_w, pag=pg,
+                                                 sampler_z, ip, region_w=region_w, pag=pg, hypertile=ht_key,
                                                  reference=None if ref is None else (ref, ref_in, reference_mod.rates(sched, start_index)))
             else:
                 latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending, ip,
-                                         region_w=region_w, pag=pg,
+                                         region_w=region_w, pag=pg, hypertile=ht_key,
                                          reference=None if ref is None else (ref, ref_in, reference_mod.rates(self.scheduler, start_index)))
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
@@ -1060,7 +1093,7 @@ class StableDiffusionBase:
             eng = self._denoise_pass(u, c, z, num_steps, g, phi, start_index, run_steps, callback,
                                      dict(sampler=sname, regions=None if reg is None else len(c), pag=None if pg is None else pg.key,
                                           region_mode="attention" if reg is not None and reg.mode == "attention" else None,
-                                          reference=None if ref is None else ref.key),
+                                          reference=None if ref is None else ref.key, hypertile=ht_key),
                                      dict(hint_image=a.get("hint"), inpaint=(a["encoded"], a["noise"], a["mask"]) if inpainting else None,
                                           step_noise=a.get("tcd") if spec is None else a.get("sampler_z"), sampler=sched,
                                           regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale,
@@ -1084,6 +1117,9 @@ class StableDiffusionBase:
                   ("host_loop=True", "a TCD pipeline (active_tcd=True)")),
         "pag": ("text-to-image on one stream only", ("regions", "tiled", "hires", "control_net_image", "reference_image", "inpaint_mask"),
                 ("denoise_streams = 2",)),
+        "hypertile": ("text-to-image on one stream only",
+                      ("tiled", "regions", "pag", "reference_only", "control_net_image", "inpaint_mask", "reference_image"),
+                      ("denoise_streams = 2",)),
         "reference_only": ("text-to-image on one stream only",
                            ("regions", "pag", "tiled", "hires", "control_net_image", "reference_image", "inpaint_mask"),
                            ("a TCD pipeline (active_tcd=True)", "denoise_streams = 2")),
@@ -1193,10 +1229,11 @@ class StableDiffusionBase:
         return cache[key]
 
     def _generate_hires(self, job, spec, context, unconditional_context, noise, hires_noise, num_steps, g, phi, seed, callback,
-                        return_latent):
+                        return_latent, hypertile=None):
         """Pass 1 (the txt2img job at the pipeline's own size, no decode) -> one msd_latent_resample launch from the pass-1 engine's
         latent into the pass-2 engine's, scaled and re-noised with the pass-2 entry rates -> pass 2 at the target size -> decode.
-        Both engines stay resident, so a repeated job constructs nothing and captures nothing."""
+        Both engines stay resident, so a repeated job constructs nothing and captures nothing.  hypertile = (nh, nw, depth): pass 2
+        runs the windowed engine of the target size; pass 1 stays plain."""
         B = noise.shape[0]
         h1, w1, h2, w2 = self.img_height // 8, self.img_width // 8, job.height // 8, job.width // 8
         a2, s2, start2, run2 = hires_mod.entry(self.scheduler, spec, job.steps, job.strength)
@@ -1216,6 +1253,8 @@ class StableDiffusionBase:
             """This rank's slice: pass 1 -> hand-off into the pass-2 engine -> pass 2 -> decode; returns a device tensor."""
             b = int(z.shape[0])
             opts = [dict(sampler=sname), dict(sampler=sname, unet=self._unet_for(job.height, job.width))]
+            if hypertile is not None:
+                opts[1]["hypertile"] = hypertile
             # (both keys in front of the first build: whatever neither pass needs goes before either arena is allocated)
             keys = [self._engine_key(b, c.shape[1], u.shape[1], n, g, phi, False, **o) for n, o in zip((num_steps, job.steps), opts)]
             self.scheduler.set_timesteps(num_steps)
@@ -1301,7 +1340,9 @@ class StableDiffusionBase:
         # (a PAG job: the selected blocks only - the scale is a per-call upload)
         key = key if not opts.get("pag") else key + (("pag", tuple(sorted(opts["pag"]))),)
         # (a reference-only job: the selected blocks only - the image, the draw and the fidelity are per-call uploads)
-        return key if not opts.get("reference") else key + (("reference", tuple(sorted(opts["reference"]))),)
+        key = key if not opts.get("reference") else key + (("reference", tuple(sorted(opts["reference"]))),)
+        # (a HyperTile job: the number of windows and the depth - there is nothing else to it)
+        return key if not opts.get("hypertile") else key + (("hypertile",) + tuple(int(v) for v in opts["hypertile"]),)
 
     def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> DenoiseEngine:
         """The resident engine of this shape, built if need be.  `opts` are DenoiseEngine's: `sampler`; `unet`: the UNet of another
@@ -1310,7 +1351,7 @@ class StableDiffusionBase:
         alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is
         built: a re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than
         the job's own engines - one for a plain job, two for a hires job."""
-        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode", "reference"}:
+        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode", "reference", "hypertile"}:
             raise TypeError(f"_engine: unknown option among {sorted(opts)}")
         key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, **opts)
         keep = {key} | set(job_keys or ())
@@ -1330,12 +1371,13 @@ class StableDiffusionBase:
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
                                 streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=opts.get("sampler"),
                                 tiled=opts.get("tiled"), regions=opts.get("regions") or 0, pag=opts.get("pag"),
-                                region_mode=opts.get("region_mode") or "latent", reference=opts.get("reference"))
+                                region_mode=opts.get("region_mode") or "latent", reference=opts.get("reference"),
+                                hypertile=opts.get("hypertile"))
             self._engines[key] = eng
         return eng
 
     def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None,
-                   region_w=None, pag=None, reference=None):
+                   region_w=None, pag=None, reference=None, hypertile=None):
         """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479)."""
         if timesteps is None:
             timesteps = self.scheduler.timesteps[::-1]
@@ -1348,7 +1390,7 @@ class StableDiffusionBase:
             t_emb = get_timestep_embedding(timestep, batch_size)
             # (a reference-only job: the position of this evaluation in the descending schedule indexes its rate table)
             ref_step = None if reference is None else reference + (n_sched - 1 - _index,)
-            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag, ref_step)
+            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag, ref_step, hypertile)
             latent = self.scheduler.step(latent, timestep, latent_prev)
             if inpaint is not None:   # reference :469-475
                 init_latent, noise, latent_mask = inpaint
@@ -1360,7 +1402,8 @@ class StableDiffusionBase:
                 callback(iteration)
         return latent
 
-    def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None, reference=None):
+    def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None, reference=None,
+                    hypertile=None):
         """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
         A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
         predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host); in mode "attention"
@@ -1380,7 +1423,10 @@ class StableDiffusionBase:
             return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
 
         def predict(ctx):
-            """The UNet's prediction for one context, through the ControlNet if there is a hint."""
+            """The UNet's prediction for one context, through the ControlNet if there is a hint; a HyperTile job's through
+            predict_windowed ((nh, nw, depth))."""
+            if hypertile is not None:
+                return self.diffusion_model.predict_windowed([latent, t_emb, ctx], hypertile[:2], hypertile[2])
             if hint is None:
                 return self.diffusion_model.predict_on_batch([latent, t_emb, ctx])
             controls = self.control_net.predict_on_batch([latent, t_emb, ctx, hint])
@@ -1402,7 +1448,7 @@ class StableDiffusionBase:
         return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
 
     def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
-                           inpaint=None, region_w=None, pag=None, reference=None):
+                           inpaint=None, region_w=None, pag=None, reference=None, hypertile=None):
         """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`."""
         batch_size = latent.shape[0]
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
@@ -1412,7 +1458,7 @@ class StableDiffusionBase:
         for iteration, i in enumerate(range(start, sched.num_steps), start=1):
             t_emb = get_timestep_embedding(float(sched.timesteps[i]), batch_size)
             e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint, region_w, pag,
-                                 None if reference is None else reference + (i,))
+                                 None if reference is None else reference + (i,), hypertile)
             z = step_noise[:, i] if step_noise is not None else None
             x, prev = smp.host_step(tab[i], x, e, prev, z)
             if inpaint is not None:   # the row's own alpha / sigma, as in the device kernel
