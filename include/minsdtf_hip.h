@@ -735,6 +735,44 @@ typedef struct MsdReferenceLatent {
 MSD_API int msd_reference_latent(const MsdReferenceLatent* p, msd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * msd_reference_adain — reference AdaIN of a reference-only job (minsdtf_amd/reference.py): every generated
+ * row's feature map is renormalised, channel by channel, to the mean and standard deviation that the reference row has at the
+ * same place, in place.  An addition to ABI 12: nothing else changed.
+ *
+ *   x:    bf16 [rows][hw][c], dense; rewritten in place
+ *   ref:  bf16 [hw][c]: the reference row; never written; may not overlap x[0 .. rows) (directly behind it is fine)
+ *   mix:  fp32 [rows] or NULL = all 0: the share of the row's own values in its result
+ *   rows in 1 .. 65535, hw >= 1, c a positive multiple of 8, hw * c < 2^31, eps finite and positive (1e-6 from the engine)
+ *
+ * Per row b and channel c (pinned; every operation a single-rounded fp32 one), with n = hw and inv_n = fp32(1) / fp32(n):
+ *   mean = (sum_p x[b][p][c]) * inv_n                 first the mean,
+ *   var  = (sum_p fma(d, d, .)) * inv_n, d = x - mean  then the squared deviations from THAT mean (never E[x^2] - mean^2)
+ *   std  = sqrt(max(var, 0) + eps)                    (correctly rounded sqrt)
+ *   mean_r, std_r likewise from ref
+ *   f = mix[b] (0 when mix is NULL), g = 1 - f, s = std_r / std (correctly rounded division)
+ *   A = fma(g, s, f)      Bc = g * fma(-mean, s, mean_r)      out = bf16(fma(x, A, Bc))
+ * which is out = f x + (1 - f) ((x - mean) s + mean_r).  Both sums run in the same order for x and for ref: a lane adds the
+ * pixels p0, p0 + L, p0 + 2 L, ... (p0 < L; L = 32 pixel lanes up to hw = 1024, 128 above) in ascending order, the eight lanes of
+ * a wave that share a channel by three cross-lane adds, the waves in ascending order ((w0 + w1) + w2) + ... - an order that
+ * depends on hw alone, so a row that is a copy of the reference gets s = 1 and Bc = 0 exactly and comes back bit for bit.  A row with f == 1 is neither read nor written (it may hold NaN); a
+ * workgroup is one row and 64 adjacent channels, so that branch is uniform over it.  A row's bits depend on its own data, the
+ * reference row and its own mix entry: not on rows, the grid or the other rows of the launch.  Up to hw = 1024 the row's and
+ * the reference's slab stay in registers between the passes; above that they are read again.
+ *
+ * Plain 16-byte vector loads and stores, no atomics, no scratch, no workspace.  Checked on the host, without a device: x / ref
+ * non-NULL; x / ref / mix 16-byte aligned; rows, hw, c, eps as above; ref and mix apart from x[0 .. rows).  Argument errors
+ * return MSD_E_ARG without launching.  Nothing is allocated; the launch is stream-ordered and capturable. */
+typedef struct MsdReferenceAdain {
+    void* x;
+    const void* ref;
+    const float* mix;
+    int32_t rows, hw, c;
+    float eps;
+} MsdReferenceAdain;
+
+MSD_API int msd_reference_adain(const MsdReferenceAdain* p, msd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * msd_attention_windowed — HyperTile: self-attention inside non-overlapping rectangular windows of the h x w feature map
  * (minsdtf_amd/hypertile.py).  The operands are those of msd_attention in its q_prescaled form, over the whole
  * image, where the q|k|v GEMM wrote them: nothing is gathered.  An addition to ABI 12: nothing else changed.

@@ -193,6 +193,13 @@ class MsdReferenceLatent(C.Structure):
     ]
 
 
+class MsdReferenceAdain(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("ref", C.c_void_p), ("mix", C.c_void_p),
+        ("rows", C.c_int32), ("hw", C.c_int32), ("c", C.c_int32), ("eps", C.c_float),   # reference AdaIN (an addition to ABI 12)
+    ]
+
+
 LORA_ROWS_PER_BLOCK = 8  # csrc/lora.hip LR_ROWS: MsdLoraJob.first_block counts workgroups of this many rows
 
 # every symbol include/minsdtf_hip.h declares: name -> (restype, argtypes)
@@ -225,6 +232,7 @@ SYMBOLS = {
     "msd_attention_identity": (C.c_int, [C.POINTER(MsdAttentionIdentity), C.c_void_p]),
     "msd_attention_joint": (C.c_int, [C.POINTER(MsdAttentionJoint), C.c_void_p]),
     "msd_reference_latent": (C.c_int, [C.POINTER(MsdReferenceLatent), C.c_void_p]),
+    "msd_reference_adain": (C.c_int, [C.POINTER(MsdReferenceAdain), C.c_void_p]),
     "msd_attention_windowed": (C.c_int, [C.POINTER(MsdAttentionWindowed), C.c_void_p]),
     "msd_add_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "msd_add_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

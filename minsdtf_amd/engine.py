@@ -780,16 +780,18 @@ def _region_kw(region_attn, x: Act) -> dict:
 
 
 def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1,
-                  pag_layers=frozenset(), perturbed: int = 0, region_attn=None, ref_kw=None) -> Act:
+                  pag_layers=frozenset(), perturbed: int = 0, region_attn=None, ref_kw=None, site=None) -> Act:
     """Down path + mid block shared by the UNet (diffusion_model.py:193-229) and the ControlNet.  shared > 1: `x` (conv_in's output) is
     `shared` identical copies of x.B / shared samples - the first ResBlock and the front of the first transformer block run on one.
     pag_layers / perturbed: the attention blocks (by name) whose attn1 is the identity for the last `perturbed` rows.
     ref_kw: block name -> Emitter.attentions' reference keywords (emit_unet's `reference`; shared is 1 then) or its window
-    keywords (emit_unet's `window`; also on the one copy of a shared first block)."""
+    keywords (emit_unet's `window`; also on the one copy of a shared first block).
+    site: (x, name of the call that produced it) -> None, emit_unet's reference AdaIN right behind a block output."""
     def pert(block):
         return perturbed if block in pag_layers else 0
 
     ref_kw = ref_kw or (lambda block: {})
+    site = site or (lambda x, name: None)
 
     for lvl, ch in enumerate(wtab.UNET_CH):
         for r in range(2):
@@ -805,6 +807,9 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
             if lvl < 3:
                 blk = f"down_blocks.{lvl}.attentions.{r}"
                 x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=pert(blk), **_region_kw(region_attn, x), **ref_kw(blk))
+                site(x, blk)
+            else:
+                site(x, name)
             outputs.append(x)
         if lvl < 3:
             x = e.conv(x, f"down_blocks.{lvl}.downsamplers.0.conv", ch, ksize=3, stride=2)
@@ -813,12 +818,13 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
     x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True, perturbed=pert("mid_block.attentions.0"),
                      **_region_kw(region_attn, x), **ref_kw("mid_block.attentions.0"))
     x = e.res_block(x, "mid_block.resnets.1", 1280, temb=temb_of("mid_block.resnets.1"), free_input=True)
+    site(x, "mid_block.resnets.1")
     return x
 
 
 def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w: int, temb, ctx_kv, ctx_len: int,
               eps_out_f32, controls=None, control_taps=None, pag_layers=None, perturbed: int = 0, region_attn=None, *,
-              reference=None, window=None, window_depth: int = 0) -> None:
+              reference=None, window=None, window_depth: int = 0, adain=None) -> None:
     """DiffusionModel graph (diffusion_model.py:184-279).
 
     window = (nh, nw) / window_depth = D (HyperTile, minsdtf_amd/hypertile.py): the self-attention of the attention blocks of levels
@@ -838,6 +844,11 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
     named in `layers` the rows in front of it attend to its keys too (Emitter.attentions; mix: fp32 [NB - 1] or None).  Nothing is
     shared across the copies of such a job.  Not with pag_layers, region_attn or ControlNet residuals.  None records exactly the
     plain forward.
+
+    adain = a set of site names (reference AdaIN, reference.ADAIN_SITES; only with `reference`, whose `layers` may then be empty):
+    right behind the call that produces a selected site, before anything reads it, ONE msd_reference_adain launch renormalises
+    the NB - 1 generated rows of the site buffer to the statistics of its last row, in place, blended by the reference `mix` -
+    so the skip connection and the onward path both see the result.  None records exactly the plan without it.
 
     latent_f32: fp32 [latent_batch_mod][h][w][4] (sample b reads row b % latent_batch_mod);
     temb = (table, step_stride, batch_stride, {resblock: column}); eps_out_f32: fp32 [NB][h][w][4].
@@ -859,10 +870,25 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
     if reference is not None:
         ref_layers, ref_latent, ref_mix = reference
         ref_layers = frozenset(ref_layers)
-        if not ref_layers or ref_layers - set(PAG_LAYERS):
-            raise ValueError(f"emit_unet: reference layers {sorted(ref_layers)} (a non-empty subset of PAG_LAYERS)")
+        if (not ref_layers and not adain) or ref_layers - set(PAG_LAYERS):
+            raise ValueError(f"emit_unet: reference layers {sorted(ref_layers)} (a non-empty subset of PAG_LAYERS, or empty next to adain sites)")
         if NB < 2 or perturbed or region_attn or controls is not None or control_taps is not None:
             raise ValueError("emit_unet: a reference row goes with at least one generated row and not with pag, regions or a ControlNet")
+    adain = frozenset(adain) if adain else frozenset()
+    if adain:
+        from .reference import ADAIN_SITES
+
+        if adain - {n for n, _gw in ADAIN_SITES}:
+            raise ValueError(f"emit_unet: unknown adain site(s) {sorted(adain - {n for n, _gw in ADAIN_SITES})}")
+        if reference is None or window is not None:   # (pag, regions and ControlNet residuals are refused with the reference row)
+            raise ValueError("emit_unet: adain goes with a reference row and not with pag, regions, a window or a ControlNet")
+
+    def site(x: Act, name: str) -> None:
+        """Reference AdaIN behind the call `name` that produced x, when that output is a selected site."""
+        if name in adain:
+            p.rec(ops.reference_adain, x=x.buf, ref=x.buf.at((NB - 1) * x.H * x.W * x.C * 2), mix=ref_mix, rows=NB - 1, hw=x.H * x.W,
+                  c=x.C, eps=1e-6, name=name + ".adain")
+
     x = p.act(NB, h, w, 320)
     gen = NB - 1 if reference is not None else NB   # the rows conv_in reads from latent_f32
     p.rec(ops.conv_direct, x=latent_f32, w=e.W["conv_in.w"], bias=e.W["conv_in.b"], out=x.buf, batch=gen,
@@ -901,7 +927,7 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
         return dict(reference=1, mix=ref_mix) if block in ref_layers else {}
 
     x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared, pag_layers=pag_layers, perturbed=perturbed,
-                      region_attn=region_attn, ref_kw=ref_kw)
+                      region_attn=region_attn, ref_kw=ref_kw, site=site)
     p.mark("controls")   # everything above is independent of the ControlNet (its encoder may run beside it on another stream)
     if control_taps is not None:
         e_c, feats = control_taps
@@ -924,10 +950,12 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
                 blk = f"up_blocks.{ui}.attentions.{r}"
                 x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=perturbed if blk in pag_layers else 0,
                                  **_region_kw(region_attn, x), **ref_kw(blk))
+            site(x, blk if lvl < 3 else name)   # (the third call of a block is no site: the upsampler conv's output is)
         if lvl > 0:
             y = e.conv(x, f"up_blocks.{ui}.upsamplers.0.conv", ch, ksize=3, upsample=True)
             p.free(x)
             x = y
+            site(x, f"up_blocks.{ui}.upsamplers.0.conv")
     g = e.group_norm(x, "conv_norm_out", silu=True)
     p.free(x)
     if MFMA_CONV_OUT and "conv_out.m.w" in e.W:

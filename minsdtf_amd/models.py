@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _lib, engine, layout, ops, packing
+from . import reference as reference_mod
 from . import weights as wtab
 
 
@@ -254,20 +255,23 @@ class DiffusionModel(HipModel):
         self.apply_control_net = apply_control_net
         self._maybe_load(ckpt_path, lora_dict)
 
-    def _build(self, B: int, T: int, with_controls: bool, pag_layers=None, regions: int = 0, reference=None, window=None) -> _BoundPlan:
+    def _build(self, B: int, T: int, with_controls: bool, pag_layers=None, regions: int = 0, reference=None, window=None,
+               adain=None) -> _BoundPlan:
         """pag_layers: the attention blocks whose self-attention is the identity map for ALL B rows (predict_perturbed).
         regions = R: all B rows are conditional rows over R region contexts (predict_regional): the context input is
         (R * B, T, 768), region-major, and `region_w` the four levels' weight planes (regions.pack_levels).
         reference = the attention blocks of a reference-only forward (predict_reference): the plan runs B + 1 rows, the last one the
         reference row read from `ref_latent`; `t_emb` and `context` carry its row last, `ref_mix` is fp32 [B]; eps keeps B rows.
+        adain = the reference AdaIN sites of such a forward (reference.ADAIN_SITES); `reference` may then be an empty set.
         window = (nh, nw, depth) of a HyperTile forward (predict_windowed): emit_unet's window / window_depth."""
         h, w = self.h, self.w
-        NB = B + 1 if reference else B
+        reference = frozenset(reference or ()) if (reference or adain) else None   # (an empty layer set next to AdaIN sites)
+        NB = B + 1 if reference is not None else B
         plan = engine.Plan(self.device)
         e = engine.Emitter(plan, self._W)
-        CB = (regions or 1) * B + (1 if reference else 0)   # context rows
+        CB = (regions or 1) * B + (1 if reference is not None else 0)   # context rows
         shapes = dict(latent=(B, h, w, 4), t_emb=(NB, 320), context=(CB, T, 768))
-        if reference:
+        if reference is not None:
             shapes.update(ref_latent=(1, h, w, 4), ref_mix=(B,))
         region_attn = None
         if regions:
@@ -295,7 +299,9 @@ class DiffusionModel(HipModel):
                 cstage.append((st, (B, hh, ww, ch)))
                 controls.append(st)
         eps = plan.alloc(NB * h * w * 4 * 4)
-        extra = dict(reference=(reference, ins["ref_latent"], ins["ref_mix"])) if reference else {}
+        extra = dict(reference=(reference, ins["ref_latent"], ins["ref_mix"])) if reference is not None else {}
+        if adain:
+            extra["adain"] = frozenset(adain)
         if window is not None:
             extra = dict(window=(window[0], window[1]), window_depth=window[2])
         engine.emit_unet(e, ins["latent"], B, NB, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls,
@@ -365,15 +371,20 @@ class DiffusionModel(HipModel):
         bp.run()
         return bp.host("eps")
 
-    def predict_reference(self, x, ref_latent_t, layers, mix, ref_context=None):
+    def predict_reference(self, x, ref_latent_t, layers, mix, ref_context=None, adain=None):
         """predict_on_batch([latent, t_emb, context]) with one more row, the reference latent `ref_latent_t` (1, h, w, 4) ALREADY
         noised to this step's level, whose keys the self-attention of the attention blocks `layers` (names of engine.PAG_LAYERS)
         also attends to (msd_attention_joint; minsdtf_amd/reference.py).  `mix`: the share of the plain self-attention in each
         row's result, a float or (B,) values in [0, 1].  The reference row takes t_emb[0] and `ref_context` (T, 768) or (1, T, 768)
-        (default: context[0]).  Returns the B rows' prediction; a bound plan of its own per (rows, T, layer set)."""
-        layers = frozenset([layers] if isinstance(layers, str) else layers)
-        if not layers or layers - set(engine.PAG_LAYERS):
-            raise ValueError(f"predict_reference: layers {sorted(layers)} (a non-empty subset of engine.PAG_LAYERS)")
+        (default: context[0]).  `adain`: None, or reference AdaIN site names (reference.ADAIN_SITES): behind those block outputs the
+        rows are renormalised to the reference row's channel statistics (msd_reference_adain), blended by the same `mix`;
+        `layers` may then be empty.  Returns the B rows' prediction; a bound plan of its own per (rows, T, layer set, site set)."""
+        layers = frozenset([layers] if isinstance(layers, str) else (layers or ()))
+        sites = frozenset([adain] if isinstance(adain, str) else (adain or ()))
+        if (not layers and not sites) or layers - set(engine.PAG_LAYERS):
+            raise ValueError(f"predict_reference: layers {sorted(layers)} (a non-empty subset of engine.PAG_LAYERS, or empty next to adain sites)")
+        if sites - {n for n, _gw in reference_mod.ADAIN_SITES}:
+            raise ValueError(f"predict_reference: unknown adain site(s) {sorted(sites - {n for n, _gw in reference_mod.ADAIN_SITES})}")
         if len(x) != 3:
             raise ValueError("predict_reference takes [latent, t_emb, context] (no control tensors)")
         latent, t_emb, context = _np32(x[0]), _np32(x[1]), _np32(x[2])
@@ -387,8 +398,8 @@ class DiffusionModel(HipModel):
         m = np.broadcast_to(np.asarray(mix, dtype=np.float32), (B,))
         if not ((m >= 0.0) & (m <= 1.0)).all():
             raise ValueError("predict_reference: mix in [0, 1]")
-        key = (B + 1, T, False, ("reference", tuple(sorted(layers))))
-        bp = self._bound(key, lambda: self._build(B, T, False, reference=layers))
+        key = (B + 1, T, False, ("reference", tuple(sorted(layers))) + ((("adain",) + tuple(sorted(sites)),) if sites else ()))
+        bp = self._bound(key, lambda: self._build(B, T, False, reference=layers, adain=sites or None))
         bp.io["latent"].copy_(torch.from_numpy(latent))
         bp.io["t_emb"].copy_(torch.from_numpy(np.concatenate([t_emb, t_emb[:1]], axis=0)))
         bp.io["context"].copy_(torch.from_numpy(np.concatenate([context, rc], axis=0)))

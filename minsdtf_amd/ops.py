@@ -289,6 +289,20 @@ def reference_latent(*, z, noise, coef, out, n, num_steps, step_ptr=None, name="
     return Call(lib.msd_reference_latent, (C.byref(r),), name, keep=r)
 
 
+ADAIN_RESIDENT_HW = 1024   # csrc/adain.hip AD_RESIDENT_HW: the largest hw whose row slab msd_reference_adain keeps in registers
+
+
+def reference_adain(*, x, ref, rows, hw, c, mix=None, eps=1e-6, name="reference_adain") -> Call:
+    """msd_reference_adain: x[b] = mix[b] * x[b] + (1 - mix[b]) * ((x[b] - mean_b) * std_r / std_b + mean_r) per channel, the statistics
+    over the hw pixels, in place - reference AdaIN of a reference-only job.  x bf16 [rows][hw][c], ref bf16 [hw][c] (apart from
+    those rows), mix fp32 [rows] or None (all 0)."""
+    lib = _lib.load()
+    a = _lib.MsdReferenceAdain()
+    a.x, a.ref, a.mix = _p(x), _p(ref), _p(mix)
+    a.rows, a.hw, a.c, a.eps = int(rows), int(hw), int(c), float(eps)
+    return Call(lib.msd_reference_adain, (C.byref(a),), name, keep=a)
+
+
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:
     lib = _lib.load()
     return Call(lib.msd_add_bf16, (_p(a), _p(b), _p(out), n), name)

@@ -15,19 +15,82 @@ which is one ``msd_attention_joint`` launch per block (the blend is the online s
 stated deviation from diffusers: n_ref is ONE draw (not a fresh one per step) and r runs once, with the conditional context of
 sample 0 (not with both contexts), so the result is a function of the arguments and the cost is one row.
 
+Reference AdaIN (the extension's ``reference_adain`` and ``reference_adain+attn`` preprocessors; diffusers' ``reference_adain``)
+is the field ``adain``: at a chosen set of block outputs (``ADAIN_SITES``) each generated row's feature map is renormalised,
+channel by channel, to the mean and standard deviation the reference row has at the same place (one ``msd_reference_adain``
+launch per site, blended by the same ``mix``).  Attention carries the subject, AdaIN the palette and contrast.
+
 This module is the host side and needs no GPU: the job description (``ReferenceSpec`` / ``parse``), the rate table (``rates``),
-the reference noise (``draw_noise``) and a float64 statement of the kernel (``joint_attention_reference``).
+the reference noise (``draw_noise``), the AdaIN site table (``ADAIN_SITES`` / ``adain_sites``) and float64 statements of the
+kernels (``joint_attention_reference``, ``adain_reference``).
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Any, FrozenSet, Optional
+from fractions import Fraction
+from typing import Any, FrozenSet, Optional, Tuple
 
 import numpy as np
 
 ALIASES = {"mid": "mid_block.attentions.0"}
-FIELDS = ("image", "latent", "fidelity", "layers", "noise")
+FIELDS = ("image", "latent", "fidelity", "layers", "noise", "adain")
 NOISE_STREAM = 3   # default_rng([seed, 3]): the convention of hires_noise (1: a job's step draws, 2: the hires re-noise draw)
+
+
+_ADAIN_DOWN = ("down_blocks.1.attentions.0", "down_blocks.1.attentions.1", "down_blocks.2.attentions.0", "down_blocks.2.attentions.1",
+               "down_blocks.3.resnets.0", "down_blocks.3.resnets.1")
+_ADAIN_UP = ("up_blocks.0.resnets.0", "up_blocks.0.resnets.1", "up_blocks.0.upsamplers.0.conv", "up_blocks.1.attentions.0",
+             "up_blocks.1.attentions.1", "up_blocks.1.upsamplers.0.conv", "up_blocks.2.attentions.0", "up_blocks.2.attentions.1")
+# The fifteen AdaIN sites in forward order: (the name of the call whose output is the site, its position weight gw).  gw is
+# 2 (1 - i / 6) down the encoder, 0 at the mid block and 2 i / 8 up the decoder, kept as exact fractions of the integer
+# positions: a site applies when gw < weight, strictly.  No site at the first level and none on a downsampler; where a block
+# ends in an upsampler the site is the upsampler conv's output.
+ADAIN_SITES: Tuple[Tuple[str, Fraction], ...] = (
+    tuple((n, Fraction(2 * (6 - i), 6)) for i, n in enumerate(_ADAIN_DOWN)) + (("mid_block.resnets.1", Fraction(0)),)
+    + tuple((n, Fraction(2 * i, 8)) for i, n in enumerate(_ADAIN_UP)))
+ADAIN_DEFAULT_WEIGHT = 1.0   # the extension's default: seven sites, all at C = 1280
+
+
+def adain_sites(weight) -> FrozenSet[str]:
+    """The sites with gw < weight (strictly; the comparison is exact: gw is a fraction of the integer position and a float is a
+    dyadic rational).  ValueError for a weight that is not a finite float in (0, 2] - every such weight selects the mid block."""
+    try:
+        w = float(weight)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"reference_only: adain = {weight!r} must be a weight in (0, 2]") from e
+    if not 0.0 < w <= 2.0:   # (NaN fails both comparisons)
+        raise ValueError(f"reference_only: adain = {weight!r} must be a weight in (0, 2]")
+    sites = frozenset(n for n, gw in ADAIN_SITES if gw < Fraction(w))
+    if not sites:
+        raise ValueError(f"reference_only: adain = {weight!r} selects no site")
+    return sites
+
+
+def _adain(value) -> Optional[FrozenSet[str]]:
+    """The `adain` field -> a non-empty frozenset of site names, or None (off)."""
+    if value is None:
+        return None
+    names = dict(ADAIN_SITES)
+    if isinstance(value, str):
+        if value == "auto":
+            return adain_sites(ADAIN_DEFAULT_WEIGHT)
+        if value == "all":
+            return frozenset(names)
+        value = [value]
+    elif isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"reference_only: adain = {value!r} must be None, 'auto', 'all', a weight in (0, 2] or site names")
+    elif isinstance(value, (int, float, np.integer, np.floating)):
+        return adain_sites(value)
+    try:
+        value = list(value)
+    except TypeError as e:
+        raise ValueError(f"reference_only: adain = {value!r} must be None, 'auto', 'all', a weight in (0, 2] or site names") from e
+    if not value:
+        raise ValueError("reference_only: adain selects no site")
+    for n in value:
+        if not isinstance(n, str) or n not in names:
+            raise ValueError(f"reference_only: adain: unknown site {n!r}: 'auto', 'all', a weight or of {', '.join(names)}")
+    return frozenset(value)
 
 
 def layer_names():
@@ -42,27 +105,39 @@ class ReferenceSpec:
     """Exactly one of ``image`` (anything ``preprocessed_image`` takes; encoded by the VAE encoder) and ``latent`` (a
     (1, h, w, 4) array, used as is); ``fidelity`` in [0, 1]: the share of the plain self-attention in the unconditional rows;
     ``layers``: "all", "mid" or attention block names (engine.PAG_LAYERS); ``noise``: the (1, h, w, 4) draw n_ref, or None for
-    ``draw_noise``."""
+    ``draw_noise``; ``adain``: None (off), "auto" (weight 1.0), "all" (the fifteen ADAIN_SITES), a weight in (0, 2] selecting the
+    sites with gw < weight, or site names - reference AdaIN at those block outputs.  With ``adain`` given, ``layers`` may be
+    empty ([] or None): AdaIN without the attention part."""
     image: Any = None
     latent: Any = None
     fidelity: float = 0.5
     layers: Any = "all"
     noise: Any = None
+    adain: Any = None
 
 
 @dataclass(frozen=True)
 class Resolved:
-    """A ReferenceSpec checked: one of image / latent, fidelity a float in [0, 1], layers a non-empty frozenset of block names."""
+    """A ReferenceSpec checked: one of image / latent, fidelity a float in [0, 1], layers a frozenset of block names (empty only
+    next to AdaIN sites), adain a non-empty frozenset of site names or None."""
     image: Any
     latent: Optional[np.ndarray]
     fidelity: float
     layers: FrozenSet[str]
     noise: Optional[np.ndarray]
+    adain: Optional[FrozenSet[str]] = None
 
     @property
     def key(self) -> tuple:
-        """The layer set in a fixed order: what an engine is keyed by (never the image, the draw or the fidelity)."""
-        return tuple(sorted(self.layers))
+        """The layer set in a fixed order: what an engine is keyed by (never the image, the draw or the fidelity).  With AdaIN
+        sites it also holds their sorted tuple, as one last element."""
+        layers = tuple(sorted(self.layers))
+        return layers if self.adain is None else layers + (("adain",) + tuple(sorted(self.adain)),)
+
+    @property
+    def adain_key(self) -> Optional[tuple]:
+        """The AdaIN sites in a fixed order, or None."""
+        return None if self.adain is None else tuple(sorted(self.adain))
 
 
 def _latent(x, what):
@@ -77,7 +152,8 @@ def _latent(x, what):
 def parse(ref) -> Optional[Resolved]:
     """None -> None; a ReferenceSpec or a dict of its fields -> the checked description.  ValueError for an unknown field, both or
     neither of image / latent, a latent or noise of another shape than (1, h, w, 4) (or two different ones), a fidelity outside
-    [0, 1], an empty layer set or an unknown layer name."""
+    [0, 1], an empty layer set (unless `adain` selects sites) or an unknown layer name, and for an `adain` that is none of None,
+    "auto", "all", a weight in (0, 2] that selects a site, a site name or a non-empty iterable of site names."""
     if ref is None:
         return None
     if isinstance(ref, Resolved):
@@ -102,7 +178,8 @@ def parse(ref) -> Optional[Resolved]:
         names = list(valid)
     else:
         names = [ref.layers] if isinstance(ref.layers, str) else list(ref.layers if ref.layers is not None else ())
-    if not names:
+    adain = _adain(ref.adain)
+    if not names and adain is None:
         raise ValueError("reference_only: no layer selected")
     layers = set()
     for n in names:
@@ -114,7 +191,7 @@ def parse(ref) -> Optional[Resolved]:
     noise = None if ref.noise is None else _latent(ref.noise, "noise")
     if latent is not None and noise is not None and latent.shape != noise.shape:
         raise ValueError(f"reference_only: noise {noise.shape} and latent {latent.shape} differ in shape")
-    return Resolved(ref.image, latent, fidelity, frozenset(layers), noise)
+    return Resolved(ref.image, latent, fidelity, frozenset(layers), noise, adain)
 
 
 def draw_noise(h: int, w: int, seed=None) -> np.ndarray:
@@ -182,4 +259,31 @@ def joint_attention_reference(q, k, v, k_ref, v_ref, mix, heads: int) -> np.ndar
             joint = attend(qh, np.concatenate([kh, heads_of(k_ref, Tr)], 1), np.concatenate([vh, heads_of(v_ref, Tr)], 1))
             o = joint if f == 0.0 else f * plain + (1.0 - f) * joint
         out[b] = o.transpose(1, 0, 2).reshape(S, C)
+    return out
+
+
+def adain_reference(x, ref, mix=None, eps: float = 1e-6) -> np.ndarray:
+    """float64 statement of msd_reference_adain.  x (rows, hw, C), ref (hw, C), mix (rows,) or None (all 0).  Returns (rows, hw, C):
+
+        mean, var = var_mean(x[b], over the pixels, correction=0)        std = sqrt(max(var, 0) + eps)
+        mean_acc, std_acc likewise from ref
+        y = ((x[b] - mean) / std) * std_acc + mean_acc                   out[b] = mix[b] * x[b] + (1 - mix[b]) * y
+
+    which is diffusers' ``reference_adain`` (torch.var_mean(..., correction=0), ((x - mean) / std) * std_acc + mean_acc) with
+    its ``style_fidelity`` blend of the unconditional rows.  A row with mix == 1 is returned as it is, whatever it holds."""
+    x, ref = np.asarray(x, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    rows = x.shape[0]
+    mix = np.zeros(rows) if mix is None else np.asarray(mix, dtype=np.float64).reshape(rows)
+    mean_r = ref.mean(axis=0)
+    std_r = np.sqrt(np.maximum(((ref - mean_r) ** 2).mean(axis=0), 0.0) + eps)
+    out = np.empty_like(x)
+    for b in range(rows):
+        f = float(mix[b])
+        if f == 1.0:
+            out[b] = x[b]
+            continue
+        mean = x[b].mean(axis=0)
+        std = np.sqrt(np.maximum(((x[b] - mean) ** 2).mean(axis=0), 0.0) + eps)
+        y = (x[b] - mean) * (std_r / std) + mean_r
+        out[b] = y if f == 0.0 else f * x[b] + (1.0 - f) * y
     return out

@@ -75,12 +75,13 @@ class DenoiseEngine:
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
-                 sampler=None, tiled=None, regions: int = 0, pag=None, region_mode: str = "latent", reference=None, hypertile=None):
+                 sampler=None, tiled=None, regions: int = 0, pag=None, region_mode: str = "latent", reference=None, hypertile=None,
+                 adain=None):
         unet._require_weights()
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
-        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag, region_mode, reference, hypertile)
-        if self.reference and guidance > 0.0 and t_cond != t_uncond:
+        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag, region_mode, reference, hypertile, adain)
+        if self.reference is not None and guidance > 0.0 and t_cond != t_uncond:
             raise ValueError("reference_only: the negative prompt must have the conditional context's token length "
                              f"({t_uncond} != {t_cond} tokens): the reference row rides in the one fused pass")
         self.use_graph = use_graph
@@ -105,7 +106,7 @@ class DenoiseEngine:
             passes = [(0, (1 + RC) * B, t_cond, "both")]
         else:
             passes = [(0, B, t_uncond, "uncond"), (B, RC * B, t_cond, "cond")]
-        if self.reference:   # one more row, the reference, last in the one pass
+        if self.reference is not None:   # one more row, the reference, last in the one pass
             (row0, nb, t, tag), = passes
             passes = [(row0, nb + 1, t, tag)]
         self.passes = passes
@@ -130,9 +131,9 @@ class DenoiseEngine:
         _lib.track_graph_owner(self)
 
     def _check_options(self, control_net, streams, inpaint, tcd, sampler, tiled, regions, pag=None, region_mode="latent",
-                       reference=None, hypertile=None) -> None:
+                       reference=None, hypertile=None, adain=None) -> None:
         """The option combinations an engine refuses (generate_image refuses them earlier, by argument name: _REFUSED; these guard
-        direct construction).  Sets `sampler`, `tiled`, `regions`, `pag`, `reference` and `hypertile`."""
+        direct construction).  Sets `sampler`, `tiled`, `regions`, `pag`, `reference`, `adain` and `hypertile`."""
         # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
         # the 8-wide coefficient rows, the previous denoised estimate and (stochastic samplers) per-step draws on the device
         self.sampler = smp.parse(sampler)
@@ -177,11 +178,18 @@ class DenoiseEngine:
         # the u and c rows, the reference latent noised to the step's level (msd_reference_latent at the head of the step plan);
         # in the selected blocks the rows in front of it attend to its keys too (msd_attention_joint, `ref_mix` per row).  The step
         # kernels still read eps as [2B][n]: the reference row's prediction is written and never read (minsdtf_amd/reference.py)
-        self.reference = frozenset(reference) if reference else None
-        if self.reference:
+        # adain (the set of reference AdaIN sites of such a job, reference.ADAIN_SITES, or None): behind those block outputs the rows
+        # in front of the reference row are renormalised to its channel statistics (msd_reference_adain, the same `ref_mix`); the
+        # layer set may then be empty (AdaIN without the attention part)
+        self.adain = frozenset(adain) if adain else None
+        self.reference = frozenset(reference or ()) if (reference or self.adain) else None
+        if self.reference is not None:
             unknown = self.reference - set(engine.PAG_LAYERS)
             if unknown:
                 raise ValueError(f"reference_only: unknown layer(s) {sorted(unknown)}")
+            unknown = (self.adain or frozenset()) - {n for n, _gw in reference_mod.ADAIN_SITES}
+            if unknown:
+                raise ValueError(f"reference_only: unknown adain site(s) {sorted(unknown)}")
             if control_net is not None or inpaint or tcd or tiled is not None or R or self.pag or streams == 2:
                 raise ValueError("reference_only: text-to-image on one stream only (no ControlNet, inpainting, TCD, tiled, regions, pag, "
                                  "denoise_streams = 2)")
@@ -194,7 +202,7 @@ class DenoiseEngine:
             if len(self.hypertile) != 3:
                 raise ValueError(f"hypertile: {hypertile!r} is not (nh, nw, depth)")
             hypertile_mod.level_geometry(self.h, self.w, *self.hypertile)   # (ValueError for windows the levels cannot take)
-            if control_net is not None or inpaint or tiled is not None or R or self.pag or self.reference or streams == 2:
+            if control_net is not None or inpaint or tiled is not None or R or self.pag or self.reference is not None or streams == 2:
                 raise ValueError("hypertile: text-to-image on one stream only (no ControlNet, inpainting, tiled, regions, pag, "
                                  "reference_only, denoise_streams = 2)")
 
@@ -260,9 +268,9 @@ class DenoiseEngine:
         dev = unet.device
         n = h * w * 4
         RC = 1 if self.region_attn else (R or (2 if self.pag else 1))
-        self.eps = torch.zeros(((1 + RC) * B if self.cfg else RC * B) + (1 if self.reference else 0), n, dtype=torch.float32, device=dev)
+        self.eps = torch.zeros(((1 + RC) * B if self.cfg else RC * B) + (1 if self.reference is not None else 0), n, dtype=torch.float32, device=dev)
         self.ref_z = self.ref_noise = self.ref_latent = self.ref_coef = self.ref_mix = None
-        if self.reference:
+        if self.reference is not None:
             self.ref_z, self.ref_noise, self.ref_latent = (torch.zeros(1, h, w, 4, dtype=torch.float32, device=dev) for _ in range(3))
             self.ref_coef = torch.zeros(self.num_steps, 2, dtype=torch.float32, device=dev)
             self.ref_mix = torch.zeros((2 if self.cfg else 1) * B, dtype=torch.float32, device=dev)
@@ -303,10 +311,10 @@ class DenoiseEngine:
             extra = dict(pag_layers=self.pag, perturbed=B) if self.pag and tag != "uncond" else {}
             if self.region_attn and tag != "uncond":   # the conditional rows are the last B rows of their pass
                 extra = dict(region_attn=(R, B, region_planes))
-            if self.reference:   # x_r of this step first, then the forward whose last row reads it
+            if self.reference is not None:   # x_r of this step first, then the forward whose last row reads it
                 step.rec(ops.reference_latent, z=self.ref_z, noise=self.ref_noise, coef=self.ref_coef, step_ptr=self.step_ptr,
                          out=self.ref_latent, n=n, num_steps=self.num_steps)
-                extra = dict(reference=(self.reference, self.ref_latent, self.ref_mix))
+                extra = dict(reference=(self.reference, self.ref_latent, self.ref_mix), adain=self.adain)
             if self.hypertile is not None:
                 extra = dict(window=self.hypertile[:2], window_depth=self.hypertile[2])
             engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps, **extra)
@@ -397,7 +405,7 @@ class DenoiseEngine:
                 context = np.concatenate([np.asarray(c, dtype=np.float32) for c in context], axis=0)
         if getattr(self, "pag", None):   # the p rows read the conditional context again
             context = torch.cat([context, context], dim=0) if isinstance(context, torch.Tensor) else np.concatenate([context, context], axis=0)
-        if getattr(self, "reference", None):   # the reference row reads the conditional context of sample 0
+        if getattr(self, "reference", None) is not None:   # the reference row reads the conditional context of sample 0
             context = torch.cat([context, context[:1]], dim=0) if isinstance(context, torch.Tensor) else np.concatenate([context, context[:1]], axis=0)
         if not self.cfg:
             return {"cond": context}
@@ -916,6 +924,11 @@ class StableDiffusionBase:
         the share of the plain self-attention in the unconditional rows (diffusers' style_fidelity).  (`reference_image` is
         image_to_image's start picture, another thing.)  Works with every sampler, with shard_batch and with host_loop=True; at most
         2 * tiled.MAX_VIEW_BATCH UNet rows (2 * batch_size + 1); the negative prompt has the prompt's token length.
+        Its field ``adain`` (None, "auto" = weight 1.0, "all", a weight in (0, 2] or site names of reference.ADAIN_SITES) adds reference
+        AdaIN (the extension's reference_adain / reference_adain+attn): behind the selected block outputs every generated row's
+        feature map is renormalised, channel by channel, to the mean and standard deviation the reference row has there (one
+        msd_reference_adain launch per site, in place, the unconditional rows blended by ``fidelity``); with ``adain`` given
+        ``layers`` may be [] (AdaIN alone).  Same refusals, row cap and token-length rule; the engine is keyed by both sets.
         ``hypertile`` (a hypertile.HypertileSpec or a dict {"tile": 512, "depth": 0}; txt2img only): HyperTile - the self-attention of
         the attention blocks of the UNet levels 0 .. depth is taken inside non-overlapping windows of `tile` picture pixels (an int
         or (height, width), a multiple of 64 * 2**depth that divides the picture), one msd_attention_windowed launch per block in
@@ -1093,7 +1106,8 @@ class StableDiffusionBase:
             eng = self._denoise_pass(u, c, z, num_steps, g, phi, start_index, run_steps, callback,
                                      dict(sampler=sname, regions=None if reg is None else len(c), pag=None if pg is None else pg.key,
                                           region_mode="attention" if reg is not None and reg.mode == "attention" else None,
-                                          reference=None if ref is None else ref.key, hypertile=ht_key),
+                                          reference=None if ref is None else tuple(sorted(ref.layers)),
+                                          adain=None if ref is None else ref.adain_key, hypertile=ht_key),
                                      dict(hint_image=a.get("hint"), inpaint=(a["encoded"], a["noise"], a["mask"]) if inpainting else None,
                                           step_noise=a.get("tcd") if spec is None else a.get("sampler_z"), sampler=sched,
                                           regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale,
@@ -1340,7 +1354,10 @@ class StableDiffusionBase:
         # (a PAG job: the selected blocks only - the scale is a per-call upload)
         key = key if not opts.get("pag") else key + (("pag", tuple(sorted(opts["pag"]))),)
         # (a reference-only job: the selected blocks only - the image, the draw and the fidelity are per-call uploads)
-        key = key if not opts.get("reference") else key + (("reference", tuple(sorted(opts["reference"]))),)
+        # (with reference AdaIN the site set too, behind the blocks - which may then be none - and only when it is present)
+        if opts.get("reference") or opts.get("adain"):
+            sites = (("adain",) + tuple(sorted(opts["adain"])),) if opts.get("adain") else ()
+            key = key + (("reference", tuple(sorted(opts.get("reference") or ()))) + sites,)
         # (a HyperTile job: the number of windows and the depth - there is nothing else to it)
         return key if not opts.get("hypertile") else key + (("hypertile",) + tuple(int(v) for v in opts["hypertile"]),)
 
@@ -1351,7 +1368,7 @@ class StableDiffusionBase:
         alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is
         built: a re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than
         the job's own engines - one for a plain job, two for a hires job."""
-        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode", "reference", "hypertile"}:
+        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode", "reference", "hypertile", "adain"}:
             raise TypeError(f"_engine: unknown option among {sorted(opts)}")
         key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, **opts)
         keep = {key} | set(job_keys or ())
@@ -1372,7 +1389,7 @@ class StableDiffusionBase:
                                 streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=opts.get("sampler"),
                                 tiled=opts.get("tiled"), regions=opts.get("regions") or 0, pag=opts.get("pag"),
                                 region_mode=opts.get("region_mode") or "latent", reference=opts.get("reference"),
-                                hypertile=opts.get("hypertile"))
+                                hypertile=opts.get("hypertile"), adain=opts.get("adain"))
             self._engines[key] = eng
         return eng
 
@@ -1415,10 +1432,11 @@ class StableDiffusionBase:
             ref, (z_ref, n_ref), rates, i = reference
             x_r = reference_mod.reference_latent_host(z_ref, n_ref, rates[i])
             rc = np.asarray(context[:1], dtype=np.float32)
-            c = self.diffusion_model.predict_reference([latent, t_emb, context], x_r, ref.layers, 0.0, ref_context=rc)
+            c = self.diffusion_model.predict_reference([latent, t_emb, context], x_r, ref.layers, 0.0, ref_context=rc, adain=ref.adain)
             if g <= 0.0:
                 return c
-            u = self.diffusion_model.predict_reference([latent, t_emb, unconditional_context], x_r, ref.layers, ref.fidelity, ref_context=rc)
+            u = self.diffusion_model.predict_reference([latent, t_emb, unconditional_context], x_r, ref.layers, ref.fidelity, ref_context=rc,
+                                                        adain=ref.adain)
             e = u + g * (c - u)
             return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
 
