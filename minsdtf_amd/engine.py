@@ -528,7 +528,8 @@ class Emitter:
         return out
 
     def attentions(self, x: Act, name, ctx_kv, ctx_len, heads=8, free_input=False, shared: int = 1, perturbed: int = 0,
-                   regions: int = 0, region_rows: int = 0, region_w=None, reference: int = 0, mix=None, window=None) -> Act:
+                   regions: int = 0, region_rows: int = 0, region_w=None, reference: int = 0, mix=None, window=None,
+                   colsum=None) -> Act:
         """Attentions / TransformerBlock / CrossAttention / GEGLU (diffusion_model.py:54-153).  shared > 1 (SHARE_CFG_PREFIX): `x` holds
         `shared` identical copies of x.B / shared samples (the cond and uncond halves in front of the first cross-attention): norm,
         proj_in, q|k|v, the self-attention and its to_out run on ONE copy, their result (rows + LayerNorm partials) is replicated, and the
@@ -549,9 +550,19 @@ class Emitter:
         window = (nh, nw) (HyperTile, minsdtf_amd/hypertile.py): attn1 is ONE msd_attention_windowed launch in place of msd_attention -
         the attention is taken inside nh x nw non-overlapping windows of H / nh x W / nw tokens, on the operands where the q|k|v GEMM
         wrote them.  Also with shared > 1 (the launch runs on the one copy); not with perturbed or reference.  None records exactly
-        the plain block."""
+        the plain block.
+        colsum = (out, workspace, row0, rows) (self-attention guidance, minsdtf_amd/sag.py): right behind attn1, while q and k are
+        live, ONE msdx_attention_colsum launch writes the attention every key of the rows row0 .. row0 + rows - 1 receives - fp32
+        [rows][H * W] to `out`, through `workspace` (ops.colsum_workspace_floats(rows, heads, H * W) floats).  Head size 160 (the mid
+        block); not with shared > 1, reference or a window, and not over perturbed rows.  None records exactly the plain block."""
         p = self.p
         x_all = x
+        if colsum is not None:
+            _cs_out, _cs_ws, cs_row0, cs_rows = colsum
+            if x.C // heads != 160 or shared > 1 or reference or window is not None or cs_row0 < 0 or cs_rows < 1 \
+                    or cs_row0 + cs_rows > x.B - perturbed:
+                raise ValueError(f"{name}: colsum over rows {cs_row0} .. {cs_row0 + cs_rows - 1} of {x.B} at head size {x.C // heads} "
+                                 f"(shared = {shared}, perturbed = {perturbed}, reference = {reference}, window = {window})")
         if window is not None:
             nh, nw = (int(v) for v in window)
             if perturbed or reference:
@@ -605,6 +616,9 @@ class Emitter:
         if perturbed:   # the last `perturbed` rows: out = V
             p.rec(ops.attention_identity, vt=vt.at((B - perturbed) * C * sp * 2), out=a1.buf.at((B - perturbed) * S * C * 2),
                   batch=perturbed, channels=C, s=S, vt_ld=sp, o_ld=C, name=tb + ".attn1.identity")
+        if colsum is not None:
+            p.rec(ops.attention_colsum, q=q.buf.at(cs_row0 * S * C * 2), k=k.buf.at(cs_row0 * S * C * 2), out=colsum[0], workspace=colsum[1],
+                  batch=cs_rows, heads=heads, head_dim=d, s=S, q_ld=C, k_ld=C, name=tb + ".attn1.colsum")
         p.free(q, k, vt)
         if shared > 1:
             t1_wide = p.act(B * shared, H, Wd, C)
@@ -780,13 +794,14 @@ def _region_kw(region_attn, x: Act) -> dict:
 
 
 def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1,
-                  pag_layers=frozenset(), perturbed: int = 0, region_attn=None, ref_kw=None, site=None) -> Act:
+                  pag_layers=frozenset(), perturbed: int = 0, region_attn=None, ref_kw=None, site=None, sag=None) -> Act:
     """Down path + mid block shared by the UNet (diffusion_model.py:193-229) and the ControlNet.  shared > 1: `x` (conv_in's output) is
     `shared` identical copies of x.B / shared samples - the first ResBlock and the front of the first transformer block run on one.
     pag_layers / perturbed: the attention blocks (by name) whose attn1 is the identity for the last `perturbed` rows.
     ref_kw: block name -> Emitter.attentions' reference keywords (emit_unet's `reference`; shared is 1 then) or its window
     keywords (emit_unet's `window`; also on the one copy of a shared first block).
-    site: (x, name of the call that produced it) -> None, emit_unet's reference AdaIN right behind a block output."""
+    site: (x, name of the call that produced it) -> None, emit_unet's reference AdaIN right behind a block output.
+    sag: Emitter.attentions' `colsum` for mid_block.attentions.0 (emit_unet's `sag`)."""
     def pert(block):
         return perturbed if block in pag_layers else 0
 
@@ -816,7 +831,7 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
             outputs.append(x)
     x = e.res_block(x, "mid_block.resnets.0", 1280, temb=temb_of("mid_block.resnets.0"))
     x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True, perturbed=pert("mid_block.attentions.0"),
-                     **_region_kw(region_attn, x), **ref_kw("mid_block.attentions.0"))
+                     **_region_kw(region_attn, x), **ref_kw("mid_block.attentions.0"), **({} if sag is None else dict(colsum=sag)))
     x = e.res_block(x, "mid_block.resnets.1", 1280, temb=temb_of("mid_block.resnets.1"), free_input=True)
     site(x, "mid_block.resnets.1")
     return x
@@ -824,7 +839,7 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
 
 def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w: int, temb, ctx_kv, ctx_len: int,
               eps_out_f32, controls=None, control_taps=None, pag_layers=None, perturbed: int = 0, region_attn=None, *,
-              reference=None, window=None, window_depth: int = 0, adain=None) -> None:
+              reference=None, window=None, window_depth: int = 0, adain=None, sag=None) -> None:
     """DiffusionModel graph (diffusion_model.py:184-279).
 
     window = (nh, nw) / window_depth = D (HyperTile, minsdtf_amd/hypertile.py): the self-attention of the attention blocks of levels
@@ -849,6 +864,10 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
     right behind the call that produces a selected site, before anything reads it, ONE msd_reference_adain launch renormalises
     the NB - 1 generated rows of the site buffer to the statistics of its last row, in place, blended by the reference `mix` -
     so the skip connection and the onward path both see the result.  None records exactly the plan without it.
+
+    sag = (colsum_buf, workspace, row0, rows) (self-attention guidance, minsdtf_amd/sag.py): mid_block.attentions.0 also writes the
+    attention map of the rows row0 .. row0 + rows - 1 (Emitter.attentions' `colsum`: fp32 [rows][mh * mw], (mh, mw) =
+    unet_levels(h, w)[3]).  The mid block is never part of the shared prefix.  None records exactly the plain forward.
 
     latent_f32: fp32 [latent_batch_mod][h][w][4] (sample b reads row b % latent_batch_mod);
     temb = (table, step_stride, batch_stride, {resblock: column}); eps_out_f32: fp32 [NB][h][w][4].
@@ -927,7 +946,7 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
         return dict(reference=1, mix=ref_mix) if block in ref_layers else {}
 
     x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared, pag_layers=pag_layers, perturbed=perturbed,
-                      region_attn=region_attn, ref_kw=ref_kw, site=site)
+                      region_attn=region_attn, ref_kw=ref_kw, site=site, sag=sag)
     p.mark("controls")   # everything above is independent of the ControlNet (its encoder may run beside it on another stream)
     if control_taps is not None:
         e_c, feats = control_taps
@@ -966,6 +985,34 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
         p.rec(ops.conv_direct, x=g.buf, w=e.W["conv_out.w"], bias=e.W["conv_out.b"], out=eps_out_f32, batch=NB, h_in=h, w_in=w,
               c_in=320, c_out=4, ksize=3, in_dtype=ops.OUT_BF16, out_dtype=ops.OUT_F32, name="conv_out")
     p.free(g)
+
+
+def emit_sag_pass(e: Emitter, latent_f32, eps_f32, coef, coef_stride: int, num_steps: int, colsum, params, degraded_f32, B: int,
+                  h: int, w: int, temb, ctx_kv, ctx_len: int, eps_out_f32) -> None:
+    """The second, dependent half of a self-attention-guidance step (minsdtf_amd/sag.py), recorded behind the pass that wrote
+    `eps_f32` (its first B rows: the u rows, or the c rows of a job without guidance) and `colsum` (emit_unet's `sag`): ONE
+    msdx_sag_degrade launch builds the degraded latent fp32 [B][h][w][4] from the latent, those rows and the map - alpha_t / sigma_t
+    from columns 0 / 1 of row *step_ptr of `coef`, taps and threshold from `params` - then the UNet runs on it, B rows over the
+    first B rows of `ctx_kv`, into `eps_out_f32` (the d rows).  The step counter is read, not advanced."""
+    mh, mw = unet_levels(h, w)[3]
+    e.p.rec(ops.sag_degrade, latent=latent_f32, eps=eps_f32, coef=coef, coef_stride=coef_stride, step_ptr=e.step_ptr, colsum=colsum,
+            params=params, out=degraded_f32, batch=B, h=h, w=w, mh=mh, mw=mw, num_steps=num_steps, name="sag.degrade")
+    emit_unet(e, degraded_f32, B, B, h, w, temb, ctx_kv, ctx_len, eps_out_f32)
+
+
+def emit_sag_combine(p: Plan, eps_at, w_at, B: int, n: int, cfg: bool) -> int:
+    """The combine of a self-attention-guidance step in front of the unchanged guidance / sampler step; returns the row GROUP (of B
+    rows) of eps that step reads.  eps_at(g) / w_at(i): eps at row group g, plane i of sag.weights.
+    With guidance eps holds the groups (u, c, d, spare, spare): c' = k u + c - k d is msd_region_combine over (u, c, d) with the
+    planes (k, 1, -k) - v = k u; v = fma(1, c, v); v = fma(-k, d, v) - written to group 4, since that kernel's output is its
+    input's first group or apart from all of it; group 3 takes a bit-exact copy of u (regions = 1 with the plane of ones), so
+    the step reads (u, c') from group 3 on.  Without guidance eps holds (c, d): c' = (1 + s) c - s d in place over c, PAG's form."""
+    if not cfg:
+        p.rec(ops.region_combine, eps=eps_at(0), w=w_at(0), out=eps_at(0), regions=2, batch=B, n=n, name="sag.combine")
+        return 0
+    p.rec(ops.region_combine, eps=eps_at(0), w=w_at(1), out=eps_at(3), regions=1, batch=B, n=n, name="sag.copy_u")
+    p.rec(ops.region_combine, eps=eps_at(0), w=w_at(0), out=eps_at(4), regions=3, batch=B, n=n, name="sag.combine")
+    return 3
 
 
 def emit_controlnet_features(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w: int, temb, ctx_kv, ctx_len: int,

@@ -256,14 +256,16 @@ class DiffusionModel(HipModel):
         self._maybe_load(ckpt_path, lora_dict)
 
     def _build(self, B: int, T: int, with_controls: bool, pag_layers=None, regions: int = 0, reference=None, window=None,
-               adain=None) -> _BoundPlan:
+               adain=None, sag: bool = False) -> _BoundPlan:
         """pag_layers: the attention blocks whose self-attention is the identity map for ALL B rows (predict_perturbed).
         regions = R: all B rows are conditional rows over R region contexts (predict_regional): the context input is
         (R * B, T, 768), region-major, and `region_w` the four levels' weight planes (regions.pack_levels).
         reference = the attention blocks of a reference-only forward (predict_reference): the plan runs B + 1 rows, the last one the
         reference row read from `ref_latent`; `t_emb` and `context` carry its row last, `ref_mix` is fp32 [B]; eps keeps B rows.
         adain = the reference AdaIN sites of such a forward (reference.ADAIN_SITES); `reference` may then be an empty set.
-        window = (nh, nw, depth) of a HyperTile forward (predict_windowed): emit_unet's window / window_depth."""
+        window = (nh, nw, depth) of a HyperTile forward (predict_windowed): emit_unet's window / window_depth.
+        sag: the mid block's self-attention also writes the attention map of all B rows (predict_sag_map): io["sag_A"], fp32
+        [B][mh * mw]."""
         h, w = self.h, self.w
         reference = frozenset(reference or ()) if (reference or adain) else None   # (an empty layer set next to AdaIN sites)
         NB = B + 1 if reference is not None else B
@@ -304,12 +306,19 @@ class DiffusionModel(HipModel):
             extra["adain"] = frozenset(adain)
         if window is not None:
             extra = dict(window=(window[0], window[1]), window_depth=window[2])
+        sag_A = None
+        if sag:
+            mh, mw = engine.unet_levels(h, w)[3]
+            sag_A = plan.alloc(B * mh * mw * 4)
+            extra = dict(sag=(sag_A, plan.alloc(ops.colsum_workspace_floats(B, 8, mh * mw) * 4), 0, B))
         engine.emit_unet(e, ins["latent"], B, NB, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls,
                          pag_layers=pag_layers, perturbed=B if pag_layers else 0, region_attn=region_attn, **extra)
         plan.finalize()
         bp = _BoundPlan(plan, self._use_graph)
         bp.io = {k: b.tensor(torch.float32, shapes[k]) for k, b in ins.items()}
         bp.io["eps"] = eps.tensor(torch.float32, (NB, h, w, 4))
+        if sag_A is not None:
+            bp.io["sag_A"] = sag_A.tensor(torch.float32, (B, mh * mw))
         for i, (st, shp) in enumerate(cstage):
             bp.io[f"control.{i}"] = st.tensor(torch.float32, shp)
         return bp
@@ -341,6 +350,15 @@ class DiffusionModel(HipModel):
         depth = int(depth)
         hypertile_mod.level_geometry(self.h, self.w, nh, nw, depth)   # (ValueError for windows the levels cannot take)
         return self._predict(x, None, window=(nh, nw, depth))
+
+    def predict_sag_map(self, x):
+        """predict_on_batch([latent, t_emb, context]) plus the self-attention map of mid_block.attentions.0 for all its rows:
+        (eps, A), A fp32 (B, mh * mw) with A[b][j] = the head-mean attention key j receives summed over the queries
+        (msdx_attention_colsum; (mh, mw) = engine.unet_levels(h, w)[3]).  The first pass of a self-attention-guidance step on the
+        host loop (minsdtf_amd/sag.py); eps is predict_on_batch's, bit for bit.  A bound plan of its own per (B, T)."""
+        if len(x) != 3:
+            raise ValueError("predict_sag_map takes [latent, t_emb, context] (no control tensors)")
+        return self._predict(x, None, sag=True)
 
     def predict_regional(self, x, contexts, level_weights):
         """predict_on_batch([latent, t_emb]) with every attn2 mixing the R region `contexts` (each (B, T, 768), T <= 96) per query by
@@ -408,7 +426,7 @@ class DiffusionModel(HipModel):
         bp.run()
         return bp.host("eps")[:B]
 
-    def _predict(self, x, pag_layers, window=None):
+    def _predict(self, x, pag_layers, window=None, sag=False):
         latent, t_emb, context = _np32(x[0]), _np32(x[1]), _np32(x[2])
         controls = [_np32(c) for c in x[3:]]
         if controls and len(controls) != 13:
@@ -419,13 +437,18 @@ class DiffusionModel(HipModel):
         key = (B, T, bool(controls)) if pag_layers is None else (B, T, False, ("pag", tuple(sorted(pag_layers))))
         if window is not None:
             key = (B, T, False, ("hypertile",) + tuple(window))
-        bp = self._bound(key, lambda: self._build(B, T, bool(controls), pag_layers, window=window))
+        if sag:
+            key = (B, T, False, ("sag",))
+        bp = self._bound(key, lambda: self._build(B, T, bool(controls), pag_layers, window=window, sag=sag))
         bp.io["latent"].copy_(torch.from_numpy(latent))
         bp.io["t_emb"].copy_(torch.from_numpy(t_emb))
         bp.io["context"].copy_(torch.from_numpy(context))
         for i, c in enumerate(controls):
             bp.io[f"control.{i}"].copy_(torch.from_numpy(c))
         bp.run()
+        if sag:
+            eps, A = bp.host(["eps", "sag_A"])
+            return eps, A
         return bp.host("eps")
 
     __call__ = predict_on_batch

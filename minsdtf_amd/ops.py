@@ -11,22 +11,23 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
-from . import _lib
+from . import _lib, _lib_ext
 from ._lib import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, OUT_BF16, OUT_F32, OUT_U8  # noqa: F401
 
 
 class Call:
     """One stream-ordered library call: ``fn(*args, stream)``."""
 
-    __slots__ = ("fn", "args", "name", "keep")
+    __slots__ = ("fn", "args", "name", "keep", "check")
 
-    def __init__(self, fn, args, name, keep=None):
-        self.fn, self.args, self.name, self.keep = fn, args, name, keep
+    def __init__(self, fn, args, name, keep=None, check=_lib.check):
+        """check: the owning library's (rc, name) -> raise (the extension library keeps its own error text)."""
+        self.fn, self.args, self.name, self.keep, self.check = fn, args, name, keep, check
 
     def __call__(self, stream: int) -> None:
         rc = self.fn(*self.args, stream)
         if rc != 0:
-            _lib.check(rc, self.name)
+            self.check(rc, self.name)
 
 
 def _p(x) -> Optional[int]:
@@ -301,6 +302,38 @@ def reference_adain(*, x, ref, rows, hw, c, mix=None, eps=1e-6, name="reference_
     a.x, a.ref, a.mix = _p(x), _p(ref), _p(mix)
     a.rows, a.hw, a.c, a.eps = int(rows), int(hw), int(c), float(eps)
     return Call(lib.msd_reference_adain, (C.byref(a),), name, keep=a)
+
+
+# ---- the extension library (include/minsdtf_hip_ext.h, minsdtf_amd/_lib_ext.py) ----------------------------------------------------
+def attention_colsum(*, q, k, out, workspace, batch, heads, head_dim, s, q_ld, k_ld, workspace_floats=None,
+                     name="attention_colsum") -> Call:
+    """msdx_attention_colsum: out[b][j] = (1 / heads) * sum_h sum_i softmax_j(q_h k_h^T)[i][j] - the attention every key receives
+    (self-attention guidance, minsdtf_amd/sag.py).  q bf16 [batch][s][q_ld] carrying scale * log2(e), k bf16 [batch][s][k_ld],
+    out fp32 [batch][s], workspace fp32 [batch][heads][s][2] (COLSUM_WS floats per (sample, head, query))."""
+    lib = _lib_ext.load()
+    a = _lib_ext.MsdxAttentionColsum()
+    a.q, a.k, a.out, a.workspace = _p(q), _p(k), _p(out), _p(workspace)
+    a.workspace_floats = int(colsum_workspace_floats(batch, heads, s) if workspace_floats is None else workspace_floats)
+    a.batch, a.heads, a.head_dim, a.s, a.q_ld, a.k_ld = int(batch), int(heads), int(head_dim), int(s), int(q_ld), int(k_ld)
+    return Call(lib.msdx_attention_colsum, (C.byref(a),), name, keep=a, check=_lib_ext.check)
+
+
+def colsum_workspace_floats(batch: int, heads: int, s: int) -> int:
+    """Floats of msdx_attention_colsum's workspace: (row maximum, row sum) per (sample, head, query)."""
+    return int(batch) * int(heads) * int(s) * 2
+
+
+def sag_degrade(*, latent, eps, coef, coef_stride, colsum, params, out, batch, h, w, mh, mw, num_steps, step_ptr=None,
+                name="sag.degrade") -> Call:
+    """msdx_sag_degrade: the degraded latent of a self-attention-guidance step.  latent / eps / out fp32 [batch][h][w][4], coef fp32
+    [num_steps][coef_stride] (columns 0, 1: alpha_t, sigma_t of row *step_ptr), colsum fp32 [batch][mh * mw], params fp32 [10]
+    (sag.params: the 9 taps, the threshold)."""
+    lib = _lib_ext.load()
+    d = _lib_ext.MsdxSagDegrade()
+    d.latent, d.eps, d.coef, d.step_ptr, d.colsum, d.params, d.out = _p(latent), _p(eps), _p(coef), _p(step_ptr), _p(colsum), _p(params), _p(out)
+    d.batch, d.h, d.w, d.mh, d.mw = int(batch), int(h), int(w), int(mh), int(mw)
+    d.coef_stride, d.num_steps = int(coef_stride), int(num_steps)
+    return Call(lib.msdx_sag_degrade, (C.byref(d),), name, keep=d, check=_lib_ext.check)
 
 
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:

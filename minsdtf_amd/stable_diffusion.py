@@ -36,6 +36,7 @@ from . import _lib, engine, ops
 from . import hires as hires_mod
 from . import hypertile as hypertile_mod
 from . import pag as pag_mod
+from . import sag as sag_mod
 from . import reference as reference_mod
 from . import regions as regions_mod
 from . import samplers as smp
@@ -76,11 +77,20 @@ class DenoiseEngine:
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
                  sampler=None, tiled=None, regions: int = 0, pag=None, region_mode: str = "latent", reference=None, hypertile=None,
-                 adain=None):
+                 adain=None, sag: bool = False):
         unet._require_weights()
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
         self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag, region_mode, reference, hypertile, adain)
+        # sag (self-attention guidance, minsdtf_amd/sag.py): the step records the UNet TWICE - behind the pass that holds the u rows
+        # (the c rows without guidance), whose mid block also writes the attention map `sag_A` (msdx_attention_colsum), ONE
+        # msdx_sag_degrade launch builds the degraded latent and a second forward of B rows over the same context K/V writes the d
+        # rows; the tail combines (u, c, d) in front of the unchanged step kernel (engine.emit_sag_pass / emit_sag_combine)
+        self.sag = bool(sag)
+        if self.sag and (control_net is not None or inpaint or tiled is not None or self.regions or self.pag or self.reference is not None
+                         or self.hypertile is not None or streams == 2):
+            raise ValueError("sag: text-to-image on one stream only (no ControlNet, inpainting, tiled, regions, pag, reference_only, "
+                             "hypertile, denoise_streams = 2)")
         if self.reference is not None and guidance > 0.0 and t_cond != t_uncond:
             raise ValueError("reference_only: the negative prompt must have the conditional context's token length "
                              f"({t_uncond} != {t_cond} tokens): the reference row rides in the one fused pass")
@@ -269,6 +279,15 @@ class DenoiseEngine:
         n = h * w * 4
         RC = 1 if self.region_attn else (R or (2 if self.pag else 1))
         self.eps = torch.zeros(((1 + RC) * B if self.cfg else RC * B) + (1 if self.reference is not None else 0), n, dtype=torch.float32, device=dev)
+        self.sag_A = self.sag_latent = self.sag_params = self.sag_w = None
+        if self.sag:
+            # eps row groups of B rows: (u, c, d, copy of u, c') with guidance, (c, d) without (engine.emit_sag_combine)
+            self.eps = torch.zeros((5 if self.cfg else 2) * B, n, dtype=torch.float32, device=dev)
+            mh, mw = engine.unet_levels(h, w)[3]
+            self.sag_A = torch.zeros(B, mh * mw, dtype=torch.float32, device=dev)
+            self.sag_latent = torch.zeros(B, h, w, 4, dtype=torch.float32, device=dev)
+            self.sag_params = torch.zeros(10, dtype=torch.float32, device=dev)
+            self.sag_w = torch.zeros(3 if self.cfg else 2, h, w, dtype=torch.float32, device=dev)
         self.ref_z = self.ref_noise = self.ref_latent = self.ref_coef = self.ref_mix = None
         if self.reference is not None:
             self.ref_z, self.ref_noise, self.ref_latent = (torch.zeros(1, h, w, 4, dtype=torch.float32, device=dev) for _ in range(3))
@@ -317,7 +336,17 @@ class DenoiseEngine:
                 extra = dict(reference=(self.reference, self.ref_latent, self.ref_mix), adain=self.adain)
             if self.hypertile is not None:
                 extra = dict(window=self.hypertile[:2], window_depth=self.hypertile[2])
+            sag_here = self.sag and tag == ("cond" if not self.cfg else "both" if len(passes) == 1 else "uncond")
+            if sag_here:   # this pass holds the u rows (the c rows without guidance) in its first B rows
+                mh, mw = engine.unet_levels(h, w)[3]
+                sag_ws = step.alloc(ops.colsum_workspace_floats(B, 8, mh * mw) * 4)
+                extra = dict(sag=(self.sag_A, sag_ws, 0, B))
             engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps, **extra)
+            if sag_here:
+                step.free(sag_ws)
+                d_rows = _Ptr(self.eps.data_ptr() + (2 if self.cfg else 1) * B * n * 4)
+                engine.emit_sag_pass(s_u, self.latent, eps_view, self.coef, int(self.coef.shape[1]), self.num_steps, self.sag_A,
+                                     self.sag_params, self.sag_latent, B, h, w, prep["table_u"], prep["kv_u"][tag], t, d_rows)
         return step
 
     def _build_tail(self, step, guidance, guidance_rescale, inpaint, tcd) -> "engine.Plan":
@@ -347,15 +376,20 @@ class DenoiseEngine:
             # c' = (1 + k) c - k p over the c rows; behind it the step kernels read [2B][n] (or [B][n]) as always
             cond = _Ptr(self.eps.data_ptr() + (B if self.cfg else 0) * n * 4)
             tail.rec(ops.region_combine, eps=cond, w=self.pag_w, out=cond, regions=2, batch=B, n=n, name="pag_combine")
+        eps_in = self.eps
+        if self.sag:   # (u, c, d) -> (u, c') where the step kernels read them; behind it they read [2B][n] (or [B][n]) as always
+            group = engine.emit_sag_combine(tail, lambda g_: _Ptr(self.eps.data_ptr() + g_ * B * n * 4),
+                                            lambda i: _Ptr(self.sag_w.data_ptr() + i * h * w * 4), B, n, self.cfg)
+            eps_in = _Ptr(self.eps.data_ptr() + group * B * n * 4)
         if self.sampler is None:
-            tail.rec(ops.cfg_step, eps=self.eps, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr, batch=B, n=n,
+            tail.rec(ops.cfg_step, eps=eps_in, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr, batch=B, n=n,
                      num_steps=num_steps, guidance=guidance, guidance_rescale=guidance_rescale, advance=2,
                      inpaint_init=ip.get("init"), inpaint_noise=ip.get("noise"), inpaint_mask=ip.get("mask"),
                      step_noise=self.step_noise, noise_coef=self.noise_coef)
         else:
             # (P needs no initial value: the first executed row has c_P = 0 and the kernel does not read it there)
             self.denoised_prev = torch.zeros(B, n, dtype=torch.float32, device=dev)
-            tail.rec(ops.sampler_step, eps=self.eps, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr,
+            tail.rec(ops.sampler_step, eps=eps_in, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr,
                      denoised_prev=self.denoised_prev, batch=B, n=n, num_steps=num_steps, guidance=guidance,
                      guidance_rescale=guidance_rescale, advance=2, inpaint_init=ip.get("init"), inpaint_noise=ip.get("noise"),
                      inpaint_mask=ip.get("mask"), step_noise=self.step_noise)
@@ -495,7 +529,7 @@ class DenoiseEngine:
 
     def prepare(self, contexts: Dict[str, np.ndarray], noise: np.ndarray, scheduler: Scheduler, timesteps,
                 start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None,
-                regions=None, pag_scale=None, reference=None) -> None:
+                regions=None, pag_scale=None, reference=None, sag=None) -> None:
         """Upload the per-call inputs and run the preparation plan.  Every array may be a host array or a (device) tensor.
         noise = None: the start latent is already in `self.latent` (written there by stream-ordered device work queued before
         this call: the hand-off of a hires job), nothing is uploaded for it.
@@ -509,7 +543,15 @@ class DenoiseEngine:
         pag_scale = the scale s of a PAG engine: the two planes fp32(1 + k), fp32(-k) (pag.weights, k from s and the engine's
         guidance in float64) are a per-call upload too, so another scale needs no other engine.
         reference = (z_ref (1, h, w, 4), n_ref (1, h, w, 4), fidelity) of an engine built with reference=<layers>: the two latents,
-        the rate table of this schedule and start index (reference.rates) and mix = [fidelity] * B + [0] * B are per-call uploads."""
+        the rate table of this schedule and start index (reference.rates) and mix = [fidelity] * B + [0] * B are per-call uploads.
+        sag = the sag.Resolved (or SagSpec / dict) of an engine built with sag=True: the 9 taps and the threshold (sag.params) and the
+        planes of the combine (sag.weights, k from the scale and the engine's guidance in float64) are per-call uploads too."""
+        if (sag is None) != (self.sag_w is None):
+            raise ValueError("prepare: `sag` goes with an engine built with sag=True, and only with one")
+        if self.sag_w is not None:   # taps, threshold and the combine's planes: per-call uploads, another scale needs no other engine
+            spec = sag_mod.parse(sag)
+            self.sag_params.copy_(torch.from_numpy(sag_mod.params(spec)))
+            self.sag_w.copy_(torch.from_numpy(sag_mod.weights(spec.scale, self.guidance, self.h, self.w)))
         if (reference is None) != (self.ref_mix is None):
             raise ValueError("prepare: `reference` goes with an engine built with reference=<layers>, and only with one")
         if self.ref_mix is not None:
@@ -641,18 +683,19 @@ class StableDiffusionBase:
     # ---- public entry points (reference :84-139)
     def text_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                       embedding=None, negative_embedding=None, seed=None, control_net_image=None, guidance_rescale=0.7,
-                      callback=None, hires=None, tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, **kw):
+                      callback=None, hires=None, tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, sag=None, **kw):
         """``hires``: None, or a hires.HiresSpec / dict for the two-pass hires fix; ``tiled``: None, or a tiled.TiledSpec / dict
         for tiled diffusion on a canvas larger than the pipeline's size; ``regions``: None, or a regions.Regions / dict for
         regional prompting, `prompt` being the base prompt; ``pag``: None, or a pag.PagSpec / dict for perturbed-attention
         guidance; ``reference_only``: None, or a reference.ReferenceSpec / dict for reference-only control; ``hypertile``: None, or a
-        hypertile.HypertileSpec / dict for windowed self-attention (see generate_image)."""
+        hypertile.HypertileSpec / dict for windowed self-attention; ``sag``: None, or a sag.SagSpec / dict for self-attention guidance
+        (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
                                    negative_embedding=negative_embedding, control_net_image=control_net_image,
                                    guidance_rescale=guidance_rescale, callback=callback, hires=hires, tiled=tiled, regions=regions,
-                                   pag=pag, reference_only=reference_only, hypertile=hypertile, **kw)
+                                   pag=pag, reference_only=reference_only, hypertile=hypertile, sag=sag, **kw)
 
     def image_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
@@ -885,7 +928,7 @@ class StableDiffusionBase:
                        diffusion_noise=None, seed=None, negative_embedding=None, control_net_image=None, inpaint_mask=None,
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
                        callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None,
-                       tiled=None, regions=None, pag=None, reference_only=None, hypertile=None):
+                       tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, sag=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
@@ -934,9 +977,25 @@ class StableDiffusionBase:
         or (height, width), a multiple of 64 * 2**depth that divides the picture), one msd_attention_windowed launch per block in
         place of msd_attention: with nh x nw windows the attention FLOPs fall by nh * nw.  The tile is fixed, never drawn.  With
         ``hires`` the spec applies to the second pass only, its geometry taken from the target size - the use it is for; one window
-        is the plain job.  Works with every sampler, on a TCD pipeline, with shard_batch and with host_loop=True."""
+        is the plain job.  Works with every sampler, on a TCD pipeline, with shard_batch and with host_loop=True.
+        ``sag`` (a sag.SagSpec or a dict {"scale": 0.75, "blur_sigma": 1.0, "threshold": 1.0}, diffusers' defaults; txt2img only):
+        self-attention guidance - every step the mid block's self-attention of the unconditional rows also yields the attention
+        each key receives (msdx_attention_colsum), the latent is blurred where that map exceeds ``threshold`` (msdx_sag_degrade) and
+        the UNet runs a second time on it with the unconditional context; eps = u + g (c - u) + s (u - d).  The second pass
+        depends on the first, so the step records the UNet twice, with the two launches in between, inside the one captured loop
+        graph; msd_region_combine writes c' = k u + c - k d (k = s / g) in front of the unchanged guidance / sampler step, so
+        `guidance_rescale` takes its reference std from c', as with ``pag``.  Without guidance the map comes from the c rows and
+        eps = (1 + s) c - s d.  Works with every sampler, on a TCD pipeline, with shard_batch and with host_loop=True; at most
+        2 * tiled.MAX_VIEW_BATCH UNet rows (3 * batch_size with guidance, 2 * batch_size without)."""
         given = dict(tiled=tiled, hires=hires, control_net_image=control_net_image, reference_image=reference_image,
-                     inpaint_mask=inpaint_mask, regions=regions, pag=pag, reference_only=reference_only)
+                     inpaint_mask=inpaint_mask, regions=regions, pag=pag, reference_only=reference_only, hypertile=hypertile)
+        sg = sag_mod.parse(sag)   # (ValueError for a bad description)
+        if sg is not None:
+            self._refuse_combinations("sag", given, host_loop)
+            rows = (3 if float(unconditional_guidance_scale) > 0.0 else 2) * int(batch_size)
+            if rows > 2 * tiled_mod.MAX_VIEW_BATCH:
+                raise ValueError(f"sag: {batch_size} image(s) are {rows} UNet rows per step, more than 2 * tiled.MAX_VIEW_BATCH = "
+                                 f"{2 * tiled_mod.MAX_VIEW_BATCH}: use a smaller batch")
         ht = hypertile_mod.parse(hypertile)   # (ValueError for a bad description)
         if ht is not None:
             self._refuse_combinations("hypertile", given, host_loop)
@@ -1065,11 +1124,11 @@ class StableDiffusionBase:
             ip = (encoded, noise, latent_mask[0]) if inpainting else None
             if spec is not None:
                 latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
-                                                 sampler_z, ip, region_w=region_w, pag=pg, hypertile=ht_key,
+                                                 sampler_z, ip, region_w=region_w, pag=pg, hypertile=ht_key, sag=sg,
                                                  reference=None if ref is None else (ref, ref_in, reference_mod.rates(sched, start_index)))
             else:
                 latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending, ip,
-                                         region_w=region_w, pag=pg, hypertile=ht_key,
+                                         region_w=region_w, pag=pg, hypertile=ht_key, sag=sg,
                                          reference=None if ref is None else (ref, ref_in, reference_mod.rates(self.scheduler, start_index)))
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
@@ -1107,11 +1166,12 @@ class StableDiffusionBase:
                                      dict(sampler=sname, regions=None if reg is None else len(c), pag=None if pg is None else pg.key,
                                           region_mode="attention" if reg is not None and reg.mode == "attention" else None,
                                           reference=None if ref is None else tuple(sorted(ref.layers)),
-                                          adain=None if ref is None else ref.adain_key, hypertile=ht_key),
+                                          adain=None if ref is None else ref.adain_key, hypertile=ht_key,
+                                          sag=None if sg is None else True),
                                      dict(hint_image=a.get("hint"), inpaint=(a["encoded"], a["noise"], a["mask"]) if inpainting else None,
                                           step_noise=a.get("tcd") if spec is None else a.get("sampler_z"), sampler=sched,
                                           regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale,
-                                          reference=None if ref is None else (a["ref_z"], a["ref_noise"], ref.fidelity)))
+                                          reference=None if ref is None else (a["ref_z"], a["ref_noise"], ref.fidelity), sag=sg))
             if return_latent:
                 return eng.latent
             if blend_pixels:   # pixel blend in fp32 before the uint8 cast
@@ -1137,6 +1197,9 @@ class StableDiffusionBase:
         "reference_only": ("text-to-image on one stream only",
                            ("regions", "pag", "tiled", "hires", "control_net_image", "reference_image", "inpaint_mask"),
                            ("a TCD pipeline (active_tcd=True)", "denoise_streams = 2")),
+        "sag": ("text-to-image on one stream only",
+                ("regions", "tiled", "hires", "pag", "reference_only", "hypertile", "control_net_image", "reference_image", "inpaint_mask"),
+                ("denoise_streams = 2",)),
     }
 
     def _refuse_combinations(self, kind, given: dict, host_loop) -> None:
@@ -1359,7 +1422,9 @@ class StableDiffusionBase:
             sites = (("adain",) + tuple(sorted(opts["adain"])),) if opts.get("adain") else ()
             key = key + (("reference", tuple(sorted(opts.get("reference") or ()))) + sites,)
         # (a HyperTile job: the number of windows and the depth - there is nothing else to it)
-        return key if not opts.get("hypertile") else key + (("hypertile",) + tuple(int(v) for v in opts["hypertile"]),)
+        key = key if not opts.get("hypertile") else key + (("hypertile",) + tuple(int(v) for v in opts["hypertile"]),)
+        # (a SAG job: nothing but the fact - scale, blur sigma and threshold are per-call uploads)
+        return key if not opts.get("sag") else key + (("sag",),)
 
     def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> DenoiseEngine:
         """The resident engine of this shape, built if need be.  `opts` are DenoiseEngine's: `sampler`; `unet`: the UNet of another
@@ -1368,7 +1433,7 @@ class StableDiffusionBase:
         alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is
         built: a re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than
         the job's own engines - one for a plain job, two for a hires job."""
-        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode", "reference", "hypertile", "adain"}:
+        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode", "reference", "hypertile", "adain", "sag"}:
             raise TypeError(f"_engine: unknown option among {sorted(opts)}")
         key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, **opts)
         keep = {key} | set(job_keys or ())
@@ -1389,12 +1454,12 @@ class StableDiffusionBase:
                                 streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=opts.get("sampler"),
                                 tiled=opts.get("tiled"), regions=opts.get("regions") or 0, pag=opts.get("pag"),
                                 region_mode=opts.get("region_mode") or "latent", reference=opts.get("reference"),
-                                hypertile=opts.get("hypertile"), adain=opts.get("adain"))
+                                hypertile=opts.get("hypertile"), adain=opts.get("adain"), sag=bool(opts.get("sag")))
             self._engines[key] = eng
         return eng
 
     def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None,
-                   region_w=None, pag=None, reference=None, hypertile=None):
+                   region_w=None, pag=None, reference=None, hypertile=None, sag=None):
         """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479)."""
         if timesteps is None:
             timesteps = self.scheduler.timesteps[::-1]
@@ -1407,7 +1472,11 @@ class StableDiffusionBase:
             t_emb = get_timestep_embedding(timestep, batch_size)
             # (a reference-only job: the position of this evaluation in the descending schedule indexes its rate table)
             ref_step = None if reference is None else reference + (n_sched - 1 - _index,)
-            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag, ref_step, hypertile)
+            # (a SAG job: its description and this timestep's rates as the device reads them, fp32 columns 0 / 1 of the coefficient row)
+            sag_step = None if sag is None else (sag, float(np.float32(self.scheduler.signal_rates[timestep])),
+                                                 float(np.float32(self.scheduler.noise_rates[timestep])))
+            latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag, ref_step, hypertile,
+                                      sag_step)
             latent = self.scheduler.step(latent, timestep, latent_prev)
             if inpaint is not None:   # reference :469-475
                 init_latent, noise, latent_mask = inpaint
@@ -1420,12 +1489,33 @@ class StableDiffusionBase:
         return latent
 
     def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None, reference=None,
-                    hypertile=None):
+                    hypertile=None, sag=None):
         """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
         A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
         predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host); in mode "attention"
         `region_w` is the list of the four levels' planes and the conditional prediction is ONE predict_regional.  A PAG job passes
-        its pag.Resolved: the conditional prediction becomes c' = (1 + k) c - k p, p from predict_perturbed (pag.combine_host)."""
+        its pag.Resolved: the conditional prediction becomes c' = (1 + k) c - k p, p from predict_perturbed (pag.combine_host).
+        A SAG job passes (its sag.Resolved, alpha_t, sigma_t): predict_sag_map for the rows that yield the map, sag.degrade_host, a
+        second predict_on_batch on the degraded latent, sag.combine_host - the device step's four parts in its order."""
+        if sag is not None:
+            spec, alpha, sigma = sag
+            dm = self.diffusion_model
+            h_, w_ = latent.shape[1], latent.shape[2]
+            if g > 0.0:
+                u, A = dm.predict_sag_map([latent, t_emb, unconditional_context])
+                c = dm.predict_on_batch([latent, t_emb, context])
+                base, base_ctx = u, unconditional_context
+            else:
+                c, A = dm.predict_sag_map([latent, t_emb, context])
+                u, base, base_ctx = None, c, context
+            degraded = sag_mod.degrade_host(latent, base, alpha, sigma, A, engine.unet_levels(h_, w_)[3], sag_mod.taps(spec.blur_sigma),
+                                            spec.threshold).astype(np.float32)
+            d = dm.predict_on_batch([degraded, t_emb, base_ctx])
+            c = sag_mod.combine_host(u, c, d, sag_mod.weights(spec.scale, g, h_, w_))
+            if u is None:
+                return c
+            e = u + g * (c - u)
+            return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
         if reference is not None:
             # reference-only control: (reference.Resolved, (z_ref, n_ref), rate table, evaluation index).  x_r in the device kernel's
             # arithmetic, then one predict_reference for the u rows (mix = fidelity) and one for the c rows (mix = 0)
@@ -1466,7 +1556,7 @@ class StableDiffusionBase:
         return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
 
     def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
-                           inpaint=None, region_w=None, pag=None, reference=None, hypertile=None):
+                           inpaint=None, region_w=None, pag=None, reference=None, hypertile=None, sag=None):
         """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`."""
         batch_size = latent.shape[0]
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
@@ -1476,7 +1566,8 @@ class StableDiffusionBase:
         for iteration, i in enumerate(range(start, sched.num_steps), start=1):
             t_emb = get_timestep_embedding(float(sched.timesteps[i]), batch_size)
             e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint, region_w, pag,
-                                 None if reference is None else reference + (i,), hypertile)
+                                 None if reference is None else reference + (i,), hypertile,
+                                 None if sag is None else (sag, float(np.float32(tab[i, 0])), float(np.float32(tab[i, 1]))))
             z = step_noise[:, i] if step_noise is not None else None
             x, prev = smp.host_step(tab[i], x, e, prev, z)
             if inpaint is not None:   # the row's own alpha / sigma, as in the device kernel
