@@ -1015,6 +1015,17 @@ def emit_sag_combine(p: Plan, eps_at, w_at, B: int, n: int, cfg: bool) -> int:
     return 3
 
 
+def emit_dynamic_threshold(p: Plan, eps_in, scales, params, step_ptr, B: int, h: int, w: int, num_steps: int):
+    """The combine of a dynamic-thresholding step (minsdtf_amd/dynthresh.py) in front of the guidance / sampler step, behind the
+    regions, PAG and SAG combines: ONE msdt_dynamic_threshold launch reads the rows (u, c) that step would read from `eps_in` -
+    the scales from row *step_ptr of `scales`, the rank and the modes from `params` - and writes the combined prediction over the
+    u rows, in place.  Returns the rows the step then takes as they are, with guidance 0 and no rescale.  The step counter is read,
+    not advanced."""
+    p.rec(ops.dynamic_threshold, eps=eps_in, out=eps_in, scales=scales, params=params, step_ptr=step_ptr, batch=B, h=h, w=w,
+          num_steps=num_steps, name="dynthresh")
+    return eps_in
+
+
 def emit_controlnet_features(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w: int, temb, ctx_kv, ctx_len: int,
                              hint: Act) -> List[Act]:
     """ControlNet (control_net.py:45-90) up to its 13 taps: conv_in(latent)+hint and the encoder.  The taps' 1x1 zero

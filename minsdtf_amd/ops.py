@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
-from . import _lib, _lib_ext
+from . import _lib, _lib_dynthresh, _lib_ext
 from ._lib import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, OUT_BF16, OUT_F32, OUT_U8  # noqa: F401
 
 
@@ -334,6 +334,18 @@ def sag_degrade(*, latent, eps, coef, coef_stride, colsum, params, out, batch, h
     d.batch, d.h, d.w, d.mh, d.mw = int(batch), int(h), int(w), int(mh), int(mw)
     d.coef_stride, d.num_steps = int(coef_stride), int(num_steps)
     return Call(lib.msdx_sag_degrade, (C.byref(d),), name, keep=d, check=_lib_ext.check)
+
+
+# ---- the dynamic-thresholding library (include/minsdtf_hip_dynthresh.h, minsdtf_amd/_lib_dynthresh.py) -----------------------------
+def dynamic_threshold(*, eps, out, scales, params, batch, h, w, num_steps, step_ptr=None, name="dynamic_threshold") -> Call:
+    """msdt_dynamic_threshold: the combined prediction of a guidance step with dynamic thresholding (minsdtf_amd/dynthresh.py).
+    eps fp32 [2 * batch][h * w * 4] (the u rows, then the c rows), out fp32 [batch][h * w * 4] (eps itself, or apart from it), scales
+    fp32 [num_steps][2] (row *step_ptr: the cfg and the mimic scale), params the 32 bytes of dynthresh.params."""
+    lib = _lib_dynthresh.load()
+    a = _lib_dynthresh.MsdtDynamicThreshold()
+    a.eps, a.out, a.scales, a.step_ptr, a.params = _p(eps), _p(out), _p(scales), _p(step_ptr), _p(params)
+    a.batch, a.h, a.w, a.num_steps = int(batch), int(h), int(w), int(num_steps)
+    return Call(lib.msdt_dynamic_threshold, (C.byref(a),), name, keep=a, check=_lib_dynthresh.check)
 
 
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:

@@ -34,6 +34,7 @@ import torch
 
 from . import _lib, engine, ops
 from . import hires as hires_mod
+from . import dynthresh as dynthresh_mod
 from . import hypertile as hypertile_mod
 from . import pag as pag_mod
 from . import sag as sag_mod
@@ -77,7 +78,7 @@ class DenoiseEngine:
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
                  sampler=None, tiled=None, regions: int = 0, pag=None, region_mode: str = "latent", reference=None, hypertile=None,
-                 adain=None, sag: bool = False):
+                 adain=None, sag: bool = False, dynthresh: bool = False):
         unet._require_weights()
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
@@ -91,6 +92,13 @@ class DenoiseEngine:
                          or self.hypertile is not None or streams == 2):
             raise ValueError("sag: text-to-image on one stream only (no ControlNet, inpainting, tiled, regions, pag, reference_only, "
                              "hypertile, denoise_streams = 2)")
+        # dynthresh (dynamic thresholding, minsdtf_amd/dynthresh.py): behind the regions / PAG / SAG combines ONE msdt_dynamic_threshold
+        # launch writes the combined prediction of the rows (u, c) over the u rows, its scales read from row *step_ptr of
+        # `dt_scales`; the step kernel then takes those rows as they are (guidance 0, no rescale: engine.emit_dynamic_threshold)
+        self.dynthresh = bool(dynthresh)
+        if self.dynthresh and (not guidance > 0.0 or control_net is not None or inpaint or tcd or tiled is not None or streams == 2):
+            raise ValueError("dynamic_threshold: guided text-to-image on one stream only (guidance > 0, no ControlNet, inpainting, TCD, "
+                             "tiled, denoise_streams = 2)")
         if self.reference is not None and guidance > 0.0 and t_cond != t_uncond:
             raise ValueError("reference_only: the negative prompt must have the conditional context's token length "
                              f"({t_uncond} != {t_cond} tokens): the reference row rides in the one fused pass")
@@ -381,6 +389,12 @@ class DenoiseEngine:
             group = engine.emit_sag_combine(tail, lambda g_: _Ptr(self.eps.data_ptr() + g_ * B * n * 4),
                                             lambda i: _Ptr(self.sag_w.data_ptr() + i * h * w * 4), B, n, self.cfg)
             eps_in = _Ptr(self.eps.data_ptr() + group * B * n * 4)
+        self.dt_scales = self.dt_params = None
+        if self.dynthresh:   # (u, c) -> the combined prediction over the u rows; the step kernels then read [B][n] and combine nothing
+            self.dt_scales = torch.zeros(num_steps, 2, dtype=torch.float32, device=dev)
+            self.dt_params = torch.zeros(dynthresh_mod.PARAM_BYTES // 4, dtype=torch.int32, device=dev)
+            eps_in = engine.emit_dynamic_threshold(tail, eps_in, self.dt_scales, self.dt_params, self.step_ptr, B, h, w, num_steps)
+            guidance = guidance_rescale = 0.0
         if self.sampler is None:
             tail.rec(ops.cfg_step, eps=eps_in, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr, batch=B, n=n,
                      num_steps=num_steps, guidance=guidance, guidance_rescale=guidance_rescale, advance=2,
@@ -529,7 +543,7 @@ class DenoiseEngine:
 
     def prepare(self, contexts: Dict[str, np.ndarray], noise: np.ndarray, scheduler: Scheduler, timesteps,
                 start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None,
-                regions=None, pag_scale=None, reference=None, sag=None) -> None:
+                regions=None, pag_scale=None, reference=None, sag=None, dynamic_threshold=None) -> None:
         """Upload the per-call inputs and run the preparation plan.  Every array may be a host array or a (device) tensor.
         noise = None: the start latent is already in `self.latent` (written there by stream-ordered device work queued before
         this call: the hand-off of a hires job), nothing is uploaded for it.
@@ -545,7 +559,19 @@ class DenoiseEngine:
         reference = (z_ref (1, h, w, 4), n_ref (1, h, w, 4), fidelity) of an engine built with reference=<layers>: the two latents,
         the rate table of this schedule and start index (reference.rates) and mix = [fidelity] * B + [0] * B are per-call uploads.
         sag = the sag.Resolved (or SagSpec / dict) of an engine built with sag=True: the 9 taps and the threshold (sag.params) and the
-        planes of the combine (sag.weights, k from the scale and the engine's guidance in float64) are per-call uploads too."""
+        planes of the combine (sag.weights, k from the scale and the engine's guidance in float64) are per-call uploads too.
+        dynamic_threshold = the dynthresh.Resolved (or DynThreshSpec / dict) of an engine built with dynthresh=True: the scale table
+        of the executed steps (dynthresh.scales over num_steps - start_index steps from the engine's guidance, rounded once to fp32,
+        in rows start_index ..) and the 32 bytes of dynthresh.params are per-call uploads too."""
+        if (dynamic_threshold is None) != (self.dt_params is None):
+            raise ValueError("prepare: `dynamic_threshold` goes with an engine built with dynthresh=True, and only with one")
+        if self.dt_params is not None:
+            spec = dynthresh_mod.parse(dynamic_threshold)
+            first = int(start_index)
+            tab = dynthresh_mod.scales(spec, self.guidance, self.num_steps - first).astype(np.float32)
+            tab = np.concatenate([np.repeat(tab[:1], first, axis=0), tab], axis=0)   # (rows in front of the first step: never read)
+            self.dt_scales.copy_(torch.from_numpy(np.ascontiguousarray(tab)))
+            self.dt_params.copy_(torch.from_numpy(dynthresh_mod.params(spec, self.h * self.w)))
         if (sag is None) != (self.sag_w is None):
             raise ValueError("prepare: `sag` goes with an engine built with sag=True, and only with one")
         if self.sag_w is not None:   # taps, threshold and the combine's planes: per-call uploads, another scale needs no other engine
@@ -683,19 +709,21 @@ class StableDiffusionBase:
     # ---- public entry points (reference :84-139)
     def text_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                       embedding=None, negative_embedding=None, seed=None, control_net_image=None, guidance_rescale=0.7,
-                      callback=None, hires=None, tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, sag=None, **kw):
+                      callback=None, hires=None, tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, sag=None,
+                      dynamic_threshold=None, **kw):
         """``hires``: None, or a hires.HiresSpec / dict for the two-pass hires fix; ``tiled``: None, or a tiled.TiledSpec / dict
         for tiled diffusion on a canvas larger than the pipeline's size; ``regions``: None, or a regions.Regions / dict for
         regional prompting, `prompt` being the base prompt; ``pag``: None, or a pag.PagSpec / dict for perturbed-attention
         guidance; ``reference_only``: None, or a reference.ReferenceSpec / dict for reference-only control; ``hypertile``: None, or a
-        hypertile.HypertileSpec / dict for windowed self-attention; ``sag``: None, or a sag.SagSpec / dict for self-attention guidance
-        (see generate_image)."""
+        hypertile.HypertileSpec / dict for windowed self-attention; ``sag``: None, or a sag.SagSpec / dict for self-attention guidance;
+        ``dynamic_threshold``: None, or a dynthresh.DynThreshSpec / dict for dynamic thresholding (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
                                    negative_embedding=negative_embedding, control_net_image=control_net_image,
                                    guidance_rescale=guidance_rescale, callback=callback, hires=hires, tiled=tiled, regions=regions,
-                                   pag=pag, reference_only=reference_only, hypertile=hypertile, sag=sag, **kw)
+                                   pag=pag, reference_only=reference_only, hypertile=hypertile, sag=sag,
+                                   dynamic_threshold=dynamic_threshold, **kw)
 
     def image_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
@@ -928,7 +956,7 @@ class StableDiffusionBase:
                        diffusion_noise=None, seed=None, negative_embedding=None, control_net_image=None, inpaint_mask=None,
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
                        callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None,
-                       tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, sag=None):
+                       tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, sag=None, dynamic_threshold=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
@@ -986,9 +1014,25 @@ class StableDiffusionBase:
         graph; msd_region_combine writes c' = k u + c - k d (k = s / g) in front of the unchanged guidance / sampler step, so
         `guidance_rescale` takes its reference std from c', as with ``pag``.  Without guidance the map comes from the c rows and
         eps = (1 + s) c - s d.  Works with every sampler, on a TCD pipeline, with shard_batch and with host_loop=True; at most
-        2 * tiled.MAX_VIEW_BATCH UNet rows (3 * batch_size with guidance, 2 * batch_size without)."""
+        2 * tiled.MAX_VIEW_BATCH UNet rows (3 * batch_size with guidance, 2 * batch_size without).
+        ``dynamic_threshold`` (a dynthresh.DynThreshSpec or a dict {"mimic_scale": 7.0, "percentile": 1.0, "mimic_mode": "constant",
+        "cfg_mode": "constant", "mimic_scale_min": 0.0, "cfg_scale_min": 0.0, "sched_val": 1.0, "measure": "ad", "startpoint": "mean",
+        "phi": 1.0}; needs guidance > 0): dynamic thresholding, the "CFG scale fix" of the sd-dynamic-thresholding extension - the
+        prediction at the (high) guidance scale keeps its direction while each (sample, channel) plane of it is forced back to the
+        spread the prediction at ``mimic_scale`` has: one msdt_dynamic_threshold launch behind the regions / PAG / SAG combines
+        writes the combined prediction (an exact quantile of every plane, on the device), and the guidance / sampler step takes it
+        as it is - so `guidance_rescale` is NOT applied to such a job.  The two scales may move over the steps (``cfg_mode``,
+        ``mimic_mode``: dynthresh.MODES); a plane without spread keeps its plain prediction.  Works with every sampler, with
+        ``hires`` (both passes, each schedule over its own executed steps), ``regions``, ``pag``, ``sag``, ``hypertile``,
+        ``reference_only``, shard_batch and host_loop=True; the engine is keyed by the fact only."""
         given = dict(tiled=tiled, hires=hires, control_net_image=control_net_image, reference_image=reference_image,
                      inpaint_mask=inpaint_mask, regions=regions, pag=pag, reference_only=reference_only, hypertile=hypertile)
+        dt = dynthresh_mod.parse(dynamic_threshold)   # (ValueError for a bad description)
+        if dt is not None:
+            self._refuse_combinations("dynamic_threshold", given, host_loop)
+            if not float(unconditional_guidance_scale) > 0.0:
+                raise ValueError(f"dynamic_threshold: unconditional_guidance_scale = {unconditional_guidance_scale!r} - without guidance "
+                                 "there is nothing to threshold")
         sg = sag_mod.parse(sag)   # (ValueError for a bad description)
         if sg is not None:
             self._refuse_combinations("sag", given, host_loop)
@@ -1066,7 +1110,7 @@ class StableDiffusionBase:
         if job is not None:
             return self._generate_hires(job, spec, context, unconditional_context, noise, hires_noise, num_steps,
                                         float(unconditional_guidance_scale), float(guidance_rescale), seed, callback, return_latent,
-                                        hypertile=ht_key)
+                                        hypertile=ht_key, dynthresh=dt)
         self.scheduler.set_timesteps(num_steps)
 
         # image_to_image (reference :410-418,559-568): encode the picture, run only the last int(n*strength+0.5) steps,
@@ -1124,11 +1168,11 @@ class StableDiffusionBase:
             ip = (encoded, noise, latent_mask[0]) if inpainting else None
             if spec is not None:
                 latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
-                                                 sampler_z, ip, region_w=region_w, pag=pg, hypertile=ht_key, sag=sg,
+                                                 sampler_z, ip, region_w=region_w, pag=pg, hypertile=ht_key, sag=sg, dynthresh=dt,
                                                  reference=None if ref is None else (ref, ref_in, reference_mod.rates(sched, start_index)))
             else:
                 latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending, ip,
-                                         region_w=region_w, pag=pg, hypertile=ht_key, sag=sg,
+                                         region_w=region_w, pag=pg, hypertile=ht_key, sag=sg, dynthresh=dt,
                                          reference=None if ref is None else (ref, ref_in, reference_mod.rates(self.scheduler, start_index)))
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
@@ -1167,11 +1211,12 @@ class StableDiffusionBase:
                                           region_mode="attention" if reg is not None and reg.mode == "attention" else None,
                                           reference=None if ref is None else tuple(sorted(ref.layers)),
                                           adain=None if ref is None else ref.adain_key, hypertile=ht_key,
-                                          sag=None if sg is None else True),
+                                          sag=None if sg is None else True, dynthresh=None if dt is None else True),
                                      dict(hint_image=a.get("hint"), inpaint=(a["encoded"], a["noise"], a["mask"]) if inpainting else None,
                                           step_noise=a.get("tcd") if spec is None else a.get("sampler_z"), sampler=sched,
                                           regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale,
-                                          reference=None if ref is None else (a["ref_z"], a["ref_noise"], ref.fidelity), sag=sg))
+                                          reference=None if ref is None else (a["ref_z"], a["ref_noise"], ref.fidelity), sag=sg,
+                                          dynamic_threshold=dt))
             if return_latent:
                 return eng.latent
             if blend_pixels:   # pixel blend in fp32 before the uint8 cast
@@ -1200,6 +1245,9 @@ class StableDiffusionBase:
         "sag": ("text-to-image on one stream only",
                 ("regions", "tiled", "hires", "pag", "reference_only", "hypertile", "control_net_image", "reference_image", "inpaint_mask"),
                 ("denoise_streams = 2",)),
+        "dynamic_threshold": ("guided text-to-image on one stream only",
+                              ("tiled", "control_net_image", "reference_image", "inpaint_mask"),
+                              ("a TCD pipeline (active_tcd=True)", "denoise_streams = 2")),
     }
 
     def _refuse_combinations(self, kind, given: dict, host_loop) -> None:
@@ -1306,11 +1354,12 @@ class StableDiffusionBase:
         return cache[key]
 
     def _generate_hires(self, job, spec, context, unconditional_context, noise, hires_noise, num_steps, g, phi, seed, callback,
-                        return_latent, hypertile=None):
+                        return_latent, hypertile=None, dynthresh=None):
         """Pass 1 (the txt2img job at the pipeline's own size, no decode) -> one msd_latent_resample launch from the pass-1 engine's
         latent into the pass-2 engine's, scaled and re-noised with the pass-2 entry rates -> pass 2 at the target size -> decode.
         Both engines stay resident, so a repeated job constructs nothing and captures nothing.  hypertile = (nh, nw, depth): pass 2
-        runs the windowed engine of the target size; pass 1 stays plain."""
+        runs the windowed engine of the target size; pass 1 stays plain.  dynthresh = the dynthresh.Resolved of a job with
+        dynamic thresholding: both passes, each with the scale schedule over its own executed steps."""
         B = noise.shape[0]
         h1, w1, h2, w2 = self.img_height // 8, self.img_width // 8, job.height // 8, job.width // 8
         a2, s2, start2, run2 = hires_mod.entry(self.scheduler, spec, job.steps, job.strength)
@@ -1332,11 +1381,13 @@ class StableDiffusionBase:
             opts = [dict(sampler=sname), dict(sampler=sname, unet=self._unet_for(job.height, job.width))]
             if hypertile is not None:
                 opts[1]["hypertile"] = hypertile
+            if dynthresh is not None:
+                opts[0]["dynthresh"] = opts[1]["dynthresh"] = True
             # (both keys in front of the first build: whatever neither pass needs goes before either arena is allocated)
             keys = [self._engine_key(b, c.shape[1], u.shape[1], n, g, phi, False, **o) for n, o in zip((num_steps, job.steps), opts)]
             self.scheduler.set_timesteps(num_steps)
             eng1 = self._denoise_pass(u, c, z, num_steps, g, phi, 0, num_steps, callback, dict(opts[0], job_keys=keys),
-                                      dict(step_noise=a.get("z1"), sampler=sched1))
+                                      dict(step_noise=a.get("z1"), sampler=sched1, dynamic_threshold=dynthresh))
 
             def hand_off(eng2):
                 wx, wy = self._hires_taps(h1, w1, h2, w2, job.upscaler, eng1.latent.device)
@@ -1348,7 +1399,7 @@ class StableDiffusionBase:
 
             self.scheduler.set_timesteps(job.steps)
             eng2 = self._denoise_pass(u, c, hand_off, job.steps, g, phi, start2, run2, callback2, dict(opts[1], job_keys=keys),
-                                      dict(step_noise=a.get("z2"), sampler=sched2))
+                                      dict(step_noise=a.get("z2"), sampler=sched2, dynamic_threshold=dynthresh))
             if return_latent:
                 return eng2.latent
             return self.image_decoder.decode_to_uint8(eng2.latent)
@@ -1424,7 +1475,9 @@ class StableDiffusionBase:
         # (a HyperTile job: the number of windows and the depth - there is nothing else to it)
         key = key if not opts.get("hypertile") else key + (("hypertile",) + tuple(int(v) for v in opts["hypertile"]),)
         # (a SAG job: nothing but the fact - scale, blur sigma and threshold are per-call uploads)
-        return key if not opts.get("sag") else key + (("sag",),)
+        key = key if not opts.get("sag") else key + (("sag",),)
+        # (a job with dynamic thresholding: nothing but the fact - scales, percentile, modes and schedules are per-call uploads)
+        return key if not opts.get("dynthresh") else key + (("dynthresh",),)
 
     def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> DenoiseEngine:
         """The resident engine of this shape, built if need be.  `opts` are DenoiseEngine's: `sampler`; `unet`: the UNet of another
@@ -1433,7 +1486,8 @@ class StableDiffusionBase:
         alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is
         built: a re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than
         the job's own engines - one for a plain job, two for a hires job."""
-        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode", "reference", "hypertile", "adain", "sag"}:
+        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode", "reference", "hypertile", "adain", "sag",
+                                "dynthresh"}:
             raise TypeError(f"_engine: unknown option among {sorted(opts)}")
         key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, **opts)
         keep = {key} | set(job_keys or ())
@@ -1454,12 +1508,13 @@ class StableDiffusionBase:
                                 streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=opts.get("sampler"),
                                 tiled=opts.get("tiled"), regions=opts.get("regions") or 0, pag=opts.get("pag"),
                                 region_mode=opts.get("region_mode") or "latent", reference=opts.get("reference"),
-                                hypertile=opts.get("hypertile"), adain=opts.get("adain"), sag=bool(opts.get("sag")))
+                                hypertile=opts.get("hypertile"), adain=opts.get("adain"), sag=bool(opts.get("sag")),
+                                dynthresh=bool(opts.get("dynthresh")))
             self._engines[key] = eng
         return eng
 
     def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None,
-                   region_w=None, pag=None, reference=None, hypertile=None, sag=None):
+                   region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None):
         """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479)."""
         if timesteps is None:
             timesteps = self.scheduler.timesteps[::-1]
@@ -1467,6 +1522,8 @@ class StableDiffusionBase:
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
         iteration = 0
         n_sched = len(self.scheduler.timesteps)
+        # (a job with dynamic thresholding: the scales of the executed steps as the device reads them, fp32)
+        dt_tab = None if dynthresh is None else dynthresh_mod.scales(dynthresh, g, len(timesteps)).astype(np.float32)
         for _index, timestep in list(enumerate(timesteps))[::-1]:
             latent_prev = latent
             t_emb = get_timestep_embedding(timestep, batch_size)
@@ -1475,8 +1532,9 @@ class StableDiffusionBase:
             # (a SAG job: its description and this timestep's rates as the device reads them, fp32 columns 0 / 1 of the coefficient row)
             sag_step = None if sag is None else (sag, float(np.float32(self.scheduler.signal_rates[timestep])),
                                                  float(np.float32(self.scheduler.noise_rates[timestep])))
+            dt_step = None if dynthresh is None else (dynthresh, float(dt_tab[iteration, 0]), float(dt_tab[iteration, 1]))
             latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag, ref_step, hypertile,
-                                      sag_step)
+                                      sag_step, dt_step)
             latent = self.scheduler.step(latent, timestep, latent_prev)
             if inpaint is not None:   # reference :469-475
                 init_latent, noise, latent_mask = inpaint
@@ -1489,14 +1547,24 @@ class StableDiffusionBase:
         return latent
 
     def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None, reference=None,
-                    hypertile=None, sag=None):
+                    hypertile=None, sag=None, dynthresh=None):
         """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
         A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
         predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host); in mode "attention"
         `region_w` is the list of the four levels' planes and the conditional prediction is ONE predict_regional.  A PAG job passes
         its pag.Resolved: the conditional prediction becomes c' = (1 + k) c - k p, p from predict_perturbed (pag.combine_host).
         A SAG job passes (its sag.Resolved, alpha_t, sigma_t): predict_sag_map for the rows that yield the map, sag.degrade_host, a
-        second predict_on_batch on the degraded latent, sag.combine_host - the device step's four parts in its order."""
+        second predict_on_batch on the degraded latent, sag.combine_host - the device step's four parts in its order.
+        A job with dynamic thresholding passes (its dynthresh.Resolved, the step's fp32 cfg scale, its fp32 mimic scale): behind
+        whatever made u and c (the regions, PAG or SAG combine included) the result is dynthresh.dynthresh_host of the two, and no
+        rescale follows - the device step's order."""
+        def guided(u, c):
+            if dynthresh is not None:
+                spec_dt, g_i, m_i = dynthresh
+                return dynthresh_mod.dynthresh_host(u, c, g_i, m_i, spec_dt).astype(np.float32)
+            e = u + g * (c - u)
+            return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
+
         if sag is not None:
             spec, alpha, sigma = sag
             dm = self.diffusion_model
@@ -1514,8 +1582,7 @@ class StableDiffusionBase:
             c = sag_mod.combine_host(u, c, d, sag_mod.weights(spec.scale, g, h_, w_))
             if u is None:
                 return c
-            e = u + g * (c - u)
-            return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
+            return guided(u, c)
         if reference is not None:
             # reference-only control: (reference.Resolved, (z_ref, n_ref), rate table, evaluation index).  x_r in the device kernel's
             # arithmetic, then one predict_reference for the u rows (mix = fidelity) and one for the c rows (mix = 0)
@@ -1527,8 +1594,7 @@ class StableDiffusionBase:
                 return c
             u = self.diffusion_model.predict_reference([latent, t_emb, unconditional_context], x_r, ref.layers, ref.fidelity, ref_context=rc,
                                                         adain=ref.adain)
-            e = u + g * (c - u)
-            return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
+            return guided(u, c)
 
         def predict(ctx):
             """The UNet's prediction for one context, through the ControlNet if there is a hint; a HyperTile job's through
@@ -1552,22 +1618,23 @@ class StableDiffusionBase:
             c = pag_mod.combine_host(c, p, pag_mod.weights(pag.scale, g, latent.shape[1], latent.shape[2]))
         if u is None:
             return c
-        e = u + g * (c - u)
-        return rescale_noise_cfg(e, c, guidance_rescale=phi) if phi > 0.0 else e
+        return guided(u, c)
 
     def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
-                           inpaint=None, region_w=None, pag=None, reference=None, hypertile=None, sag=None):
+                           inpaint=None, region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None):
         """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`."""
         batch_size = latent.shape[0]
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
         tab = smp.rows(sched, start)
         x = np.asarray(latent, dtype=np.float64)
         prev = None
+        dt_tab = None if dynthresh is None else dynthresh_mod.scales(dynthresh, g, sched.num_steps - start).astype(np.float32)
         for iteration, i in enumerate(range(start, sched.num_steps), start=1):
             t_emb = get_timestep_embedding(float(sched.timesteps[i]), batch_size)
             e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint, region_w, pag,
                                  None if reference is None else reference + (i,), hypertile,
-                                 None if sag is None else (sag, float(np.float32(tab[i, 0])), float(np.float32(tab[i, 1]))))
+                                 None if sag is None else (sag, float(np.float32(tab[i, 0])), float(np.float32(tab[i, 1]))),
+                                 None if dynthresh is None else (dynthresh, float(dt_tab[i - start, 0]), float(dt_tab[i - start, 1])))
             z = step_noise[:, i] if step_noise is not None else None
             x, prev = smp.host_step(tab[i], x, e, prev, z)
             if inpaint is not None:   # the row's own alpha / sigma, as in the device kernel
