@@ -785,43 +785,24 @@ def unet_levels(h: int, w: int) -> List[Tuple[int, int]]:
     return out
 
 
-def _region_kw(region_attn, x: Act) -> dict:
-    """Emitter.attentions' regional keywords for a block at x's resolution; region_attn = (R, conditional rows, {(h_l, w_l): plane})."""
-    if not region_attn:
-        return {}
-    R, rows, planes = region_attn
-    return dict(regions=R, region_rows=rows, region_w=planes[(x.H, x.W)])
-
-
-def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1,
-                  pag_layers=frozenset(), perturbed: int = 0, region_attn=None, ref_kw=None, site=None, sag=None) -> Act:
+def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1, attn_kw=lambda block, x: {},
+                  site=lambda x, name: None) -> Act:
     """Down path + mid block shared by the UNet (diffusion_model.py:193-229) and the ControlNet.  shared > 1: `x` (conv_in's output) is
     `shared` identical copies of x.B / shared samples - the first ResBlock and the front of the first transformer block run on one.
-    pag_layers / perturbed: the attention blocks (by name) whose attn1 is the identity for the last `perturbed` rows.
-    ref_kw: block name -> Emitter.attentions' reference keywords (emit_unet's `reference`; shared is 1 then) or its window
-    keywords (emit_unet's `window`; also on the one copy of a shared first block).
-    site: (x, name of the call that produced it) -> None, emit_unet's reference AdaIN right behind a block output.
-    sag: Emitter.attentions' `colsum` for mid_block.attentions.0 (emit_unet's `sag`)."""
-    def pert(block):
-        return perturbed if block in pag_layers else 0
-
-    ref_kw = ref_kw or (lambda block: {})
-    site = site or (lambda x, name: None)
-
+    attn_kw: (block name, its input) -> what Emitter.attentions takes beyond the plain block (emit_unet's closure of that name).
+    site: (x, name of the call that produced it) -> None, emit_unet's reference AdaIN right behind a block output."""
     for lvl, ch in enumerate(wtab.UNET_CH):
         for r in range(2):
-            name = f"down_blocks.{lvl}.resnets.{r}"
+            name, blk = f"down_blocks.{lvl}.resnets.{r}", f"down_blocks.{lvl}.attentions.{r}"
             if shared > 1 and lvl == 0 and r == 0:
                 one = Act(x.buf, x.B // shared, x.H, x.W, x.C)
                 x = e.res_block(one, name, ch, temb=temb_of(name), out_copies=shared)
-                x = e.attentions(x, f"down_blocks.{lvl}.attentions.{r}", ctx_kv, ctx_len, free_input=True, shared=shared,
-                                 **_region_kw(region_attn, x), **ref_kw(f"down_blocks.{lvl}.attentions.{r}"))
+                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, shared=shared, **attn_kw(blk, x))
                 outputs.append(x)
                 continue
             x = e.res_block(x, name, ch, temb=temb_of(name))
             if lvl < 3:
-                blk = f"down_blocks.{lvl}.attentions.{r}"
-                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=pert(blk), **_region_kw(region_attn, x), **ref_kw(blk))
+                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, **attn_kw(blk, x))
                 site(x, blk)
             else:
                 site(x, name)
@@ -830,8 +811,7 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
             x = e.conv(x, f"down_blocks.{lvl}.downsamplers.0.conv", ch, ksize=3, stride=2)
             outputs.append(x)
     x = e.res_block(x, "mid_block.resnets.0", 1280, temb=temb_of("mid_block.resnets.0"))
-    x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True, perturbed=pert("mid_block.attentions.0"),
-                     **_region_kw(region_attn, x), **ref_kw("mid_block.attentions.0"), **({} if sag is None else dict(colsum=sag)))
+    x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True, **attn_kw("mid_block.attentions.0", x))
     x = e.res_block(x, "mid_block.resnets.1", 1280, temb=temb_of("mid_block.resnets.1"), free_input=True)
     site(x, "mid_block.resnets.1")
     return x
@@ -940,13 +920,21 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
             for blk in [f"down_blocks.{lvl}.attentions.{r}" for r in range(2)] + [f"up_blocks.{3 - lvl}.attentions.{r}" for r in range(3)]:
                 win_levels[blk] = tuple(window)
 
-    def ref_kw(block):
+    def attn_kw(block: str, x: Act) -> dict:
+        """What Emitter.attentions takes for `block`, whose input is x, beyond the plain block."""
+        kw = dict(perturbed=perturbed if block in pag_layers else 0)
+        if region_attn:   # the weight plane of x's level
+            R, rows, planes = region_attn
+            kw.update(regions=R, region_rows=rows, region_w=planes[(x.H, x.W)])
         if block in win_levels:
-            return dict(window=win_levels[block])
-        return dict(reference=1, mix=ref_mix) if block in ref_layers else {}
+            kw.update(window=win_levels[block])
+        elif block in ref_layers:
+            kw.update(reference=1, mix=ref_mix)
+        if sag is not None and block == "mid_block.attentions.0":
+            kw.update(colsum=sag)
+        return kw
 
-    x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared, pag_layers=pag_layers, perturbed=perturbed,
-                      region_attn=region_attn, ref_kw=ref_kw, site=site, sag=sag)
+    x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared, attn_kw=attn_kw, site=site)
     p.mark("controls")   # everything above is independent of the ControlNet (its encoder may run beside it on another stream)
     if control_taps is not None:
         e_c, feats = control_taps
@@ -967,8 +955,7 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
             x = e.res_block((x, skip), name, ch, temb=temb_of(name), free_input=True)
             if lvl < 3:
                 blk = f"up_blocks.{ui}.attentions.{r}"
-                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, perturbed=perturbed if blk in pag_layers else 0,
-                                 **_region_kw(region_attn, x), **ref_kw(blk))
+                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, **attn_kw(blk, x))
             site(x, blk if lvl < 3 else name)   # (the third call of a block is no site: the upsampler conv's output is)
         if lvl > 0:
             y = e.conv(x, f"up_blocks.{ui}.upsamplers.0.conv", ch, ksize=3, upsample=True)

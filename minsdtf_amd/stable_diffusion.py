@@ -43,6 +43,7 @@ from . import regions as regions_mod
 from . import samplers as smp
 from . import tiled as tiled_mod
 from . import weights as wtab
+from .jobopts import REFUSED, EngineOptions, job_options
 from .models import (ControlNet, DiffusionModel, HintNet, ImageDecoder, ImageEncoder, TextClipEmbedding, TextEncoder, _BoundPlan,
                      _skip_hw, default_device)
 from .scheduler import Scheduler
@@ -76,35 +77,23 @@ class DenoiseEngine:
 
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
-                 use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
-                 sampler=None, tiled=None, regions: int = 0, pag=None, region_mode: str = "latent", reference=None, hypertile=None,
-                 adain=None, sag: bool = False, dynthresh: bool = False):
+                 use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False, **options):
+        """`options`: the fields of jobopts.EngineOptions as a caller gives them; kept as `options` and each as its own attribute."""
         unet._require_weights()
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
-        self._check_options(control_net, streams, inpaint, tcd, sampler, tiled, regions, pag, region_mode, reference, hypertile, adain)
-        # sag (self-attention guidance, minsdtf_amd/sag.py): the step records the UNet TWICE - behind the pass that holds the u rows
-        # (the c rows without guidance), whose mid block also writes the attention map `sag_A` (msdx_attention_colsum), ONE
-        # msdx_sag_degrade launch builds the degraded latent and a second forward of B rows over the same context K/V writes the d
-        # rows; the tail combines (u, c, d) in front of the unchanged step kernel (engine.emit_sag_pass / emit_sag_combine)
-        self.sag = bool(sag)
-        if self.sag and (control_net is not None or inpaint or tiled is not None or self.regions or self.pag or self.reference is not None
-                         or self.hypertile is not None or streams == 2):
-            raise ValueError("sag: text-to-image on one stream only (no ControlNet, inpainting, tiled, regions, pag, reference_only, "
-                             "hypertile, denoise_streams = 2)")
-        # dynthresh (dynamic thresholding, minsdtf_amd/dynthresh.py): behind the regions / PAG / SAG combines ONE msdt_dynamic_threshold
-        # launch writes the combined prediction of the rows (u, c) over the u rows, its scales read from row *step_ptr of
-        # `dt_scales`; the step kernel then takes those rows as they are (guidance 0, no rescale: engine.emit_dynamic_threshold)
-        self.dynthresh = bool(dynthresh)
-        if self.dynthresh and (not guidance > 0.0 or control_net is not None or inpaint or tcd or tiled is not None or streams == 2):
-            raise ValueError("dynamic_threshold: guided text-to-image on one stream only (guidance > 0, no ControlNet, inpainting, TCD, "
-                             "tiled, denoise_streams = 2)")
+        self.options = EngineOptions.of(**options)
+        self.options.check(self.h, self.w, B, guidance, control_net is not None, inpaint, tcd, streams)   # (before anything is allocated)
+        # self.sampler, .tiled, .regions, .region_mode, .pag, .reference, .adain, .hypertile, .sag, .dynthresh: the fields, as they are
+        vars(self).update(vars(self.options))
+        self.region_attn = self.region_mode == "attention"   # ("latent" without regions)
         if self.reference is not None and guidance > 0.0 and t_cond != t_uncond:
             raise ValueError("reference_only: the negative prompt must have the conditional context's token length "
                              f"({t_uncond} != {t_cond} tokens): the reference row rides in the one fused pass")
         self.use_graph = use_graph
         self.guidance = float(guidance)
-        self.cfg = cfg = guidance > 0.0
+        # ---- the rows of a step, computed here once: `passes`, the number of `eps` rows, the pass whose mid block writes SAG's map
+        self.cfg = cfg = self.guidance > 0.0
         # Two ways to run the cond and uncond halves of a step (no op couples samples, so both are the
         # reference's two predict_on_batch calls, :442-460):
         #  * fused: ONE batch-2B forward;
@@ -115,18 +104,40 @@ class DenoiseEngine:
         # one kernel chain); dual stays selectable.
         self.dual = bool(cfg and streams == 2)
         fuse = cfg and (t_cond == t_uncond) and not self.dual
-        # passes: list of (rows in eps, NB, context length); fused = uncond rows then cond rows
-        # (regions in attention mode: the masks act inside every attn2 - the UNet runs the plain job's rows, only the CONTEXT rows grow)
-        RC = 1 if self.region_attn else (self.regions or (2 if self.pag else 1))   # conditional copies of the batch (a PAG job: the c rows, then the p rows)
+        # regions (R, the number of evaluated region prompts, or 0): the conditional half is R * B rows, region-major (row
+        # r * B + b) behind the unconditional rows; one msd_region_combine launch in front of the guidance / sampler step sums them
+        # per pixel with the weights of `region_w` into the first B of those rows, in place (minsdtf_amd/regions.py)
+        # region_mode "attention": the UNet keeps the plain job's rows (only the CONTEXT rows grow); every attn2 gives the
+        # conditional rows ONE msd_region_attention launch over the R region contexts with the level's weight plane (`region_w`: the
+        # four levels' planes, regions.pack_levels), and there is no combine in the tail
+        # pag (the set of attention blocks of a perturbed-attention-guidance job, or None): the conditional half is 2 * B rows, the
+        # c rows and behind them the p rows (the same context; the selected blocks' attn1 is the identity for them); one
+        # msd_region_combine launch in front of the guidance / sampler step writes c' = (1 + k) c - k p over the c rows with the two
+        # constant planes of `pag_w` (minsdtf_amd/pag.py)
+        RC = 1 if self.region_attn else (self.regions or (2 if self.pag else 1))   # conditional copies of the batch
         if not cfg:
             passes = [(0, RC * B, t_cond, "cond")]
         elif fuse:
-            passes = [(0, (1 + RC) * B, t_cond, "both")]
+            passes = [(0, (1 + RC) * B, t_cond, "both")]   # uncond rows, then cond rows
         else:
             passes = [(0, B, t_uncond, "uncond"), (B, RC * B, t_cond, "cond")]
-        if self.reference is not None:   # one more row, the reference, last in the one pass
+        # reference (the set of attention blocks of a reference-only job, or None): the one fused pass carries one more row behind
+        # the u and c rows, the reference latent noised to the step's level (msd_reference_latent at the head of the step plan);
+        # in the selected blocks the rows in front of it attend to its keys too (msd_attention_joint, `ref_mix` per row).  The step
+        # kernels still read eps as [2B][n]: the reference row's prediction is written and never read (minsdtf_amd/reference.py)
+        # adain (the set of reference AdaIN sites of such a job, reference.ADAIN_SITES, or None): behind those block outputs the rows
+        # in front of the reference row are renormalised to its channel statistics (msd_reference_adain, the same `ref_mix`); the
+        # layer set may then be empty (AdaIN without the attention part)
+        if self.reference is not None:
             (row0, nb, t, tag), = passes
             passes = [(row0, nb + 1, t, tag)]
+        # sag (self-attention guidance, minsdtf_amd/sag.py): the step records the UNet TWICE - behind the pass that holds the u rows
+        # (the c rows without guidance) in its first B rows, whose mid block also writes the attention map `sag_A`
+        # (msdx_attention_colsum), ONE msdx_sag_degrade launch builds the degraded latent and a second forward of B rows over the same
+        # context K/V writes the d rows; the tail combines (u, c, d) in front of the unchanged step kernel (engine.emit_sag_pass /
+        # emit_sag_combine).  eps row groups of B rows: (u, c, d, copy of u, c') with guidance, (c, d) without
+        self._sag_tag = passes[0][3] if self.sag else None
+        self._eps_rows = (5 if cfg else 2) * B if self.sag else passes[-1][0] + passes[-1][1]   # (else: the rows the passes write)
         self.passes = passes
         self.has_control = control_net is not None
         prep = self._build_prep(control_net, hint_net)
@@ -147,82 +158,6 @@ class DenoiseEngine:
         self._loop_graph_steps = 0
         self._warmed = False
         _lib.track_graph_owner(self)
-
-    def _check_options(self, control_net, streams, inpaint, tcd, sampler, tiled, regions, pag=None, region_mode="latent",
-                       reference=None, hypertile=None, adain=None) -> None:
-        """The option combinations an engine refuses (generate_image refuses them earlier, by argument name: _REFUSED; these guard
-        direct construction).  Sets `sampler`, `tiled`, `regions`, `pag`, `reference`, `adain` and `hypertile`."""
-        # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
-        # the 8-wide coefficient rows, the previous denoised estimate and (stochastic samplers) per-step draws on the device
-        self.sampler = smp.parse(sampler)
-        if self.sampler is not None and tcd:
-            raise ValueError("a sampler cannot be combined with the TCD sampler")
-        # tiled (a tiled.Geometry, or None): the B rows are the views of B / V canvases, sample-major (row b * V + v); the step
-        # plan ends with one msd_tile_consensus launch that averages the stepped views into `canvas` and back into `latent`
-        self.tiled = tiled
-        if tiled is not None:
-            if (tiled.th, tiled.tw) != (self.h, self.w) or self.B % tiled.views:
-                raise ValueError(f"tiled: {tiled.views} views of {tiled.th} x {tiled.tw} on an engine of batch {self.B} at {self.h} x {self.w}")
-            if control_net is not None or inpaint or tcd:
-                raise ValueError("tiled: text-to-image only (no ControlNet, inpainting or TCD)")
-        # regions (R, the number of evaluated region prompts, or 0): the conditional half is R * B rows, region-major (row
-        # r * B + b) behind the unconditional rows; one msd_region_combine launch in front of the guidance / sampler step sums them
-        # per pixel with the weights of `region_w` into the first B of those rows, in place (minsdtf_amd/regions.py)
-        # region_mode "attention": the UNet keeps the plain job's rows; every attn2 gives the conditional rows ONE msd_region_attention
-        # launch over the R region contexts with the level's weight plane (`region_w`: the four levels' planes, regions.pack_levels),
-        # and there is no combine in the tail
-        self.regions = R = int(regions or 0)
-        if region_mode not in regions_mod.MODES:
-            raise ValueError(f"regions: mode = {region_mode!r}: one of {regions_mod.MODES}")
-        self.region_mode = region_mode if R else "latent"
-        self.region_attn = bool(R) and region_mode == "attention"
-        if R:
-            if not 1 <= R <= regions_mod.MAX_REGIONS:
-                raise ValueError(f"regions: {R} region prompts (1 .. {regions_mod.MAX_REGIONS})")
-            if control_net is not None or inpaint or tcd or tiled is not None or streams == 2:
-                raise ValueError("regions: text-to-image on one stream only (no ControlNet, inpainting, TCD, tiled, denoise_streams = 2)")
-        # pag (the set of attention blocks of a perturbed-attention-guidance job, or None): the conditional half is 2 * B rows, the
-        # c rows and behind them the p rows (the same context; the selected blocks' attn1 is the identity for them); one
-        # msd_region_combine launch in front of the guidance / sampler step writes c' = (1 + k) c - k p over the c rows with the two
-        # constant planes of `pag_w` (minsdtf_amd/pag.py)
-        self.pag = frozenset(pag) if pag else None
-        if self.pag:
-            unknown = self.pag - set(engine.PAG_LAYERS)
-            if unknown:
-                raise ValueError(f"pag: unknown layer(s) {sorted(unknown)}")
-            if control_net is not None or inpaint or tiled is not None or R or streams == 2:
-                raise ValueError("pag: text-to-image on one stream only (no ControlNet, inpainting, tiled, regions, denoise_streams = 2)")
-        # reference (the set of attention blocks of a reference-only job, or None): the one fused pass carries one more row behind
-        # the u and c rows, the reference latent noised to the step's level (msd_reference_latent at the head of the step plan);
-        # in the selected blocks the rows in front of it attend to its keys too (msd_attention_joint, `ref_mix` per row).  The step
-        # kernels still read eps as [2B][n]: the reference row's prediction is written and never read (minsdtf_amd/reference.py)
-        # adain (the set of reference AdaIN sites of such a job, reference.ADAIN_SITES, or None): behind those block outputs the rows
-        # in front of the reference row are renormalised to its channel statistics (msd_reference_adain, the same `ref_mix`); the
-        # layer set may then be empty (AdaIN without the attention part)
-        self.adain = frozenset(adain) if adain else None
-        self.reference = frozenset(reference or ()) if (reference or self.adain) else None
-        if self.reference is not None:
-            unknown = self.reference - set(engine.PAG_LAYERS)
-            if unknown:
-                raise ValueError(f"reference_only: unknown layer(s) {sorted(unknown)}")
-            unknown = (self.adain or frozenset()) - {n for n, _gw in reference_mod.ADAIN_SITES}
-            if unknown:
-                raise ValueError(f"reference_only: unknown adain site(s) {sorted(unknown)}")
-            if control_net is not None or inpaint or tcd or tiled is not None or R or self.pag or streams == 2:
-                raise ValueError("reference_only: text-to-image on one stream only (no ControlNet, inpainting, TCD, tiled, regions, pag, "
-                                 "denoise_streams = 2)")
-
-        # hypertile ((nh, nw, depth) of a HyperTile job, or None): the self-attention of the attention blocks of levels 0 .. depth
-        # is taken inside nh x nw windows (msd_attention_windowed in place of msd_attention, every row of every pass); nothing else
-        # in the step changes and nothing is uploaded per call (minsdtf_amd/hypertile.py)
-        self.hypertile = None if hypertile is None else tuple(int(v) for v in hypertile)
-        if self.hypertile is not None:
-            if len(self.hypertile) != 3:
-                raise ValueError(f"hypertile: {hypertile!r} is not (nh, nw, depth)")
-            hypertile_mod.level_geometry(self.h, self.w, *self.hypertile)   # (ValueError for windows the levels cannot take)
-            if control_net is not None or inpaint or tiled is not None or R or self.pag or self.reference is not None or streams == 2:
-                raise ValueError("hypertile: text-to-image on one stream only (no ControlNet, inpainting, tiled, regions, pag, "
-                                 "reference_only, denoise_streams = 2)")
 
     def _build_prep(self, control_net, hint_net) -> dict:
         """The preparation plans: per SCHEDULE the time-embedding tables (timestep -> MLP -> every ResBlock's projection: they do
@@ -285,12 +220,9 @@ class DenoiseEngine:
         unet, B, h, w, R, passes = self.unet, self.B, self.h, self.w, self.regions, self.passes
         dev = unet.device
         n = h * w * 4
-        RC = 1 if self.region_attn else (R or (2 if self.pag else 1))
-        self.eps = torch.zeros(((1 + RC) * B if self.cfg else RC * B) + (1 if self.reference is not None else 0), n, dtype=torch.float32, device=dev)
+        self.eps = torch.zeros(self._eps_rows, n, dtype=torch.float32, device=dev)
         self.sag_A = self.sag_latent = self.sag_params = self.sag_w = None
         if self.sag:
-            # eps row groups of B rows: (u, c, d, copy of u, c') with guidance, (c, d) without (engine.emit_sag_combine)
-            self.eps = torch.zeros((5 if self.cfg else 2) * B, n, dtype=torch.float32, device=dev)
             mh, mw = engine.unet_levels(h, w)[3]
             self.sag_A = torch.zeros(B, mh * mw, dtype=torch.float32, device=dev)
             self.sag_latent = torch.zeros(B, h, w, 4, dtype=torch.float32, device=dev)
@@ -334,28 +266,39 @@ class DenoiseEngine:
                 feats = engine.emit_controlnet_features(s_cf, self.latent, B, nb, h, w, prep["table_c"], prep["kv_c"][tag], t, hint_nb)
                 taps = (s_c, feats)
             eps_view = _Ptr(self.eps.data_ptr() + row0 * n * 4)
-            # (a PAG job: the p rows are the last B rows of the pass that holds the conditional rows)
-            extra = dict(pag_layers=self.pag, perturbed=B) if self.pag and tag != "uncond" else {}
-            if self.region_attn and tag != "uncond":   # the conditional rows are the last B rows of their pass
-                extra = dict(region_attn=(R, B, region_planes))
             if self.reference is not None:   # x_r of this step first, then the forward whose last row reads it
                 step.rec(ops.reference_latent, z=self.ref_z, noise=self.ref_noise, coef=self.ref_coef, step_ptr=self.step_ptr,
                          out=self.ref_latent, n=n, num_steps=self.num_steps)
-                extra = dict(reference=(self.reference, self.ref_latent, self.ref_mix), adain=self.adain)
-            if self.hypertile is not None:
-                extra = dict(window=self.hypertile[:2], window_depth=self.hypertile[2])
-            sag_here = self.sag and tag == ("cond" if not self.cfg else "both" if len(passes) == 1 else "uncond")
-            if sag_here:   # this pass holds the u rows (the c rows without guidance) in its first B rows
-                mh, mw = engine.unet_levels(h, w)[3]
+            sag_here, sag_ws = tag == self._sag_tag, None
+            if sag_here:
                 sag_ws = step.alloc(ops.colsum_workspace_floats(B, 8, mh * mw) * 4)
-                extra = dict(sag=(self.sag_A, sag_ws, 0, B))
-            engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps, **extra)
+            engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps,
+                             **self._unet_keywords(tag, region_planes, sag_ws))
             if sag_here:
                 step.free(sag_ws)
                 d_rows = _Ptr(self.eps.data_ptr() + (2 if self.cfg else 1) * B * n * 4)
                 engine.emit_sag_pass(s_u, self.latent, eps_view, self.coef, int(self.coef.shape[1]), self.num_steps, self.sag_A,
                                      self.sag_params, self.sag_latent, B, h, w, prep["table_u"], prep["kv_u"][tag], t, d_rows)
         return step
+
+    def _unet_keywords(self, tag: str, region_planes, sag_ws) -> dict:
+        """emit_unet's keywords for the pass `tag` beyond the plain forward's, every option adding its own.  The refusals (jobopts.REFUSED)
+        are what makes the contributions disjoint: pag, regions in attention mode, reference, hypertile and sag exclude each other."""
+        kw, B = {}, self.B
+        if self.pag and tag != "uncond":   # the p rows are the last B rows of the pass that holds the conditional rows
+            kw.update(pag_layers=self.pag, perturbed=B)
+        if self.region_attn and tag != "uncond":   # the conditional rows are the last B rows of their pass
+            kw.update(region_attn=(self.regions, B, region_planes))
+        if self.reference is not None:
+            kw.update(reference=(self.reference, self.ref_latent, self.ref_mix), adain=self.adain)
+        # hypertile ((nh, nw, depth) of a HyperTile job, or None): the self-attention of the attention blocks of levels 0 .. depth
+        # is taken inside nh x nw windows (msd_attention_windowed in place of msd_attention, every row of every pass); nothing else
+        # in the step changes and nothing is uploaded per call (minsdtf_amd/hypertile.py)
+        if self.hypertile is not None:
+            kw.update(window=self.hypertile[:2], window_depth=self.hypertile[2])
+        if sag_ws is not None:   # this pass holds the u rows (the c rows without guidance) in its first B rows
+            kw.update(sag=(self.sag_A, sag_ws, 0, B))
+        return kw
 
     def _build_tail(self, step, guidance, guidance_rescale, inpaint, tcd) -> "engine.Plan":
         """What follows the UNet in a step: the region combine, the guidance / sampler step, the tile consensus - recorded behind
@@ -389,12 +332,17 @@ class DenoiseEngine:
             group = engine.emit_sag_combine(tail, lambda g_: _Ptr(self.eps.data_ptr() + g_ * B * n * 4),
                                             lambda i: _Ptr(self.sag_w.data_ptr() + i * h * w * 4), B, n, self.cfg)
             eps_in = _Ptr(self.eps.data_ptr() + group * B * n * 4)
+        # dynthresh (dynamic thresholding, minsdtf_amd/dynthresh.py): behind the regions / PAG / SAG combines ONE msdt_dynamic_threshold
+        # launch writes the combined prediction of the rows (u, c) over the u rows, its scales read from row *step_ptr of
+        # `dt_scales`; the step kernel then takes those rows as they are (guidance 0, no rescale: engine.emit_dynamic_threshold)
         self.dt_scales = self.dt_params = None
         if self.dynthresh:   # (u, c) -> the combined prediction over the u rows; the step kernels then read [B][n] and combine nothing
             self.dt_scales = torch.zeros(num_steps, 2, dtype=torch.float32, device=dev)
             self.dt_params = torch.zeros(dynthresh_mod.PARAM_BYTES // 4, dtype=torch.int32, device=dev)
             eps_in = engine.emit_dynamic_threshold(tail, eps_in, self.dt_scales, self.dt_params, self.step_ptr, B, h, w, num_steps)
             guidance = guidance_rescale = 0.0
+        # sampler (a name of minsdtf_amd/samplers.py, or None): a multistep / ancestral sampler through msd_sampler_step, with
+        # the 8-wide coefficient rows, the previous denoised estimate and (stochastic samplers) per-step draws on the device
         if self.sampler is None:
             tail.rec(ops.cfg_step, eps=eps_in, latent=self.latent, coef=self.coef, step_ptr=self.step_ptr, batch=B, n=n,
                      num_steps=num_steps, guidance=guidance, guidance_rescale=guidance_rescale, advance=2,
@@ -407,6 +355,8 @@ class DenoiseEngine:
                      denoised_prev=self.denoised_prev, batch=B, n=n, num_steps=num_steps, guidance=guidance,
                      guidance_rescale=guidance_rescale, advance=2, inpaint_init=ip.get("init"), inpaint_noise=ip.get("noise"),
                      inpaint_mask=ip.get("mask"), step_noise=self.step_noise)
+        # tiled (a tiled.Geometry, or None): the B rows are the views of B / V canvases, sample-major (row b * V + v); the step
+        # plan ends with one msd_tile_consensus launch that averages the stepped views into `canvas` and back into `latent`
         self.canvas = self._tile_args = None
         if tiled is not None:
             images = B // tiled.views
@@ -451,9 +401,9 @@ class DenoiseEngine:
                 context = torch.cat([_f32_tensor(c).to(dev) for c in context], dim=0)
             else:
                 context = np.concatenate([np.asarray(c, dtype=np.float32) for c in context], axis=0)
-        if getattr(self, "pag", None):   # the p rows read the conditional context again
+        if self.pag:   # the p rows read the conditional context again
             context = torch.cat([context, context], dim=0) if isinstance(context, torch.Tensor) else np.concatenate([context, context], axis=0)
-        if getattr(self, "reference", None) is not None:   # the reference row reads the conditional context of sample 0
+        if self.reference is not None:   # the reference row reads the conditional context of sample 0
             context = torch.cat([context, context[:1]], dim=0) if isinstance(context, torch.Tensor) else np.concatenate([context, context[:1]], axis=0)
         if not self.cfg:
             return {"cond": context}
@@ -1036,40 +986,28 @@ class StableDiffusionBase:
         sg = sag_mod.parse(sag)   # (ValueError for a bad description)
         if sg is not None:
             self._refuse_combinations("sag", given, host_loop)
-            rows = (3 if float(unconditional_guidance_scale) > 0.0 else 2) * int(batch_size)
-            if rows > 2 * tiled_mod.MAX_VIEW_BATCH:
-                raise ValueError(f"sag: {batch_size} image(s) are {rows} UNet rows per step, more than 2 * tiled.MAX_VIEW_BATCH = "
-                                 f"{2 * tiled_mod.MAX_VIEW_BATCH}: use a smaller batch")
+            self._cap_rows("sag", batch_size, (3 if float(unconditional_guidance_scale) > 0.0 else 2) * int(batch_size))
         ht = hypertile_mod.parse(hypertile)   # (ValueError for a bad description)
         if ht is not None:
             self._refuse_combinations("hypertile", given, host_loop)
         ref = reference_mod.parse(reference_only)   # (ValueError for a bad description)
         if ref is not None:
             self._refuse_combinations("reference_only", given, host_loop)
-            rows = 2 * int(batch_size) + 1
-            if rows > 2 * tiled_mod.MAX_VIEW_BATCH:
-                raise ValueError(f"reference_only: {batch_size} image(s) are {rows} UNet rows per step, more than 2 * tiled.MAX_VIEW_BATCH "
-                                 f"= {2 * tiled_mod.MAX_VIEW_BATCH}: use a smaller batch")
+            self._cap_rows("reference_only", batch_size, 2 * int(batch_size) + 1)
         pg = pag_mod.parse(pag)   # (ValueError for a bad description)
         if pg is not None and pg.scale == 0.0:
             pg = None   # (c' = c: the plain job, on the plain engine)
         if pg is not None:
             self._refuse_combinations("pag", given, host_loop)
-            rows = (3 if float(unconditional_guidance_scale) > 0.0 else 2) * int(batch_size)
-            if rows > 2 * tiled_mod.MAX_VIEW_BATCH:
-                raise ValueError(f"pag: {batch_size} image(s) are {rows} UNet rows per step, more than 2 * tiled.MAX_VIEW_BATCH = "
-                                 f"{2 * tiled_mod.MAX_VIEW_BATCH}: use a smaller batch")
+            self._cap_rows("pag", batch_size, (3 if float(unconditional_guidance_scale) > 0.0 else 2) * int(batch_size))
         reg = regions_mod.parse(regions, self.img_height, self.img_width)   # (ValueError for a bad description)
         if reg is not None:
             self._refuse_combinations("regions", given, host_loop)
             if reg.mode == "attention":   # the UNet runs the plain job's rows whatever the number of regions
-                if 2 * int(batch_size) > 2 * tiled_mod.MAX_VIEW_BATCH:
-                    raise ValueError(f'regions: {batch_size} image(s) in mode="attention" are {2 * int(batch_size)} UNet rows per step, more '
-                                     f"than 2 * tiled.MAX_VIEW_BATCH = {2 * tiled_mod.MAX_VIEW_BATCH}: use a smaller batch")
-            elif (1 + reg.count) * int(batch_size) > 2 * tiled_mod.MAX_VIEW_BATCH:
-                raise ValueError(f"regions: {batch_size} image(s) of 1 + {reg.count} prompts are {(1 + reg.count) * int(batch_size)} UNet "
-                                 f"rows per step, more than 2 * tiled.MAX_VIEW_BATCH = {2 * tiled_mod.MAX_VIEW_BATCH}: use fewer regions "
-                                 "or a smaller batch")
+                self._cap_rows("regions", batch_size, 2 * int(batch_size), ' in mode="attention"')
+            else:
+                self._cap_rows("regions", batch_size, (1 + reg.count) * int(batch_size), f" of 1 + {reg.count} prompts",
+                               "use fewer regions or a smaller batch")
         geo = tiled_mod.parse(tiled, self.img_height, self.img_width)   # (ValueError for a bad description)
         if geo is not None:
             self._refuse_combinations("tiled", given, host_loop)
@@ -1095,6 +1033,9 @@ class StableDiffusionBase:
         spec = smp.parse(sampler)   # (ValueError for an unknown name)
         if spec is not None and self.active_tcd:
             raise ValueError(f"sampler={sampler!r} on a TCD pipeline (active_tcd=True): the TCD sampler is the only one it runs")
+        # what the job's engines are built with, built here once.  A tiled or hires job takes all of it too: every option but the sampler,
+        # dynthresh and (hires, second pass only) the windows is refused with those two - its REFUSED row names `tiled` / `hires`
+        engine_opts = job_options(sampler=spec, regions=reg, pag=pg, reference=ref, hypertile=ht_key, sag=sg, dynthresh=dt)
         B = batch_size
         context = self._batch_of(encoded_text, B, 2)
         unconditional_context = self._negative_context(negative_prompt, negative_embedding, B)
@@ -1105,12 +1046,12 @@ class StableDiffusionBase:
                 raise ValueError(f"tiled: diffusion_noise has shape {tuple(noise.shape)}, the {geo.height}x{geo.width} canvas latent of "
                                  f"batch {B} is {(B, geo.H, geo.W, 4)}")
             return self._generate_tiled(geo, spec, context, unconditional_context, noise, num_steps, float(unconditional_guidance_scale),
-                                        float(guidance_rescale), seed, callback, return_latent)
+                                        float(guidance_rescale), seed, callback, return_latent, engine_opts)
         noise = self._get_initial_diffusion_noise(B, seed) if diffusion_noise is None else self._batch_of(diffusion_noise, B, 3)
         if job is not None:
             return self._generate_hires(job, spec, context, unconditional_context, noise, hires_noise, num_steps,
                                         float(unconditional_guidance_scale), float(guidance_rescale), seed, callback, return_latent,
-                                        hypertile=ht_key, dynthresh=dt)
+                                        ({k: v for k, v in engine_opts.items() if k != "hypertile"}, engine_opts), dt)
         self.scheduler.set_timesteps(num_steps)
 
         # image_to_image (reference :410-418,559-568): encode the picture, run only the last int(n*strength+0.5) steps,
@@ -1197,7 +1138,6 @@ class StableDiffusionBase:
             shared["region_ctx"], shared["region_w"] = region_ctx, region_w
         if ref is not None:   # the reference latent and its draw: whole on every rank, every rank runs its own reference row
             shared["ref_z"], shared["ref_noise"] = ref_in
-        sname = None if spec is None else spec.name
 
         def local(c, u, z, a):
             """This rank's slice of the batch: one denoise pass -> decode; returns a device tensor."""
@@ -1206,12 +1146,7 @@ class StableDiffusionBase:
                 rc = a["region_ctx"]
                 rep = (lambda x: x.unsqueeze(0).expand(b, -1, -1)) if isinstance(rc, torch.Tensor) else (lambda x: np.repeat(x[None], b, axis=0))
                 c = ([c] if reg.base_weight > 0.0 else []) + [rep(rc[i]) for i in range(rc.shape[0])]
-            eng = self._denoise_pass(u, c, z, num_steps, g, phi, start_index, run_steps, callback,
-                                     dict(sampler=sname, regions=None if reg is None else len(c), pag=None if pg is None else pg.key,
-                                          region_mode="attention" if reg is not None and reg.mode == "attention" else None,
-                                          reference=None if ref is None else tuple(sorted(ref.layers)),
-                                          adain=None if ref is None else ref.adain_key, hypertile=ht_key,
-                                          sag=None if sg is None else True, dynthresh=None if dt is None else True),
+            eng = self._denoise_pass(u, c, z, num_steps, g, phi, start_index, run_steps, callback, engine_opts,
                                      dict(hint_image=a.get("hint"), inpaint=(a["encoded"], a["noise"], a["mask"]) if inpainting else None,
                                           step_noise=a.get("tcd") if spec is None else a.get("sampler_z"), sampler=sched,
                                           regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale,
@@ -1226,29 +1161,7 @@ class StableDiffusionBase:
 
         return self._run_sharded(local, context, unconditional_context, start_latent, per_sample, shared)
 
-    # job kind -> (what it is, the arguments and then the states it cannot be combined with, in the order the error names them)
-    _REFUSED = {
-        "regions": ("text-to-image on one stream only", ("tiled", "hires", "control_net_image", "reference_image", "inpaint_mask"),
-                    ("a TCD pipeline (active_tcd=True)", "denoise_streams = 2")),
-        "tiled": ("text-to-image on the device loop only", ("reference_image", "inpaint_mask", "control_net_image", "hires"),
-                  ("host_loop=True", "a TCD pipeline (active_tcd=True)")),
-        "hires": ("text-to-image on the device loop only", ("reference_image", "inpaint_mask", "control_net_image"),
-                  ("host_loop=True", "a TCD pipeline (active_tcd=True)")),
-        "pag": ("text-to-image on one stream only", ("regions", "tiled", "hires", "control_net_image", "reference_image", "inpaint_mask"),
-                ("denoise_streams = 2",)),
-        "hypertile": ("text-to-image on one stream only",
-                      ("tiled", "regions", "pag", "reference_only", "control_net_image", "inpaint_mask", "reference_image"),
-                      ("denoise_streams = 2",)),
-        "reference_only": ("text-to-image on one stream only",
-                           ("regions", "pag", "tiled", "hires", "control_net_image", "reference_image", "inpaint_mask"),
-                           ("a TCD pipeline (active_tcd=True)", "denoise_streams = 2")),
-        "sag": ("text-to-image on one stream only",
-                ("regions", "tiled", "hires", "pag", "reference_only", "hypertile", "control_net_image", "reference_image", "inpaint_mask"),
-                ("denoise_streams = 2",)),
-        "dynamic_threshold": ("guided text-to-image on one stream only",
-                              ("tiled", "control_net_image", "reference_image", "inpaint_mask"),
-                              ("a TCD pipeline (active_tcd=True)", "denoise_streams = 2")),
-    }
+    _REFUSED = REFUSED   # (jobopts.py: the one table generate_image and the engines refuse from)
 
     def _refuse_combinations(self, kind, given: dict, host_loop) -> None:
         """ValueError naming every argument of `given` that is set and every state that holds which job `kind` cannot take."""
@@ -1258,6 +1171,13 @@ class StableDiffusionBase:
         refused = [n for n in arguments if given[n] is not None] + [s for s in states if holds[s]]
         if refused:
             raise ValueError(f"{kind} is {what}: it cannot be combined with {', '.join(refused)}")
+
+    @staticmethod
+    def _cap_rows(kind, batch_size, rows, how="", advice="use a smaller batch") -> None:
+        """ValueError when a job of `kind` would run more UNet rows per step than 2 * tiled.MAX_VIEW_BATCH."""
+        if rows > 2 * tiled_mod.MAX_VIEW_BATCH:
+            raise ValueError(f"{kind}: {batch_size} image(s){how} are {rows} UNet rows per step, more than 2 * tiled.MAX_VIEW_BATCH = "
+                             f"{2 * tiled_mod.MAX_VIEW_BATCH}: {advice}")
 
     def _reference_inputs(self, ref, h, w, seed):
         """(z_ref, n_ref) of a reference-only job, each (1, h, w, 4) float32: the given latent, or the picture through the VAE
@@ -1305,9 +1225,9 @@ class StableDiffusionBase:
     def _denoise_pass(self, u, c, start, steps, g, phi, first, count, callback, engine_opts: dict, extras: dict) -> DenoiseEngine:
         """Engine for these rows -> contexts -> prepare -> `count` steps from step `first` of the `steps`-step schedule; returns the
         engine.  `start`: the start latent, or a function of the engine whose device work leaves it in `engine.latent`.
-        `engine_opts` (_engine's keywords) and `extras` (prepare's) are passed on without their None entries, so a job hands
-        _engine and prepare only what is its own."""
-        engine_opts, extras = ({k: v for k, v in d.items() if v is not None} for d in (engine_opts, extras))
+        `engine_opts`: _engine's keywords.  `extras` (prepare's) are passed on without their None entries, so a job hands prepare
+        only what is its own."""
+        extras = {k: v for k, v in extras.items() if v is not None}
         tc = c[0].shape[1] if isinstance(c, list) else c.shape[1]
         eng = self._engine(int(u.shape[0]), tc, u.shape[1], steps, g, phi, "hint_image" in extras, "inpaint" in extras, **engine_opts)
         if callable(start):
@@ -1354,12 +1274,12 @@ class StableDiffusionBase:
         return cache[key]
 
     def _generate_hires(self, job, spec, context, unconditional_context, noise, hires_noise, num_steps, g, phi, seed, callback,
-                        return_latent, hypertile=None, dynthresh=None):
+                        return_latent, pass_opts, dynthresh=None):
         """Pass 1 (the txt2img job at the pipeline's own size, no decode) -> one msd_latent_resample launch from the pass-1 engine's
         latent into the pass-2 engine's, scaled and re-noised with the pass-2 entry rates -> pass 2 at the target size -> decode.
-        Both engines stay resident, so a repeated job constructs nothing and captures nothing.  hypertile = (nh, nw, depth): pass 2
-        runs the windowed engine of the target size; pass 1 stays plain.  dynthresh = the dynthresh.Resolved of a job with
-        dynamic thresholding: both passes, each with the scale schedule over its own executed steps."""
+        Both engines stay resident, so a repeated job constructs nothing and captures nothing.  pass_opts = _engine's option keywords
+        for the two passes (pass 2 gets the UNet of the target size here).  dynthresh = the dynthresh.Resolved of a job with dynamic
+        thresholding: both passes, each with the scale schedule over its own executed steps."""
         B = noise.shape[0]
         h1, w1, h2, w2 = self.img_height // 8, self.img_width // 8, job.height // 8, job.width // 8
         a2, s2, start2, run2 = hires_mod.entry(self.scheduler, spec, job.steps, job.strength)
@@ -1372,17 +1292,12 @@ class StableDiffusionBase:
         sched2, z2 = self._sampler_inputs(spec, B, job.steps, h2, w2, seed, stream_key=3)
         if z1 is not None:
             per_sample["z1"], per_sample["z2"] = z1.reshape(B, num_steps, -1), z2.reshape(B, job.steps, -1)
-        sname = None if spec is None else spec.name
         callback2 = None if callback is None else (lambda i: callback(num_steps + i))
 
         def local(c, u, z, a):
             """This rank's slice: pass 1 -> hand-off into the pass-2 engine -> pass 2 -> decode; returns a device tensor."""
             b = int(z.shape[0])
-            opts = [dict(sampler=sname), dict(sampler=sname, unet=self._unet_for(job.height, job.width))]
-            if hypertile is not None:
-                opts[1]["hypertile"] = hypertile
-            if dynthresh is not None:
-                opts[0]["dynthresh"] = opts[1]["dynthresh"] = True
+            opts = [pass_opts[0], dict(pass_opts[1], unet=self._unet_for(job.height, job.width))]
             # (both keys in front of the first build: whatever neither pass needs goes before either arena is allocated)
             keys = [self._engine_key(b, c.shape[1], u.shape[1], n, g, phi, False, **o) for n, o in zip((num_steps, job.steps), opts)]
             self.scheduler.set_timesteps(num_steps)
@@ -1407,7 +1322,8 @@ class StableDiffusionBase:
         return self._run_sharded(local, context, unconditional_context, noise, per_sample, {})
 
     # ---- tiled diffusion: the views of a canvas as batch rows of one engine (minsdtf_amd/tiled.py)
-    def _generate_tiled(self, geo, spec, context, unconditional_context, noise, num_steps, g, phi, seed, callback, return_latent):
+    def _generate_tiled(self, geo, spec, context, unconditional_context, noise, num_steps, g, phi, seed, callback, return_latent,
+                        engine_opts):
         """One engine of batch images * V keyed by the geometry: the canvas noise is uploaded and gathered into the views by one
         launch, the loop (UNet on every view, sampler step per view, consensus) is the engine's replayed graph, the canvas latent
         is decoded.  The engine stays resident, so a repeated job constructs nothing and captures nothing."""
@@ -1427,7 +1343,7 @@ class StableDiffusionBase:
             if zs is not None:
                 zs = tiled_mod.slice_views(zs.reshape(int(z.shape[0]), num_steps, geo.H, geo.W, 4), geo)
             eng = self._denoise_pass(per_view(u), per_view(c), lambda eng: eng.load_canvas(z), num_steps, g, phi, 0, num_steps, callback,
-                                     dict(sampler=None if spec is None else spec.name, tiled=geo), dict(step_noise=zs, sampler=sched))
+                                     dict(engine_opts, tiled=geo), dict(step_noise=zs, sampler=sched))
             if return_latent:
                 return eng.canvas
             return self.image_decoder.decode_to_uint8(eng.canvas)
@@ -1454,41 +1370,21 @@ class StableDiffusionBase:
         return np.stack(encoded, axis=0), reg.weights()
 
     def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> tuple:
-        """`opts`: sampler / unet / tiled / regions / pag as _engine takes them; one at its default (None) adds nothing to the key."""
+        """`opts` as _engine takes them: one at its default (None) adds nothing to the key, an unknown name is a TypeError."""
         # the engine's plans (and captured hipGraphs) hold raw addresses of the packed weights: a set_weights() /
         # load_synthetic() / LoRA reload on any of the models it was built from must retire it
         base = self.diffusion_model
-        unet, tiled, regions = opts.get("unet") or base, opts.get("tiled"), opts.get("regions")
+        unet = opts.pop("unet", None) or base
         wver = (unet.weights_version,) + ((self.control_net.weights_version, self.hint_net.weights_version) if control else ())
         key = (B, tc, tu, steps, g, phi, control, self.denoise_streams, inpaint, self.active_tcd, wver, engine.GN_EPOCH, opts.get("sampler"))
         key = key if unet is base else key + ((unet.h, unet.w),)   # (a hires job's second size: a view of the same weights)
-        key = key if tiled is None else key + (tiled.key,)         # (a tiled job: B counts views)
-        # (a regional job: the NUMBER of evaluated region prompts only - masks, weights and prompts are per-call uploads)
-        key = key if not regions else key + (("regions", int(regions)) + (("attention",) if opts.get("region_mode") == "attention" else ()),)
-        # (a PAG job: the selected blocks only - the scale is a per-call upload)
-        key = key if not opts.get("pag") else key + (("pag", tuple(sorted(opts["pag"]))),)
-        # (a reference-only job: the selected blocks only - the image, the draw and the fidelity are per-call uploads)
-        # (with reference AdaIN the site set too, behind the blocks - which may then be none - and only when it is present)
-        if opts.get("reference") or opts.get("adain"):
-            sites = (("adain",) + tuple(sorted(opts["adain"])),) if opts.get("adain") else ()
-            key = key + (("reference", tuple(sorted(opts.get("reference") or ()))) + sites,)
-        # (a HyperTile job: the number of windows and the depth - there is nothing else to it)
-        key = key if not opts.get("hypertile") else key + (("hypertile",) + tuple(int(v) for v in opts["hypertile"]),)
-        # (a SAG job: nothing but the fact - scale, blur sigma and threshold are per-call uploads)
-        key = key if not opts.get("sag") else key + (("sag",),)
-        # (a job with dynamic thresholding: nothing but the fact - scales, percentile, modes and schedules are per-call uploads)
-        return key if not opts.get("dynthresh") else key + (("dynthresh",),)
+        return key + EngineOptions.of(**opts).key()
 
     def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> DenoiseEngine:
-        """The resident engine of this shape, built if need be.  `opts` are DenoiseEngine's: `sampler`; `unet`: the UNet of another
-        size (a hires job's second pass); `tiled`: the geometry of a tiled job (B counts its views); `regions`: the number of
-        evaluated region prompts of a regional job; `pag`: the attention blocks of a PAG job.  `job_keys`: the keys of every engine the current job uses (default: this one
-        alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is
-        built: a re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than
-        the job's own engines - one for a plain job, two for a hires job."""
-        if not set(opts) <= {"sampler", "unet", "tiled", "regions", "pag", "region_mode", "reference", "hypertile", "adain", "sag",
-                                "dynthresh"}:
-            raise TypeError(f"_engine: unknown option among {sorted(opts)}")
+        """The resident engine of this shape, built if need be.  `opts`: `unet` (the UNet of another size: a hires job's second pass) and
+        DenoiseEngine's options (jobopts.EngineOptions).  `job_keys`: the keys of every engine the current job uses (default: this one
+        alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is built: a
+        re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than the job's own engines."""
         key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, **opts)
         keep = {key} | set(job_keys or ())
         if any(k not in keep for k in self._engines):
@@ -1502,14 +1398,11 @@ class StableDiffusionBase:
             gc.collect()
         eng = self._engines.get(key)
         if eng is None:
-            eng = DenoiseEngine(opts.get("unet") or self.diffusion_model, B, tc, tu, steps, g, phi,
+            eng = DenoiseEngine(opts.pop("unet", None) or self.diffusion_model, B, tc, tu, steps, g, phi,
                                 control_net=self.control_net if control else None,
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
-                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, sampler=opts.get("sampler"),
-                                tiled=opts.get("tiled"), regions=opts.get("regions") or 0, pag=opts.get("pag"),
-                                region_mode=opts.get("region_mode") or "latent", reference=opts.get("reference"),
-                                hypertile=opts.get("hypertile"), adain=opts.get("adain"), sag=bool(opts.get("sag")),
-                                dynthresh=bool(opts.get("dynthresh")))
+                                # (`regions` always as an int: what the residency tests read off this call for a plain job)
+                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, **dict(opts, regions=opts.get("regions") or 0))
             self._engines[key] = eng
         return eng
 

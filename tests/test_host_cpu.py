@@ -396,7 +396,7 @@ def test_engine_contexts_accept_mixed_host_and_device_inputs():
 
     from minsdtf_amd.stable_diffusion import DenoiseEngine
 
-    eng = SimpleNamespace(cfg=True, passes=[None])
+    eng = SimpleNamespace(cfg=True, passes=[None], pag=None, reference=None)
     host = np.zeros((1, 77, 768), dtype=np.float32)
     on_dev = torch.empty(1, 77, 768, device="meta")
     for u, c in ((host, on_dev), (on_dev, host), (on_dev, on_dev)):

@@ -178,17 +178,12 @@ def test_refusals_come_before_any_device_work():
 
 
 def test_engine_refuses_direct_construction():
-    from minsdtf_amd.stable_diffusion import DenoiseEngine
+    from minsdtf_amd.jobopts import EngineOptions
 
-    class Unet:
-        h = w = 16
-
-    def check(**kw):
-        e = DenoiseEngine.__new__(DenoiseEngine)
-        e.h, e.w = 16, 16
-        args = dict(control_net=None, streams=None, inpaint=False, tcd=False, sampler=None, tiled=None, regions=0)
-        args.update(kw)
-        e._check_options(**args)
+    def check(control_net=None, streams=None, inpaint=False, tcd=False, **kw):
+        """The options as an engine of batch 2 at 16 x 16 keeps them, behind the check it makes before it allocates anything."""
+        e = EngineOptions.of(**kw)
+        e.check(16, 16, 2, 7.5, control_net is not None, inpaint, tcd, streams)
         return e
 
     assert check(hypertile=(2, 2, 0)).hypertile == (2, 2, 0) and check().hypertile is None
