@@ -4,7 +4,9 @@ msd_conv_gemm launch the emitters record for a network at a latent size, with wh
 The walk hooks engine.Plan.rec and leaves tuning.lookup in place, so a record holds the configuration the engine really
 chose (table row, nearest measured batch, or tuning.shape_config), the epilogue it asked for and the weight layout it would
 read.  Nothing is launched; ops.conv_gemm_ln_slots loads the built library (LayerNorm-fold producers ask it for their slot
-count).  Not a conftest: plain helpers, imported by name."""
+count).  The same walk keeps the other launch families of a default job - msd_group_norm, msd_attention, msd_cross_attention_q,
+msd_conv_direct, msd_layer_norm - for tests/test_layer_launches_gpu.py (walk_families, family_cases).  Not a conftest: plain
+helpers, imported by name."""
 import collections
 
 # what one recorded ops.conv_gemm call keeps.  Presence flags are booleans; split = the q|k|v^T / k|v^T epilogue (ns0, ns1 its
@@ -70,18 +72,78 @@ def _launch(kw):
                   ns0=split[0] if split else 0, ns1=split[1] if split else 0)
 
 
-def walk(what, nb, h, w):
-    """Every ops.conv_gemm call the emitters record for `what` ("unet" | "controlnet" | "vae" | "vae_enc") at fused batch nb and
-    latent size h x w, in recording order, as Launch records."""
+# ---- the other launch families of a default job: what one recorded call keeps -------------------------------------------------------
+# ops.group_norm.  sync: whether the caller lent its sync block (the cluster and the row-major forms run only then)
+NormLaunch = collections.namedtuple("NormLaunch", ["name", "batch", "hw", "c0", "c1", "silu", "sync"])
+# ops.attention.  workspace_floats: the d = 512 key-split scratch the engine lent (0: none)
+AttnLaunch = collections.namedtuple("AttnLaunch", ["name", "batch", "heads", "head_dim", "s", "t", "q_ld", "k_ld", "vt_ld", "o_ld", "causal",
+                                                   "q_prescaled", "workspace_floats", "scale"])
+# ops.cross_attention_q.  ln_in_slots: the row-moment partials per row its producer left; w_layout: how the folded to_q weights lie
+XattnLaunch = collections.namedtuple("XattnLaunch", ["name", "batch", "heads", "head_dim", "s", "t", "k_ld", "vt_ld", "o_ld", "ln_in_slots", "w_layout"])
+# ops.conv_direct.  in_batch_mod: the input's rows (output row b reads input row b % in_batch_mod)
+DirectLaunch = collections.namedtuple("DirectLaunch", ["name", "batch", "in_batch_mod", "h_in", "w_in", "c_in", "c_out", "ksize", "stride", "in_dtype",
+                                                       "out_dtype", "act", "act_in", "in_scale", "bias", "residual"])
+# ops.layer_norm as a launch of its own (the text encoder's; the UNet's LayerNorms are folded into their consumers)
+LnLaunch = collections.namedtuple("LnLaunch", ["name", "batch", "rows", "c"])
+
+FAMILIES = ("conv_gemm", "group_norm", "attention", "cross_attention_q", "conv_direct", "layer_norm")
+
+
+def _norm_launch(kw):
+    return NormLaunch(name=kw.get("name", ""), batch=kw["batch"], hw=kw["hw"], c0=kw["c0"], c1=kw.get("c1", 0), silu=bool(kw.get("silu", False)),
+                      sync=kw.get("sync") is not None)
+
+
+def _attn_launch(kw):
+    return AttnLaunch(name=kw.get("name", ""), batch=kw["batch"], heads=kw["heads"], head_dim=kw["head_dim"], s=kw["s"], t=kw["t"], q_ld=kw["q_ld"],
+                      k_ld=kw["k_ld"], vt_ld=kw["vt_ld"], o_ld=kw["o_ld"], causal=bool(kw.get("causal", False)),
+                      q_prescaled=bool(kw.get("q_prescaled", False)),
+                      workspace_floats=int(kw.get("workspace_floats", 0)) if kw.get("workspace") is not None else 0, scale=float(kw["scale"]))
+
+
+def _xattn_launch(kw):
+    return XattnLaunch(name=kw.get("name", ""), batch=kw["batch"], heads=kw["heads"], head_dim=kw["head_dim"], s=kw["s"], t=kw["t"], k_ld=kw["k_ld"],
+                       vt_ld=kw["vt_ld"], o_ld=kw["o_ld"], ln_in_slots=kw["ln_in_slots"], w_layout=kw.get("w_layout", 0))
+
+
+def _direct_launch(kw):
+    from minsdtf_amd import ops
+
+    mod = kw.get("in_batch_mod")
+    return DirectLaunch(name=kw.get("name", ""), batch=kw["batch"], in_batch_mod=kw["batch"] if mod is None else mod, h_in=kw["h_in"], w_in=kw["w_in"],
+                        c_in=kw["c_in"], c_out=kw["c_out"], ksize=kw.get("ksize", 3), stride=kw.get("stride", 1),
+                        in_dtype=kw.get("in_dtype", ops.OUT_BF16), out_dtype=kw.get("out_dtype", ops.OUT_BF16), act=kw.get("act", ops.ACT_NONE),
+                        act_in=bool(kw.get("act_in", False)), in_scale=float(kw.get("in_scale", 1.0)), bias=kw.get("bias") is not None,
+                        residual=kw.get("residual") is not None)
+
+
+def _ln_launch(kw, nb):
+    return LnLaunch(name=kw.get("name", ""), batch=nb, rows=kw["rows"], c=kw["c"])
+
+
+def walk_families(what, nb, h, w):
+    """Every launch of the families above that the emitters record for `what` ("unet" | "controlnet" | "vae" | "vae_enc" | "text") at
+    fused batch nb and latent size h x w (text: h tokens, w = 1), in recording order: {family: [records]}.  The decoder is walked
+    with the uint8 output a default job asks of it (models.ImageDecoder.decode_to_uint8); no msd_conv_gemm record reads that."""
     from minsdtf_amd import engine, ops
     from minsdtf_amd import weights as wtab
 
-    out = []
+    out = {f: [] for f in FAMILIES}
     orig = engine.Plan.rec
 
     def rec(self, fn, **kw):
         if fn is ops.conv_gemm:
-            out.append(_launch(kw))
+            out["conv_gemm"].append(_launch(kw))
+        elif fn is ops.group_norm:
+            out["group_norm"].append(_norm_launch(kw))
+        elif fn is ops.attention:
+            out["attention"].append(_attn_launch(kw))
+        elif fn is ops.cross_attention_q:
+            out["cross_attention_q"].append(_xattn_launch(kw))
+        elif fn is ops.conv_direct:
+            out["conv_direct"].append(_direct_launch(kw))
+        elif fn is ops.layer_norm:
+            out["layer_norm"].append(_ln_launch(kw, nb))
         return orig(self, fn, **kw)
 
     engine.Plan.rec = rec
@@ -100,14 +162,22 @@ def walk(what, nb, h, w):
                 outs = [p.act(nb, h >> lv, w >> lv, ch) for lv, ch in zip((0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3), wtab.UNET_SKIP_CH + (1280,))]
                 engine.emit_controlnet(e, T(), nb, nb, h, w, temb, kv, 77, p.act(nb, h, w, 320), outs)
         elif what == "vae":
-            engine.emit_decoder(e, T(), nb, h, w, T(), 0)
+            engine.emit_decoder(e, T(), nb, h, w, T(), ops.OUT_U8)
         elif what == "vae_enc":
             engine.emit_encoder(e, T(), nb, 8 * h, 8 * w, T())
+        elif what == "text":
+            engine.emit_text_encoder(e, p.act(nb, h, w, 768), 12)
         else:
             raise ValueError(what)
     finally:
         engine.Plan.rec = orig
     return out
+
+
+def walk(what, nb, h, w):
+    """Every ops.conv_gemm call the emitters record for `what` ("unet" | "controlnet" | "vae" | "vae_enc") at fused batch nb and
+    latent size h x w, in recording order, as Launch records."""
+    return walk_families(what, nb, h, w)["conv_gemm"]
 
 
 def out_hw(l):
@@ -218,6 +288,126 @@ def config_is_built(cfg, shape):
     if -(-N // bn) >= 256:   # column tiles travel in 8 bits of a packed launch argument (cg_hot_ok)
         return False
     return not (bm == 256 and M < 1024) and not (bn == 128 and N <= 64) and not (bn == 80 and (N % 80 or not allow_split)) and not (bn == 160 and (N % 160 or N < 1280))
+
+
+# ---- signatures, ids and case lists of the other families (tests/test_layer_launches_gpu.py) -----------------------------------------
+# A signature is the record without its batch and its name, and without what follows from the batch or from the producer's
+# configuration: attention keeps the workspace PER SAMPLE (the engine lends 4 * batch * s * 514 floats), cross_attention_q leaves
+# ln_in_slots and w_layout to the records (the producing GEMM's tile decides the slots, and the tile follows the batch), conv_direct
+# keeps whether all output rows read the same input rows (in_batch_mod < batch) instead of the row count.
+# The walks: ALL_WALKS plus the CLIP text transformer at one and two prompts (its causal d = 64 attention, its LayerNorm launches)
+FAMILY_WALKS = ALL_WALKS + (("text", 1, 77, 1), ("text", 2, 77, 1))
+
+NormSig = collections.namedtuple("NormSig", ["hw", "c0", "c1", "silu", "sync"])
+AttnSig = collections.namedtuple("AttnSig", ["heads", "head_dim", "s", "t", "q_ld", "k_ld", "vt_ld", "o_ld", "causal", "q_prescaled",
+                                             "workspace_per_sample", "scale"])
+XattnSig = collections.namedtuple("XattnSig", ["heads", "head_dim", "s", "t", "k_ld", "vt_ld", "o_ld"])
+DirectSig = collections.namedtuple("DirectSig", ["shared_input", "h_in", "w_in", "c_in", "c_out", "ksize", "stride", "in_dtype", "out_dtype", "act",
+                                                 "act_in", "in_scale", "bias", "residual"])
+LnSig = collections.namedtuple("LnSig", ["rows_per_sample", "c"])
+
+
+def family_signature(family, l):
+    if family == "conv_gemm":
+        return signature(l)
+    if family == "group_norm":
+        return NormSig(l.hw, l.c0, l.c1, l.silu, l.sync)
+    if family == "attention":
+        assert l.workspace_floats % l.batch == 0
+        return AttnSig(l.heads, l.head_dim, l.s, l.t, l.q_ld, l.k_ld, l.vt_ld, l.o_ld, l.causal, l.q_prescaled, l.workspace_floats // l.batch, l.scale)
+    if family == "cross_attention_q":
+        return XattnSig(l.heads, l.head_dim, l.s, l.t, l.k_ld, l.vt_ld, l.o_ld)
+    if family == "conv_direct":
+        return DirectSig(l.in_batch_mod != l.batch, l.h_in, l.w_in, l.c_in, l.c_out, l.ksize, l.stride, l.in_dtype, l.out_dtype, l.act, l.act_in,
+                         l.in_scale, l.bias, l.residual)
+    if family == "layer_norm":
+        assert l.rows % l.batch == 0
+        return LnSig(l.rows // l.batch, l.c)
+    raise ValueError(family)
+
+
+def family_id(family, s):
+    """'gn 4096x640|320 silu', 'attn 8x40 s4096 t4096 vt4096 presc', 'xattn 8x40 s4096 t77 vt80', 'direct 64x64x4->320k3s1 f32->bf16 bias',
+    'ln 77x768'."""
+    from minsdtf_amd import ops
+
+    if family == "conv_gemm":
+        return sig_id(s)
+    if family == "group_norm":
+        words = [f"gn {s.hw}x{s.c0}" + (f"|{s.c1}" if s.c1 else "")] + [n for n, on in (("silu", s.silu), ("nosync", not s.sync)) if on]
+    elif family == "attention":
+        words = [f"attn {s.heads}x{s.head_dim} s{s.s} t{s.t} vt{s.vt_ld}"]
+        if not (s.q_ld == s.k_ld == s.o_ld == s.heads * s.head_dim):
+            words.append(f"ld{s.q_ld},{s.k_ld},{s.o_ld}")
+        words += [n for n, on in (("causal", s.causal), ("presc", s.q_prescaled), ("ws", s.workspace_per_sample)) if on]
+        if abs(s.scale - s.head_dim ** -0.5) > 1e-6 * s.scale:
+            words.append(f"scale{s.scale:.6g}")
+    elif family == "cross_attention_q":
+        words = [f"xattn {s.heads}x{s.head_dim} s{s.s} t{s.t} vt{s.vt_ld}"]
+        if not (s.k_ld == s.o_ld == s.heads * s.head_dim):
+            words.append(f"ld{s.k_ld},{s.o_ld}")
+    elif family == "conv_direct":
+        dt = {ops.OUT_BF16: "bf16", ops.OUT_F32: "f32", ops.OUT_U8: "u8"}
+        words = [f"direct {s.h_in}x{s.w_in}x{s.c_in}->{s.c_out}k{s.ksize}s{s.stride} {dt[s.in_dtype]}->{dt[s.out_dtype]}"]
+        words += [n for n, on in (("bias", s.bias), ("resid", s.residual), ("shared_in", s.shared_input), ("act_in", s.act_in)) if on]
+        if s.in_scale != 1.0:
+            words.append(f"scale{s.in_scale:.6g}")
+        act = {ops.ACT_NONE: None, ops.ACT_SILU: "silu", ops.ACT_QUICK_GELU: "quick_gelu"}[s.act]
+        if act:
+            words.append(act)
+    elif family == "layer_norm":
+        words = [f"ln {s.rows_per_sample}x{s.c}"]
+    else:
+        raise ValueError(family)
+    return " ".join(words)
+
+
+# Signatures per family over FAMILY_WALKS, kept like EXPECTED_CASES: tests/test_layer_cases_cpu.py holds them to what the walk finds,
+# tests/test_layer_launches_gpu.py asserts that it ran this many cases of each.
+EXPECTED_FAMILY_CASES = {"group_norm": 70, "attention": 21, "cross_attention_q": 6, "conv_direct": 12, "layer_norm": 1}
+
+_family_cases = None
+
+
+def family_cases(family=None, walks=FAMILY_WALKS):
+    """{family: {signature: {batch: [distinct records, names dropped]}}} over `walks`, in first-seen order (or one family's dict): one
+    GPU test case per signature.  "conv_gemm" is left to cases(): its list is ALL_WALKS', without the text transformer."""
+    global _family_cases
+    if walks is FAMILY_WALKS and _family_cases is not None:
+        out = _family_cases
+    else:
+        out = {f: collections.OrderedDict() for f in FAMILIES if f != "conv_gemm"}
+        for (what, nb, h, w) in walks:
+            fam = walk_families(what, nb, h, w)
+            for f in out:
+                for l in fam[f]:
+                    per = out[f].setdefault(family_signature(f, l), {}).setdefault(l.batch, [])
+                    l = l._replace(name="")
+                    if l not in per:
+                        per.append(l)
+        if walks is FAMILY_WALKS:
+            _family_cases = out
+    return out if family is None else out[family]
+
+
+def cases_group_norm():
+    return family_cases("group_norm")
+
+
+def cases_attention():
+    return family_cases("attention")
+
+
+def cases_cross_attention_q():
+    return family_cases("cross_attention_q")
+
+
+def cases_conv_direct():
+    return family_cases("conv_direct")
+
+
+def cases_layer_norm():
+    return family_cases("layer_norm")
 
 
 # ---- the second walker: EVERY recorded launch with the state of its buffers (tests/test_plan_extents_cpu.py) -----------------------
