@@ -381,6 +381,59 @@ XATTN_FUSED_D160 = os.environ.get("MSD_XATTN_FUSED_D160", "0") != "0"
 
 
 # ----------------------------------------------------------------------------- layer emitters
+@dataclass(frozen=True)
+class AttnVariant:
+    """How one attention block (Emitter.attentions) differs from the plain block.  AttnVariant() records exactly the plain block;
+    constructing one checks nothing - check(), which also says what does not go together, runs when the block is emitted."""
+    # perturbed-attention guidance (minsdtf_amd/pag.py): the number of TRAILING batch rows whose attn1 uses the identity attention
+    # map - their output is V itself (msd_attention_identity, the transpose of V^T), the rows in front of them take msd_attention as
+    # always.  Not with shared > 1: the copies are no longer identical behind this attn1.
+    perturbed: int = 0
+    # regions = R (regional prompting inside cross-attention, minsdtf_amd/regions.py mode "attention"): the TRAILING `region_rows`
+    # rows of the batch are the conditional rows and ctx_kv holds B_u + R * region_rows context rows - the unconditional rows'
+    # first, then the regions', region-major.  attn2 then takes the unfused route: q from attn2.to_q, msd_attention for the
+    # unconditional rows, ONE msd_region_attention launch for the conditional rows with the weight plane `region_w`
+    # (fp32 [R][H * W], this level's).
+    regions: int = 0
+    region_rows: int = 0
+    region_w: object = None
+    # reference = 1 (reference-only control, minsdtf_amd/reference.py): the LAST row of `x` is the reference row.  attn1 of the
+    # rows in front of it is ONE msd_attention_joint launch - own keys, then the reference row's (k_ref / vt_ref are views of the
+    # same k / vt buffers at row B - 1), blended with the plain result by `mix` (fp32 [B - 1], or None) - and the reference row
+    # takes one msd_attention with batch = 1 at the offset pointers.
+    reference: int = 0
+    mix: object = None
+    # window = (nh, nw) (HyperTile, minsdtf_amd/hypertile.py): attn1 is ONE msd_attention_windowed launch in place of msd_attention -
+    # the attention is taken inside nh x nw non-overlapping windows of H / nh x W / nw tokens, on the operands where the q|k|v GEMM
+    # wrote them.  Also with shared > 1: the launch runs on the one copy.
+    window: Optional[tuple] = None
+    # colsum = (out, workspace, row0, rows) (self-attention guidance, minsdtf_amd/sag.py): right behind attn1, while q and k are
+    # live, ONE msdx_attention_colsum launch writes the attention every key of the rows row0 .. row0 + rows - 1 receives - fp32
+    # [rows][H * W] to `out`, through `workspace` (ops.colsum_workspace_floats(rows, heads, H * W) floats).  Head size 160: the mid block.
+    colsum: Optional[tuple] = None
+
+    def check(self, name, x: Act, heads: int, shared: int) -> None:
+        """What the fields exclude for the block `name` over the whole input x (all `shared` copies), as ValueError."""
+        perturbed, regions, reference, window = self.perturbed, self.regions, self.reference, self.window
+        if self.colsum is not None:
+            _cs_out, _cs_ws, cs_row0, cs_rows = self.colsum
+            if x.C // heads != 160 or shared > 1 or reference or window is not None or cs_row0 < 0 or cs_rows < 1 \
+                    or cs_row0 + cs_rows > x.B - perturbed:
+                raise ValueError(f"{name}: colsum over rows {cs_row0} .. {cs_row0 + cs_rows - 1} of {x.B} at head size {x.C // heads} "
+                                 f"(shared = {shared}, perturbed = {perturbed}, reference = {reference}, window = {window})")
+        if window is not None:
+            nh, nw = (int(v) for v in window)
+            if perturbed or reference:
+                raise ValueError(f"{name}: window = {window} with perturbed = {perturbed}, reference = {reference}")
+            if nh < 1 or nw < 1 or x.H % nh or x.W % nw or (x.W // nw) % 8 or x.C // heads not in (40, 80, 160):
+                raise ValueError(f"{name}: {nh} x {nw} windows of a {x.H} x {x.W} map at head size {x.C // heads} "
+                                 "(whole windows whose width is a multiple of 8 tokens; head size 40, 80 or 160)")
+        if reference not in (0, 1) or (reference and (shared > 1 or perturbed or regions or x.B < 2)):
+            raise ValueError(f"{name}: reference = {reference} with {x.B} rows (shared = {shared}, perturbed = {perturbed}, regions = {regions})")
+        if not 0 <= perturbed <= x.B or (perturbed and shared > 1):
+            raise ValueError(f"{name}: {perturbed} perturbed rows of {x.B} (shared = {shared})")
+
+
 class Emitter:
     """Emits the calls of the reference's layer types into a Plan. `W` maps logical weight names to
     device tensors prepared by the model classes (minsdtf_amd/models.py)."""
@@ -527,136 +580,109 @@ class Emitter:
                 p.free(a)
         return out
 
-    def attentions(self, x: Act, name, ctx_kv, ctx_len, heads=8, free_input=False, shared: int = 1, perturbed: int = 0,
-                   regions: int = 0, region_rows: int = 0, region_w=None, reference: int = 0, mix=None, window=None,
-                   colsum=None) -> Act:
+    def attentions(self, x: Act, name, ctx_kv, ctx_len, heads=8, free_input=False, shared: int = 1, variant=AttnVariant()) -> Act:
         """Attentions / TransformerBlock / CrossAttention / GEGLU (diffusion_model.py:54-153).  shared > 1 (SHARE_CFG_PREFIX): `x` holds
         `shared` identical copies of x.B / shared samples (the cond and uncond halves in front of the first cross-attention): norm,
         proj_in, q|k|v, the self-attention and its to_out run on ONE copy, their result (rows + LayerNorm partials) is replicated, and the
         block continues on the whole batch from attn2 on, where the halves' text contexts differ.
-        perturbed (perturbed-attention guidance, minsdtf_amd/pag.py): the number of TRAILING batch rows whose attn1 uses the identity
-        attention map - their output is V itself (msd_attention_identity, the transpose of V^T), the rows in front of them take
-        msd_attention as always.  Not with shared > 1: the copies are no longer identical behind this attn1.
-        regions = R (regional prompting inside cross-attention, minsdtf_amd/regions.py mode "attention"): the TRAILING `region_rows`
-        rows of the batch are the conditional rows and ctx_kv holds B_u + R * region_rows context rows - the unconditional rows'
-        first, then the regions', region-major.  attn2 then takes the unfused route: q from attn2.to_q, msd_attention for the
-        unconditional rows, ONE msd_region_attention launch for the conditional rows with the weight plane `region_w`
-        (fp32 [R][H * W], this level's).  regions = 0 records exactly the plain block.
-        reference = 1 (reference-only control, minsdtf_amd/reference.py): the LAST row of `x` is the reference row.  attn1 of the
-        rows in front of it is ONE msd_attention_joint launch - own keys, then the reference row's (k_ref / vt_ref are views of the
-        same k / vt buffers at row B - 1), blended with the plain result by `mix` (fp32 [B - 1], or None) - and the reference row
-        takes one msd_attention with batch = 1 at the offset pointers.  Not with shared > 1, perturbed or regions.  reference = 0
-        records exactly the plain block.
-        window = (nh, nw) (HyperTile, minsdtf_amd/hypertile.py): attn1 is ONE msd_attention_windowed launch in place of msd_attention -
-        the attention is taken inside nh x nw non-overlapping windows of H / nh x W / nw tokens, on the operands where the q|k|v GEMM
-        wrote them.  Also with shared > 1 (the launch runs on the one copy); not with perturbed or reference.  None records exactly
-        the plain block.
-        colsum = (out, workspace, row0, rows) (self-attention guidance, minsdtf_amd/sag.py): right behind attn1, while q and k are
-        live, ONE msdx_attention_colsum launch writes the attention every key of the rows row0 .. row0 + rows - 1 receives - fp32
-        [rows][H * W] to `out`, through `workspace` (ops.colsum_workspace_floats(rows, heads, H * W) floats).  Head size 160 (the mid
-        block); not with shared > 1, reference or a window, and not over perturbed rows.  None records exactly the plain block."""
+        variant: how the block differs from the plain one (AttnVariant: its fields say what _attn1 / _attn2 then record)."""
         p = self.p
-        x_all = x
-        if colsum is not None:
-            _cs_out, _cs_ws, cs_row0, cs_rows = colsum
-            if x.C // heads != 160 or shared > 1 or reference or window is not None or cs_row0 < 0 or cs_rows < 1 \
-                    or cs_row0 + cs_rows > x.B - perturbed:
-                raise ValueError(f"{name}: colsum over rows {cs_row0} .. {cs_row0 + cs_rows - 1} of {x.B} at head size {x.C // heads} "
-                                 f"(shared = {shared}, perturbed = {perturbed}, reference = {reference}, window = {window})")
-        if window is not None:
-            nh, nw = (int(v) for v in window)
-            if perturbed or reference:
-                raise ValueError(f"{name}: window = {window} with perturbed = {perturbed}, reference = {reference}")
-            if nh < 1 or nw < 1 or x.H % nh or x.W % nw or (x.W // nw) % 8 or x.C // heads not in (40, 80, 160):
-                raise ValueError(f"{name}: {nh} x {nw} windows of a {x.H} x {x.W} map at head size {x.C // heads} "
-                                 "(whole windows whose width is a multiple of 8 tokens; head size 40, 80 or 160)")
-        if reference not in (0, 1) or (reference and (shared > 1 or perturbed or regions or x.B < 2)):
-            raise ValueError(f"{name}: reference = {reference} with {x.B} rows (shared = {shared}, perturbed = {perturbed}, regions = {regions})")
-        if not 0 <= perturbed <= x.B or (perturbed and shared > 1):
-            raise ValueError(f"{name}: {perturbed} perturbed rows of {x.B} (shared = {shared})")
-        if shared > 1:
-            assert x.B % shared == 0
-            x = Act(x.buf, x.B // shared, x.H, x.W, x.C)   # the first copy
-        B, H, Wd, C = x.B, x.H, x.W, x.C
-        S = H * Wd
-        d = C // heads
+        variant.check(name, x, heads, shared)
+        assert x.B % shared == 0
+        one = Act(x.buf, x.B // shared, x.H, x.W, x.C)   # the first copy (all of x where nothing is shared)
         tb = name + ".transformer_blocks.0"
         fold = LN_FOLD and (tb + ".attn1.qkv.lnw") in self.W
-        g = self.group_norm(x, name + ".norm", silu=False)
-        t0 = self.conv(g, name + ".proj_in", C, ln_out=fold)
+        g = self.group_norm(one, name + ".norm", silu=False)
+        t0 = self.conv(g, name + ".proj_in", x.C, ln_out=fold)
         p.free(g)
-        # self-attention: fused q|k|v projection, v written transposed for the PV product
+        a1 = self._attn1(t0, name, tb, heads, fold, variant)
+        t1 = self._attn1_out(a1, t0, tb, fold, shared)
+        a2 = self._attn2(t1, name, tb, ctx_kv, ctx_len, heads, fold, variant)
+        t2 = self.conv(a2, tb + ".attn2.to_out.0", x.C, residual=t1, ln_out=fold)
+        p.free(a2, t1)
+        out = self._feed_forward(t2, name, tb, fold, x)
+        if free_input:
+            p.free(x)
+        return out
+
+    def _ln_conv(self, x: Act, norm_name, conv_name, N, fold: bool, bias: bool = False, **conv_kw):
+        """LayerNorm `norm_name` of x, then the GEMM `conv_name`.  fold: as ONE launch, on x's row-moment partials (x.ln, freed behind it),
+        the norm's shift in the bias; else layer_norm, then the GEMM, with its own bias where `bias`, and the normalised rows are freed."""
+        if fold:
+            out = self.conv(x, conv_name, N, bias=False, ln_in=x.ln, **conv_kw)
+            self.p.free(x.ln[0])
+            return out
+        n = self.layer_norm(x, norm_name)
+        out = self.conv(n, conv_name, N, bias=bias, **conv_kw)
+        self.p.free(n)
+        return out
+
+    def _attn1(self, t0: Act, name, tb, heads, fold: bool, v: AttnVariant) -> Act:
+        """norm1 -> fused q|k|v projection (v written transposed for the PV product) -> the self-attention of the variant."""
+        p = self.p
+        B, H, Wd, C = t0.B, t0.H, t0.W, t0.C
+        S, d = H * Wd, C // heads
         q, k = p.act(B, H, Wd, C), p.act(B, H, Wd, C)
         sp = (S + 7) // 8 * 8  # V^T rows are read in 16-byte chunks
         vt = p.alloc(B * C * sp * 2)
-        if fold:   # LayerNorm(norm1) inside the q|k|v GEMM
-            self.conv(t0, tb + ".attn1.qkv", 3 * C, bias=False, split=(C, C, q.buf, k.buf, vt, sp), ln_in=t0.ln)
-            p.free(t0.ln[0])
-        else:
-            n1 = self.layer_norm(t0, tb + ".norm1")
-            self.conv(n1, tb + ".attn1.qkv", 3 * C, bias=False, split=(C, C, q.buf, k.buf, vt, sp))
-            p.free(n1)
+        self._ln_conv(t0, tb + ".norm1", tb + ".attn1.qkv", 3 * C, fold, split=(C, C, q.buf, k.buf, vt, sp))
         a1 = p.act(B, H, Wd, C)
-        if reference:
+        if v.reference:
             if d not in (40, 80, 160):
                 raise ValueError(f"{name}: reference-only attention at head size {d}")
             g_rows = B - 1   # the generated rows; row B - 1 is the reference
             p.rec(ops.attention_joint, q=q.buf, k=k.buf, vt=vt, k_ref=k.buf.at(g_rows * S * C * 2), vt_ref=vt.at(g_rows * C * sp * 2),
-                  mix=mix, out=a1.buf, batch=g_rows, heads=heads, head_dim=d, s=S, t=S, t_ref=S, q_ld=C, k_ld=C, vt_ld=sp, o_ld=C,
+                  mix=v.mix, out=a1.buf, batch=g_rows, heads=heads, head_dim=d, s=S, t=S, t_ref=S, q_ld=C, k_ld=C, vt_ld=sp, o_ld=C,
                   name=tb + ".attn1.joint")
             p.rec(ops.attention, q=q.buf.at(g_rows * S * C * 2), k=k.buf.at(g_rows * S * C * 2), vt=vt.at(g_rows * C * sp * 2),
                   out=a1.buf.at(g_rows * S * C * 2), batch=1, heads=heads, head_dim=d, s=S, t=S, q_ld=C, k_ld=C, vt_ld=sp, o_ld=C,
                   scale=d ** -0.5, q_prescaled=True, name=tb + ".attn1")
-        elif window is not None:
+        elif v.window is not None:
+            nh, nw = (int(n) for n in v.window)
             p.rec(ops.attention_windowed, q=q.buf, k=k.buf, vt=vt, out=a1.buf, batch=B, heads=heads, head_dim=d, h=H, w=Wd, wh=H // nh,
                   ww=Wd // nw, q_ld=C, k_ld=C, vt_ld=sp, o_ld=C, name=tb + ".attn1.windowed")
-        elif perturbed < B:
-            p.rec(ops.attention, q=q.buf, k=k.buf, vt=vt, out=a1.buf, batch=B - perturbed, heads=heads, head_dim=d, s=S, t=S, q_ld=C,
+        elif v.perturbed < B:
+            p.rec(ops.attention, q=q.buf, k=k.buf, vt=vt, out=a1.buf, batch=B - v.perturbed, heads=heads, head_dim=d, s=S, t=S, q_ld=C,
                   k_ld=C, vt_ld=sp, o_ld=C, scale=d ** -0.5, q_prescaled=True, name=tb + ".attn1")
-        if perturbed:   # the last `perturbed` rows: out = V
-            p.rec(ops.attention_identity, vt=vt.at((B - perturbed) * C * sp * 2), out=a1.buf.at((B - perturbed) * S * C * 2),
-                  batch=perturbed, channels=C, s=S, vt_ld=sp, o_ld=C, name=tb + ".attn1.identity")
-        if colsum is not None:
-            p.rec(ops.attention_colsum, q=q.buf.at(cs_row0 * S * C * 2), k=k.buf.at(cs_row0 * S * C * 2), out=colsum[0], workspace=colsum[1],
+        if v.perturbed:   # the last `perturbed` rows: out = V
+            p.rec(ops.attention_identity, vt=vt.at((B - v.perturbed) * C * sp * 2), out=a1.buf.at((B - v.perturbed) * S * C * 2),
+                  batch=v.perturbed, channels=C, s=S, vt_ld=sp, o_ld=C, name=tb + ".attn1.identity")
+        if v.colsum is not None:
+            cs_out, cs_ws, cs_row0, cs_rows = v.colsum
+            p.rec(ops.attention_colsum, q=q.buf.at(cs_row0 * S * C * 2), k=k.buf.at(cs_row0 * S * C * 2), out=cs_out, workspace=cs_ws,
                   batch=cs_rows, heads=heads, head_dim=d, s=S, q_ld=C, k_ld=C, name=tb + ".attn1.colsum")
         p.free(q, k, vt)
-        if shared > 1:
-            t1_wide = p.act(B * shared, H, Wd, C)
-            t1 = self.conv(a1, tb + ".attn1.to_out.0", C, residual=t0, ln_out=fold, out=Act(t1_wide.buf, B, H, Wd, C))
-            p.free(a1, t0)
-            ln = t1.ln
-            t1 = self.widen(t1, shared, tb + ".attn1.to_out.0")
-            if ln is not None:   # the row-moment partials of the rows, replicated like the rows
-                nb_ln = B * H * Wd * ln[1] * 8
-                ln_wide = p.alloc(shared * nb_ln)
-                p.rec(ops.replicate, src=ln[0], dst=ln_wide, nbytes=nb_ln, copies=shared, name=tb + ".attn1.to_out.0.ln.replicate")
-                p.free(ln[0])
-                t1.ln = (ln_wide, ln[1])
-            x, B = x_all, B * shared
-        else:
-            t1 = self.conv(a1, tb + ".attn1.to_out.0", C, residual=t0, ln_out=fold)
-            p.free(a1, t0)
-        # cross-attention over the text context (k, v^T precomputed once per prompt)
+        return a1
+
+    def _attn1_out(self, a1: Act, t0: Act, tb, fold: bool, shared: int) -> Act:
+        """attn1.to_out.0 over the residual t0; shared > 1: the rows and their row-moment partials are replicated, the whole batch comes back."""
+        p = self.p
+        B, H, Wd, C = a1.B, a1.H, a1.W, a1.C
+        head = Act(p.act(B * shared, H, Wd, C).buf, B, H, Wd, C) if shared > 1 else None
+        t1 = self.conv(a1, tb + ".attn1.to_out.0", C, residual=t0, ln_out=fold, out=head)
+        p.free(a1, t0)
+        ln = t1.ln
+        t1 = self.widen(t1, shared, tb + ".attn1.to_out.0")
+        if shared > 1 and ln is not None:   # the row-moment partials of the rows, replicated like the rows
+            nb_ln = B * H * Wd * ln[1] * 8
+            ln_wide = p.alloc(shared * nb_ln)
+            p.rec(ops.replicate, src=ln[0], dst=ln_wide, nbytes=nb_ln, copies=shared, name=tb + ".attn1.to_out.0.ln.replicate")
+            p.free(ln[0])
+            t1.ln = (ln_wide, ln[1])
+        return t1
+
+    def _attn2(self, t1: Act, name, tb, ctx_kv, ctx_len, heads, fold: bool, v: AttnVariant) -> Act:
+        """Cross-attention over the text context (k, v^T precomputed once per prompt): norm2 -> to_q -> attention, as ONE launch where
+        the fused kernel has the shape, else as its parts; with regions the conditional rows take the region launch on those parts."""
+        p = self.p
+        B, H, Wd, C = t1.B, t1.H, t1.W, t1.C
+        S, d = H * Wd, C // heads
         kc, vtc, tp = ctx_kv[tb + ".attn2"]
         a2 = p.act(B, H, Wd, C)
-        if regions:
-            bu = B - region_rows   # unconditional rows in front
-            if not 1 <= region_rows <= B or region_w is None or ctx_len > 96 or d not in (40, 80, 160):
-                raise ValueError(f"{name}: {regions} regions over {region_rows} of {B} rows, {ctx_len} context tokens, head size {d}")
-            if fold:
-                q2 = self.conv(t1, tb + ".attn2.to_q", C, bias=False, ln_in=t1.ln)
-                p.free(t1.ln[0])
-            else:
-                n2 = self.layer_norm(t1, tb + ".norm2")
-                q2 = self.conv(n2, tb + ".attn2.to_q", C, bias=False)
-                p.free(n2)
-            if bu:
-                p.rec(ops.attention, q=q2.buf, k=kc, vt=vtc, out=a2.buf, batch=bu, heads=heads, head_dim=d, s=S, t=ctx_len, q_ld=C,
-                      k_ld=C, vt_ld=tp, o_ld=C, scale=d ** -0.5, q_prescaled=True, name=tb + ".attn2")
-            p.rec(ops.region_attention, q=q2.buf.at(bu * S * C * 2), k=kc.at(bu * ctx_len * C * 2), vt=vtc.at(bu * C * tp * 2),
-                  w=region_w, out=a2.buf.at(bu * S * C * 2), batch=region_rows, heads=heads, head_dim=d, s=S, t=ctx_len,
-                  regions=regions, q_ld=C, k_ld=C, vt_ld=tp, w_ld=S, o_ld=C, name=tb + ".attn2.regions")
-            p.free(q2)
+        bu = B - v.region_rows if v.regions else B   # the rows msd_attention takes: the unconditional rows in front, or all
+        if v.regions:
+            if not 1 <= v.region_rows <= B or v.region_w is None or ctx_len > 96 or d not in (40, 80, 160):
+                raise ValueError(f"{name}: {v.regions} regions over {v.region_rows} of {B} rows, {ctx_len} context tokens, head size {d}")
         elif fold and XATTN_FUSED and heads == 8 and (d in (40, 80) or (d == 160 and XATTN_FUSED_D160)) and ctx_len <= 96:
             # norm2 -> to_q -> attention over the 77 context tokens as ONE launch (msd_cross_attention_q)
             wn = tb + ".attn2.to_q"
@@ -665,27 +691,23 @@ class Emitter:
                   head_dim=d, s=S, t=ctx_len, k_ld=C, vt_ld=tp, o_ld=C, ln_eps=EPS, w_layout=self.w_layout(wn + ".lnw"),
                   name=tb + ".attn2")
             p.free(t1.ln[0])
-        else:
-            if fold:
-                q2 = self.conv(t1, tb + ".attn2.to_q", C, bias=False, ln_in=t1.ln)
-                p.free(t1.ln[0])
-            else:
-                n2 = self.layer_norm(t1, tb + ".norm2")
-                q2 = self.conv(n2, tb + ".attn2.to_q", C, bias=False)
-                p.free(n2)
-            p.rec(ops.attention, q=q2.buf, k=kc, vt=vtc, out=a2.buf, batch=B, heads=heads, head_dim=d, s=S, t=ctx_len, q_ld=C,
+            return a2
+        q2 = self._ln_conv(t1, tb + ".norm2", tb + ".attn2.to_q", C, fold)
+        if bu:
+            p.rec(ops.attention, q=q2.buf, k=kc, vt=vtc, out=a2.buf, batch=bu, heads=heads, head_dim=d, s=S, t=ctx_len, q_ld=C,
                   k_ld=C, vt_ld=tp, o_ld=C, scale=d ** -0.5, q_prescaled=True, name=tb + ".attn2")
-            p.free(q2)
-        t2 = self.conv(a2, tb + ".attn2.to_out.0", C, residual=t1, ln_out=fold)
-        p.free(a2, t1)
-        # feed-forward: GEGLU fused into the first GEMM's epilogue
-        if fold:
-            ff = self.conv(t2, tb + ".ff.net.0.proj", 8 * C, act=ops.ACT_GEGLU, bias=False, ln_in=t2.ln)
-            p.free(t2.ln[0])
-        else:
-            n3 = self.layer_norm(t2, tb + ".norm3")
-            ff = self.conv(n3, tb + ".ff.net.0.proj", 8 * C, act=ops.ACT_GEGLU)
-            p.free(n3)
+        if v.regions:
+            p.rec(ops.region_attention, q=q2.buf.at(bu * S * C * 2), k=kc.at(bu * ctx_len * C * 2), vt=vtc.at(bu * C * tp * 2),
+                  w=v.region_w, out=a2.buf.at(bu * S * C * 2), batch=v.region_rows, heads=heads, head_dim=d, s=S, t=ctx_len,
+                  regions=v.regions, q_ld=C, k_ld=C, vt_ld=tp, w_ld=S, o_ld=C, name=tb + ".attn2.regions")
+        p.free(q2)
+        return a2
+
+    def _feed_forward(self, t2: Act, name, tb, fold: bool, x: Act) -> Act:
+        """norm3 -> GEGLU feed-forward (the gate fused into the first GEMM's epilogue) -> proj_out over the block's input x."""
+        p = self.p
+        C = t2.C
+        ff = self._ln_conv(t2, tb + ".norm3", tb + ".ff.net.0.proj", 8 * C, fold, bias=True, act=ops.ACT_GEGLU)
         if FF_PROJ_FOLD and (name + ".ffproj.w") in self.W:   # ff.net.2 and proj_out as one GEMM over [ff | t2]
             out = self.conv((ff, t2), name + ".ffproj", C, residual=x)
             p.free(ff, t2)
@@ -694,8 +716,6 @@ class Emitter:
             p.free(ff, t2)
             out = self.conv(t3, name + ".proj_out", C, residual=x)
             p.free(t3)
-        if free_input:
-            p.free(x)
         return out
 
 
@@ -728,6 +748,7 @@ for _ui, _lvl in enumerate((3, 2, 1, 0)):
 
 # the 16 attention blocks of the UNet, in forward order: what a PAG job may select (minsdtf_amd/pag.py)
 PAG_LAYERS: Tuple[str, ...] = tuple(n[:-len(".transformer_blocks.0.attn2")] for n, _c in UNET_ATTN_LAYERS)
+ATTN_LEVEL: Dict[str, int] = dict(zip(PAG_LAYERS, (0, 0, 1, 1, 2, 2, 3, 2, 2, 2, 1, 1, 1, 0, 0, 0)))   # their resolution level (unet_levels)
 
 
 def resblock_names(encoder_only: bool) -> List[Tuple[str, int]]:
@@ -785,69 +806,115 @@ def unet_levels(h: int, w: int) -> List[Tuple[int, int]]:
     return out
 
 
-def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1, attn_kw=lambda block, x: {},
-                  site=lambda x, name: None) -> Act:
+@dataclass(frozen=True)
+class UNetVariant:
+    """How one UNet forward (emit_unet) differs from the plain one: which attention blocks take which AttnVariant field (at()), and
+    what the network records beyond them.  UNetVariant() records exactly the plain forward; constructing one checks nothing -
+    check(), which also says what does not go together, runs when the forward is emitted."""
+    # pag_layers (a set of PAG_LAYERS names) / perturbed: those blocks take AttnVariant.perturbed, the last `perturbed` of the NB rows;
+    # with perturbed = 0 the layers select nothing.
+    pag_layers: object = None
+    perturbed: int = 0
+    # region_attn = (R, rows, {(h_l, w_l): fp32 plane [R][h_l * w_l]}): every block takes AttnVariant.regions = R over the last `rows`
+    # of the NB rows, with its level's plane; ctx_kv then holds NB - rows + R * rows context rows.
+    region_attn: Optional[tuple] = None
+    # reference = (layers, ref_latent_f32, mix): the LAST of the NB rows is the reference row - conv_in reads it from ref_latent_f32
+    # (fp32 [1][h][w][4]) in a launch of its own - and the blocks named in `layers` take AttnVariant.reference with `mix`.  Nothing
+    # is shared across the copies of such a job.
+    reference: Optional[tuple] = None
+    # adain = a set of site names (reference AdaIN, reference.ADAIN_SITES; only with `reference`, whose `layers` may then be empty):
+    # right behind the call that produces a selected site, before anything reads it, ONE msd_reference_adain launch renormalises
+    # the NB - 1 generated rows of the site buffer to the statistics of its last row, in place, blended by the reference `mix` -
+    # so the skip connection and the onward path both see the result.
+    adain: object = None
+    # window = (nh, nw) / window_depth = D: the blocks of levels 0 .. D (level 0: down_blocks.0 / up_blocks.3, d = 40; 1: d = 80;
+    # 2: d = 160) take AttnVariant.window, the same number of windows at every level; deeper levels and the mid block stay plain.
+    window: Optional[tuple] = None
+    window_depth: int = 0
+    # sag = mid_block.attentions.0's AttnVariant.colsum, its map fp32 [rows][mh * mw] with (mh, mw) = unet_levels(h, w)[3]; the mid
+    # block is never part of the shared prefix.
+    sag: Optional[tuple] = None
+
+    def _pag(self) -> frozenset:
+        return frozenset(self.pag_layers or ()) if self.perturbed else frozenset()
+
+    def check(self, NB: int, controls, control_taps) -> None:
+        """What the fields exclude for a forward of NB rows with these ControlNet residuals, as ValueError."""
+        adain = frozenset(self.adain) if self.adain else frozenset()
+        if self.reference is not None:
+            ref_layers = frozenset(self.reference[0])
+            if (not ref_layers and not adain) or ref_layers - set(PAG_LAYERS):
+                raise ValueError(f"emit_unet: reference layers {sorted(ref_layers)} (a non-empty subset of PAG_LAYERS, or empty next to adain sites)")
+            if NB < 2 or self.perturbed or self.region_attn or controls is not None or control_taps is not None:
+                raise ValueError("emit_unet: a reference row goes with at least one generated row and not with pag, regions or a ControlNet")
+        if adain:
+            from .reference import ADAIN_SITES
+
+            if adain - {n for n, _gw in ADAIN_SITES}:
+                raise ValueError(f"emit_unet: unknown adain site(s) {sorted(adain - {n for n, _gw in ADAIN_SITES})}")
+            if self.reference is None or self.window is not None:   # (pag, regions and ControlNet residuals are refused with the reference row)
+                raise ValueError("emit_unet: adain goes with a reference row and not with pag, regions, a window or a ControlNet")
+        if self._pag() - set(PAG_LAYERS):
+            raise ValueError(f"emit_unet: unknown attention block(s) {sorted(self._pag() - set(PAG_LAYERS))}")
+        if self.window is not None:
+            if self.perturbed or self.region_attn or self.reference is not None:
+                raise ValueError("emit_unet: window does not go with pag, regions or a reference row")
+            if self.window_depth not in (0, 1, 2):
+                raise ValueError(f"emit_unet: window_depth = {self.window_depth} (0, 1 or 2)")
+
+    def shared(self, NB: int, latent_batch_mod: int) -> int:
+        """The number of identical copies the front of the network runs once for (SHARE_CFG_PREFIX), or 1."""
+        if PAG_LAYERS[0] in self._pag() or self.reference is not None:
+            # perturbed rows make the first block's front differ across the copies, and a reference row is no copy of anything:
+            # nothing is shared (exact either way - a sample's bits do not depend on its batch)
+            return 1
+        return NB // latent_batch_mod if (SHARE_CFG_PREFIX and latent_batch_mod > 0 and NB % latent_batch_mod == 0) else 1
+
+    def at(self, block: str, x: Act) -> AttnVariant:
+        """How the attention block `block`, whose input is x, differs from the plain block."""
+        R, rows, planes = self.region_attn or (0, 0, None)
+        windowed = self.window is not None and ATTN_LEVEL[block] <= self.window_depth   # (such a block takes the window, not the reference)
+        referenced = not windowed and self.reference is not None and block in frozenset(self.reference[0])
+        return AttnVariant(perturbed=self.perturbed if block in self._pag() else 0, regions=R, region_rows=rows,
+                           region_w=planes[(x.H, x.W)] if self.region_attn else None,   # the weight plane of x's level
+                           reference=int(referenced), mix=self.reference[2] if referenced else None,
+                           window=tuple(self.window) if windowed else None, colsum=self.sag if block == "mid_block.attentions.0" else None)
+
+    def adain_site(self, p: Plan, x: Act, name: str, NB: int) -> None:
+        """Reference AdaIN behind the call `name` that produced x, when that output is a selected site."""
+        if self.adain and name in self.adain:
+            p.rec(ops.reference_adain, x=x.buf, ref=x.buf.at((NB - 1) * x.H * x.W * x.C * 2), mix=self.reference[2], rows=NB - 1,
+                  hw=x.H * x.W, c=x.C, eps=1e-6, name=name + ".adain")
+
+
+def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1, variant=UNetVariant(), NB: int = 0) -> Act:
     """Down path + mid block shared by the UNet (diffusion_model.py:193-229) and the ControlNet.  shared > 1: `x` (conv_in's output) is
     `shared` identical copies of x.B / shared samples - the first ResBlock and the front of the first transformer block run on one.
-    attn_kw: (block name, its input) -> what Emitter.attentions takes beyond the plain block (emit_unet's closure of that name).
-    site: (x, name of the call that produced it) -> None, emit_unet's reference AdaIN right behind a block output."""
+    variant / NB: emit_unet's, for what its attention blocks and its reference AdaIN sites take; the ControlNet passes neither."""
+    p = e.p
     for lvl, ch in enumerate(wtab.UNET_CH):
         for r in range(2):
             name, blk = f"down_blocks.{lvl}.resnets.{r}", f"down_blocks.{lvl}.attentions.{r}"
-            if shared > 1 and lvl == 0 and r == 0:
-                one = Act(x.buf, x.B // shared, x.H, x.W, x.C)
-                x = e.res_block(one, name, ch, temb=temb_of(name), out_copies=shared)
-                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, shared=shared, **attn_kw(blk, x))
-                outputs.append(x)
-                continue
-            x = e.res_block(x, name, ch, temb=temb_of(name))
+            copies = shared if (lvl == 0 and r == 0) else 1   # only the very first pair runs on one of the identical copies
+            one = Act(x.buf, x.B // copies, x.H, x.W, x.C)
+            x = e.res_block(one, name, ch, temb=temb_of(name), out_copies=copies)
             if lvl < 3:
-                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, **attn_kw(blk, x))
-                site(x, blk)
-            else:
-                site(x, name)
+                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, shared=copies, variant=variant.at(blk, x))
+            variant.adain_site(p, x, blk if lvl < 3 else name, NB)
             outputs.append(x)
         if lvl < 3:
             x = e.conv(x, f"down_blocks.{lvl}.downsamplers.0.conv", ch, ksize=3, stride=2)
             outputs.append(x)
     x = e.res_block(x, "mid_block.resnets.0", 1280, temb=temb_of("mid_block.resnets.0"))
-    x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True, **attn_kw("mid_block.attentions.0", x))
+    x = e.attentions(x, "mid_block.attentions.0", ctx_kv, ctx_len, free_input=True, variant=variant.at("mid_block.attentions.0", x))
     x = e.res_block(x, "mid_block.resnets.1", 1280, temb=temb_of("mid_block.resnets.1"), free_input=True)
-    site(x, "mid_block.resnets.1")
+    variant.adain_site(p, x, "mid_block.resnets.1", NB)
     return x
 
 
 def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w: int, temb, ctx_kv, ctx_len: int,
-              eps_out_f32, controls=None, control_taps=None, pag_layers=None, perturbed: int = 0, region_attn=None, *,
-              reference=None, window=None, window_depth: int = 0, adain=None, sag=None) -> None:
-    """DiffusionModel graph (diffusion_model.py:184-279).
-
-    window = (nh, nw) / window_depth = D (HyperTile, minsdtf_amd/hypertile.py): the self-attention of the attention blocks of levels
-    0 .. D (level 0: down_blocks.0 / up_blocks.3, d = 40; 1: d = 80; 2: d = 160) is taken inside nh x nw windows, the same number
-    at every selected level (Emitter.attentions); deeper levels and the mid block stay plain.  Not with pag_layers, region_attn or
-    reference.  None records exactly the plain forward.
-
-    region_attn = (R, rows, {(h_l, w_l): fp32 plane [R][h_l * w_l]}) (regional prompting inside cross-attention): the last `rows` of
-    the NB rows are conditional rows whose every attn2 mixes R region contexts (Emitter.attentions); ctx_kv then holds
-    NB - rows + R * rows context rows.  None records exactly the plain forward.
-
-    pag_layers (a set of attention block names, PAG_LAYERS) / perturbed: the last `perturbed` of the NB rows run those blocks'
-    self-attention with the identity map (Emitter.attentions); perturbed = 0 records exactly the plain forward.
-
-    reference = (layers, ref_latent_f32, mix) (reference-only control, minsdtf_amd/reference.py): the LAST of the NB rows is the
-    reference row - conv_in reads it from ref_latent_f32 (fp32 [1][h][w][4]) in a launch of its own - and in the attention blocks
-    named in `layers` the rows in front of it attend to its keys too (Emitter.attentions; mix: fp32 [NB - 1] or None).  Nothing is
-    shared across the copies of such a job.  Not with pag_layers, region_attn or ControlNet residuals.  None records exactly the
-    plain forward.
-
-    adain = a set of site names (reference AdaIN, reference.ADAIN_SITES; only with `reference`, whose `layers` may then be empty):
-    right behind the call that produces a selected site, before anything reads it, ONE msd_reference_adain launch renormalises
-    the NB - 1 generated rows of the site buffer to the statistics of its last row, in place, blended by the reference `mix` -
-    so the skip connection and the onward path both see the result.  None records exactly the plan without it.
-
-    sag = (colsum_buf, workspace, row0, rows) (self-attention guidance, minsdtf_amd/sag.py): mid_block.attentions.0 also writes the
-    attention map of the rows row0 .. row0 + rows - 1 (Emitter.attentions' `colsum`: fp32 [rows][mh * mw], (mh, mw) =
-    unet_levels(h, w)[3]).  The mid block is never part of the shared prefix.  None records exactly the plain forward.
+              eps_out_f32, controls=None, control_taps=None, *, variant: UNetVariant = UNetVariant()) -> None:
+    """DiffusionModel graph (diffusion_model.py:184-279).  variant: how this forward differs from the plain one (UNetVariant).
 
     latent_f32: fp32 [latent_batch_mod][h][w][4] (sample b reads row b % latent_batch_mod);
     temb = (table, step_stride, batch_stride, {resblock: column}); eps_out_f32: fp32 [NB][h][w][4].
@@ -865,76 +932,19 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
     def temb_of(name):
         return (table.at(cols[name] * 4), sstride, bstride)
 
-    ref_layers = frozenset()
-    if reference is not None:
-        ref_layers, ref_latent, ref_mix = reference
-        ref_layers = frozenset(ref_layers)
-        if (not ref_layers and not adain) or ref_layers - set(PAG_LAYERS):
-            raise ValueError(f"emit_unet: reference layers {sorted(ref_layers)} (a non-empty subset of PAG_LAYERS, or empty next to adain sites)")
-        if NB < 2 or perturbed or region_attn or controls is not None or control_taps is not None:
-            raise ValueError("emit_unet: a reference row goes with at least one generated row and not with pag, regions or a ControlNet")
-    adain = frozenset(adain) if adain else frozenset()
-    if adain:
-        from .reference import ADAIN_SITES
-
-        if adain - {n for n, _gw in ADAIN_SITES}:
-            raise ValueError(f"emit_unet: unknown adain site(s) {sorted(adain - {n for n, _gw in ADAIN_SITES})}")
-        if reference is None or window is not None:   # (pag, regions and ControlNet residuals are refused with the reference row)
-            raise ValueError("emit_unet: adain goes with a reference row and not with pag, regions, a window or a ControlNet")
-
-    def site(x: Act, name: str) -> None:
-        """Reference AdaIN behind the call `name` that produced x, when that output is a selected site."""
-        if name in adain:
-            p.rec(ops.reference_adain, x=x.buf, ref=x.buf.at((NB - 1) * x.H * x.W * x.C * 2), mix=ref_mix, rows=NB - 1, hw=x.H * x.W,
-                  c=x.C, eps=1e-6, name=name + ".adain")
-
+    variant.check(NB, controls, control_taps)
     x = p.act(NB, h, w, 320)
-    gen = NB - 1 if reference is not None else NB   # the rows conv_in reads from latent_f32
+    gen = NB - 1 if variant.reference is not None else NB   # the rows conv_in reads from latent_f32
     p.rec(ops.conv_direct, x=latent_f32, w=e.W["conv_in.w"], bias=e.W["conv_in.b"], out=x.buf, batch=gen,
           in_batch_mod=latent_batch_mod, h_in=h, w_in=w, c_in=4, c_out=320, ksize=3, in_dtype=ops.OUT_F32,
           out_dtype=ops.OUT_BF16, name="conv_in")
-    if reference is not None:
-        p.rec(ops.conv_direct, x=ref_latent, w=e.W["conv_in.w"], bias=e.W["conv_in.b"], out=x.buf.at(gen * h * w * 320 * 2), batch=1,
+    if variant.reference is not None:
+        p.rec(ops.conv_direct, x=variant.reference[1], w=e.W["conv_in.w"], bias=e.W["conv_in.b"], out=x.buf.at(gen * h * w * 320 * 2), batch=1,
               in_batch_mod=1, h_in=h, w_in=w, c_in=4, c_out=320, ksize=3, in_dtype=ops.OUT_F32, out_dtype=ops.OUT_BF16,
               name="conv_in.reference")
     outputs: List[Act] = [x]
     # (conv_in itself stays on the whole batch: every row reads latent row b % latent_batch_mod, a 10-us launch whose output is skip 0)
-    shared = NB // latent_batch_mod if (SHARE_CFG_PREFIX and latent_batch_mod > 0 and NB % latent_batch_mod == 0) else 1
-    pag_layers = frozenset(pag_layers or ()) if perturbed else frozenset()
-    if pag_layers - set(PAG_LAYERS):
-        raise ValueError(f"emit_unet: unknown attention block(s) {sorted(pag_layers - set(PAG_LAYERS))}")
-    if PAG_LAYERS[0] in pag_layers:
-        # the first block's front is no longer identical across the copies: nothing is shared (exact either way - a sample's bits
-        # do not depend on its batch)
-        shared = 1
-    if reference is not None:
-        shared = 1   # the reference row is no copy of anything
-
-    win_levels = {}
-    if window is not None:
-        if perturbed or region_attn or reference is not None:
-            raise ValueError("emit_unet: window does not go with pag, regions or a reference row")
-        if window_depth not in (0, 1, 2):
-            raise ValueError(f"emit_unet: window_depth = {window_depth} (0, 1 or 2)")
-        for lvl in range(window_depth + 1):
-            for blk in [f"down_blocks.{lvl}.attentions.{r}" for r in range(2)] + [f"up_blocks.{3 - lvl}.attentions.{r}" for r in range(3)]:
-                win_levels[blk] = tuple(window)
-
-    def attn_kw(block: str, x: Act) -> dict:
-        """What Emitter.attentions takes for `block`, whose input is x, beyond the plain block."""
-        kw = dict(perturbed=perturbed if block in pag_layers else 0)
-        if region_attn:   # the weight plane of x's level
-            R, rows, planes = region_attn
-            kw.update(regions=R, region_rows=rows, region_w=planes[(x.H, x.W)])
-        if block in win_levels:
-            kw.update(window=win_levels[block])
-        elif block in ref_layers:
-            kw.update(reference=1, mix=ref_mix)
-        if sag is not None and block == "mid_block.attentions.0":
-            kw.update(colsum=sag)
-        return kw
-
-    x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared, attn_kw=attn_kw, site=site)
+    x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=variant.shared(NB, latent_batch_mod), variant=variant, NB=NB)
     p.mark("controls")   # everything above is independent of the ControlNet (its encoder may run beside it on another stream)
     if control_taps is not None:
         e_c, feats = control_taps
@@ -955,13 +965,13 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
             x = e.res_block((x, skip), name, ch, temb=temb_of(name), free_input=True)
             if lvl < 3:
                 blk = f"up_blocks.{ui}.attentions.{r}"
-                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, **attn_kw(blk, x))
-            site(x, blk if lvl < 3 else name)   # (the third call of a block is no site: the upsampler conv's output is)
+                x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, variant=variant.at(blk, x))
+            variant.adain_site(p, x, blk if lvl < 3 else name, NB)   # (the third call of a block is no site: the upsampler conv's output is)
         if lvl > 0:
             y = e.conv(x, f"up_blocks.{ui}.upsamplers.0.conv", ch, ksize=3, upsample=True)
             p.free(x)
             x = y
-            site(x, f"up_blocks.{ui}.upsamplers.0.conv")
+            variant.adain_site(p, x, f"up_blocks.{ui}.upsamplers.0.conv", NB)
     g = e.group_norm(x, "conv_norm_out", silu=True)
     p.free(x)
     if MFMA_CONV_OUT and "conv_out.m.w" in e.W:
@@ -977,7 +987,7 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
 def emit_sag_pass(e: Emitter, latent_f32, eps_f32, coef, coef_stride: int, num_steps: int, colsum, params, degraded_f32, B: int,
                   h: int, w: int, temb, ctx_kv, ctx_len: int, eps_out_f32) -> None:
     """The second, dependent half of a self-attention-guidance step (minsdtf_amd/sag.py), recorded behind the pass that wrote
-    `eps_f32` (its first B rows: the u rows, or the c rows of a job without guidance) and `colsum` (emit_unet's `sag`): ONE
+    `eps_f32` (its first B rows: the u rows, or the c rows of a job without guidance) and `colsum` (UNetVariant.sag): ONE
     msdx_sag_degrade launch builds the degraded latent fp32 [B][h][w][4] from the latent, those rows and the map - alpha_t / sigma_t
     from columns 0 / 1 of row *step_ptr of `coef`, taps and threshold from `params` - then the UNet runs on it, B rows over the
     first B rows of `ctx_kv`, into `eps_out_f32` (the d rows).  The step counter is read, not advanced."""
@@ -1029,8 +1039,7 @@ def emit_controlnet_features(e: Emitter, latent_f32, latent_batch_mod: int, NB: 
           out_dtype=ops.OUT_BF16, name="conv_in+hint")
     outputs: List[Act] = [x]
     # (the hint is tiled to both halves - emit_hintnet's copies - so conv_in + hint is the same in every copy of the batch too)
-    shared = NB // latent_batch_mod if (SHARE_CFG_PREFIX and latent_batch_mod > 0 and NB % latent_batch_mod == 0) else 1
-    x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=shared)
+    x = _emit_encoder(e, x, temb_of, ctx_kv, ctx_len, outputs, shared=UNetVariant().shared(NB, latent_batch_mod))
     outputs.append(x)
     assert len(outputs) == 13
     return outputs

@@ -263,7 +263,7 @@ class DiffusionModel(HipModel):
         reference = the attention blocks of a reference-only forward (predict_reference): the plan runs B + 1 rows, the last one the
         reference row read from `ref_latent`; `t_emb` and `context` carry its row last, `ref_mix` is fp32 [B]; eps keeps B rows.
         adain = the reference AdaIN sites of such a forward (reference.ADAIN_SITES); `reference` may then be an empty set.
-        window = (nh, nw, depth) of a HyperTile forward (predict_windowed): emit_unet's window / window_depth.
+        window = (nh, nw, depth) of a HyperTile forward (predict_windowed): engine.UNetVariant's window / window_depth.
         sag: the mid block's self-attention also writes the attention map of all B rows (predict_sag_map): io["sag_A"], fp32
         [B][mh * mw]."""
         h, w = self.h, self.w
@@ -301,18 +301,19 @@ class DiffusionModel(HipModel):
                 cstage.append((st, (B, hh, ww, ch)))
                 controls.append(st)
         eps = plan.alloc(NB * h * w * 4 * 4)
-        extra = dict(reference=(reference, ins["ref_latent"], ins["ref_mix"])) if reference is not None else {}
-        if adain:
-            extra["adain"] = frozenset(adain)
-        if window is not None:
-            extra = dict(window=(window[0], window[1]), window_depth=window[2])
-        sag_A = None
+        sag_A = sag_ws = None
         if sag:
             mh, mw = engine.unet_levels(h, w)[3]
             sag_A = plan.alloc(B * mh * mw * 4)
-            extra = dict(sag=(sag_A, plan.alloc(ops.colsum_workspace_floats(B, 8, mh * mw) * 4), 0, B))
-        engine.emit_unet(e, ins["latent"], B, NB, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls,
-                         pag_layers=pag_layers, perturbed=B if pag_layers else 0, region_attn=region_attn, **extra)
+            sag_ws = plan.alloc(ops.colsum_workspace_floats(B, 8, mh * mw) * 4)
+        # (every predict_* entry passes its own option alone; what does not go together is emit_unet's to refuse, not dropped here)
+        variant = engine.UNetVariant(
+            pag_layers=pag_layers, perturbed=B if pag_layers else 0, region_attn=region_attn,
+            reference=(reference, ins["ref_latent"], ins["ref_mix"]) if reference is not None else None,
+            adain=frozenset(adain) if adain else None,
+            window=window[:2] if window is not None else None, window_depth=window[2] if window is not None else 0,
+            sag=(sag_A, sag_ws, 0, B) if sag else None)
+        engine.emit_unet(e, ins["latent"], B, NB, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls, variant=variant)
         plan.finalize()
         bp = _BoundPlan(plan, self._use_graph)
         bp.io = {k: b.tensor(torch.float32, shapes[k]) for k, b in ins.items()}

@@ -273,7 +273,7 @@ class DenoiseEngine:
             if sag_here:
                 sag_ws = step.alloc(ops.colsum_workspace_floats(B, 8, mh * mw) * 4)
             engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps,
-                             **self._unet_keywords(tag, region_planes, sag_ws))
+                             variant=self._unet_variant(tag, region_planes, sag_ws))
             if sag_here:
                 step.free(sag_ws)
                 d_rows = _Ptr(self.eps.data_ptr() + (2 if self.cfg else 1) * B * n * 4)
@@ -281,9 +281,9 @@ class DenoiseEngine:
                                      self.sag_params, self.sag_latent, B, h, w, prep["table_u"], prep["kv_u"][tag], t, d_rows)
         return step
 
-    def _unet_keywords(self, tag: str, region_planes, sag_ws) -> dict:
-        """emit_unet's keywords for the pass `tag` beyond the plain forward's, every option adding its own.  The refusals (jobopts.REFUSED)
-        are what makes the contributions disjoint: pag, regions in attention mode, reference, hypertile and sag exclude each other."""
+    def _unet_variant(self, tag: str, region_planes, sag_ws) -> "engine.UNetVariant":
+        """How the pass `tag` differs from the plain forward, every option adding its own fields.  The refusals (jobopts.REFUSED) are
+        what makes the contributions disjoint: pag, regions in attention mode, reference, hypertile and sag exclude each other."""
         kw, B = {}, self.B
         if self.pag and tag != "uncond":   # the p rows are the last B rows of the pass that holds the conditional rows
             kw.update(pag_layers=self.pag, perturbed=B)
@@ -298,7 +298,7 @@ class DenoiseEngine:
             kw.update(window=self.hypertile[:2], window_depth=self.hypertile[2])
         if sag_ws is not None:   # this pass holds the u rows (the c rows without guidance) in its first B rows
             kw.update(sag=(self.sag_A, sag_ws, 0, B))
-        return kw
+        return engine.UNetVariant(**kw)
 
     def _build_tail(self, step, guidance, guidance_rescale, inpaint, tcd) -> "engine.Plan":
         """What follows the UNet in a step: the region combine, the guidance / sampler step, the tile consensus - recorded behind

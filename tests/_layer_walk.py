@@ -481,7 +481,7 @@ def walk_all(what, nb, h, w):
                 engine.emit_unet(e, T(), nb, nb, h, w, temb, kv, 77, T(), None)
             elif what == "unet_pag":   # the last row perturbed, in a 64x64-level block, the mid block and an up block
                 layers_ = (engine.PAG_LAYERS[1], "mid_block.attentions.0", engine.PAG_LAYERS[-1])
-                engine.emit_unet(e, T(), 1, nb, h, w, temb, kv, 77, T(), None, pag_layers=layers_, perturbed=1)
+                engine.emit_unet(e, T(), 1, nb, h, w, temb, kv, 77, T(), None, variant=engine.UNetVariant(pag_layers=layers_, perturbed=1))
             elif what == "unet_taps":  # ControlNet features -> zero convs into the skips (residual == out)
                 kv_c = engine.emit_context_kv(e, ctx, engine.ENCODER_ATTN_LAYERS, p)
                 feats = engine.emit_controlnet_features(e, T(), nb // 2, nb, h, w, (T(), 0, 0, engine.temb_columns(True)), kv_c, 77,

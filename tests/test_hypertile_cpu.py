@@ -313,7 +313,7 @@ def _walk(latent_mod, nb, hw=16, **kw):
         ctx = engine.Act(p.alloc(nb * 77 * 768 * 2), nb, 77, 1, 768)
         kv = engine.emit_context_kv(e, ctx, engine.UNET_ATTN_LAYERS, p)
         out.clear()
-        engine.emit_unet(e, LW._Tensor(), latent_mod, nb, hw, hw, (LW._Tensor(), 0, 0, engine.temb_columns(False)), kv, 77, LW._Tensor(), None, **kw)
+        engine.emit_unet(e, LW._Tensor(), latent_mod, nb, hw, hw, (LW._Tensor(), 0, 0, engine.temb_columns(False)), kv, 77, LW._Tensor(), None, variant=engine.UNetVariant(**kw))
     finally:
         engine.Plan.rec = orig
     return out
@@ -391,9 +391,9 @@ def test_window_is_not_combined():
     kv = {"b.transformer_blocks.0.attn2": (LW._Tensor(), LW._Tensor(), 80)}
     for kw in (dict(perturbed=1), dict(reference=1), dict(window=(3, 1)), dict(window=(1, 3)), dict(window=(0, 1))):
         with pytest.raises(ValueError, match="window"):
-            e.attentions(p.act(4, 16, 16, 320), "b", kv, 77, **{"window": (2, 2), **kw})
+            e.attentions(p.act(4, 16, 16, 320), "b", kv, 77, variant=engine.AttnVariant(**{"window": (2, 2), **kw}))
     with pytest.raises(ValueError, match="head size"):
-        e.attentions(p.act(4, 16, 16, 512), "b", kv, 77, window=(2, 2))
+        e.attentions(p.act(4, 16, 16, 512), "b", kv, 77, variant=engine.AttnVariant(window=(2, 2)))
 
 
 def test_every_windowed_launch_fits_its_buffers():
@@ -416,7 +416,7 @@ def test_every_windowed_launch_fits_its_buffers():
         kv = engine.emit_context_kv(e, ctx, engine.UNET_ATTN_LAYERS, p)
         recs.clear()
         engine.emit_unet(e, LW._Tensor(), 2, 4, 48, 64, (LW._Tensor(), 0, 0, engine.temb_columns(False)), kv, 77, LW._Tensor(), None,
-                         window=(3, 2), window_depth=2)
+                         variant=engine.UNetVariant(window=(3, 2), window_depth=2))
     finally:
         engine.Plan.rec = orig
     checked = 0

@@ -120,3 +120,45 @@ def test_defaults_key_and_unknown_names():
         sd._engine_key(1, 77, 77, 4, 7.5, 0.0, False, bogus=1)
     with pytest.raises(TypeError):
         _construct(bogus=1)
+
+
+def test_unet_variant_at_every_attention_block():
+    """engine.UNetVariant.at over the 16 attention blocks, each with its input Act at its level: which blocks an option touches."""
+    from minsdtf_amd import engine
+    from minsdtf_amd import weights as wtab
+    from minsdtf_amd.engine import AttnVariant, UNetVariant
+
+    levels = engine.unet_levels(SIZE, SIZE)
+
+    def level_of(block):
+        part, idx = block.split(".")[:2]
+        return 3 if part == "mid_block" else int(idx) if part == "down_blocks" else 3 - int(idx)
+
+    acts = {b: engine.Act(None, 4, *levels[level_of(b)], wtab.UNET_CH[level_of(b)]) for b in engine.PAG_LAYERS}
+    assert len(acts) == 16
+
+    def touched(variant):
+        return {b: variant.at(b, x) for b, x in acts.items() if variant.at(b, x) != AttnVariant()}
+
+    assert touched(UNetVariant()) == {}
+    some = {engine.PAG_LAYERS[1], MID}
+    assert touched(UNetVariant(pag_layers=some, perturbed=2)) == {b: AttnVariant(perturbed=2) for b in some}
+    assert touched(UNetVariant(pag_layers=some, perturbed=0)) == {}
+    for depth in (0, 1, 2):
+        got = touched(UNetVariant(window=[2, 2], window_depth=depth))
+        assert set(got) == {b for b in acts if level_of(b) <= depth} and len(got) == 5 * (depth + 1)
+        assert set(got.values()) == {AttnVariant(window=(2, 2))}
+    sag = (object(), object(), 0, 2)
+    assert touched(UNetVariant(sag=sag)) == {MID: AttnVariant(colsum=sag)}
+    planes = {lv: object() for lv in levels}
+    got = touched(UNetVariant(region_attn=(3, 2, planes)))
+    assert got == {b: AttnVariant(regions=3, region_rows=2, region_w=planes[(x.H, x.W)]) for b, x in acts.items()}
+    assert all(got[b].region_w is planes[levels[level_of(b)]] for b in acts)
+    # a block in the window levels and in the reference layers takes the window; the reference layers elsewhere stay
+    mix = object()
+    both = touched(UNetVariant(window=(2, 2), window_depth=0, reference=(frozenset(engine.PAG_LAYERS), object(), mix)))
+    assert all(both[b] == (AttnVariant(window=(2, 2)) if level_of(b) == 0 else AttnVariant(reference=1, mix=mix)) for b in acts)
+    assert touched(UNetVariant(reference=({MID}, object(), mix))) == {MID: AttnVariant(reference=1, mix=mix)}
+    for cls in (UNetVariant, AttnVariant):
+        with pytest.raises(TypeError):
+            cls(bogus=1)

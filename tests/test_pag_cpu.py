@@ -257,7 +257,7 @@ def _walk(latent_mod, nb, **kw):
         ctx = engine.Act(p.alloc(nb * 77 * 768 * 2), nb, 77, 1, 768)
         kv = engine.emit_context_kv(e, ctx, engine.UNET_ATTN_LAYERS, p)
         out.clear()
-        engine.emit_unet(e, _Tensor(), latent_mod, nb, 16, 16, (_Tensor(), 0, 0, engine.temb_columns(False)), kv, 77, _Tensor(), None, **kw)
+        engine.emit_unet(e, _Tensor(), latent_mod, nb, 16, 16, (_Tensor(), 0, 0, engine.temb_columns(False)), kv, 77, _Tensor(), None, variant=engine.UNetVariant(**kw))
     finally:
         engine.Plan.rec = orig
     return out

@@ -250,7 +250,7 @@ def _record(nb, hw, **kw):
         if "reference" in kw:
             kw["reference"] = (kw["reference"], ref_latent, mix)
         engine.emit_unet(e, LW._Tensor(), 2, nb, hw, hw, (LW._Tensor(), 0, 0, engine.temb_columns(False)), kv, 77, LW._Tensor(),
-                         kw.pop("controls", None), **kw)
+                         kw.pop("controls", None), variant=engine.UNetVariant(**kw))
     finally:
         engine.Plan.rec = orig
     return recs

@@ -340,7 +340,7 @@ def _walk(latent_mod, nb, **kw):
         ctx = engine.Act(p.alloc(nb * 77 * 768 * 2), nb, 77, 1, 768)
         kv = engine.emit_context_kv(e, ctx, engine.UNET_ATTN_LAYERS, p)
         out.clear()
-        engine.emit_unet(e, LW._Tensor(), latent_mod, nb, 16, 16, (LW._Tensor(), 0, 0, engine.temb_columns(False)), kv, 77, LW._Tensor(), None, **kw)
+        engine.emit_unet(e, LW._Tensor(), latent_mod, nb, 16, 16, (LW._Tensor(), 0, 0, engine.temb_columns(False)), kv, 77, LW._Tensor(), None, variant=engine.UNetVariant(**kw))
     finally:
         engine.Plan.rec = orig
     return out
@@ -412,7 +412,7 @@ def test_reference_is_not_combined():
     kv = {"b.transformer_blocks.0.attn2": (LW._Tensor(), LW._Tensor(), 80)}
     for kw in (dict(shared=2), dict(perturbed=1), dict(regions=2, region_rows=2, region_w=LW._Tensor()), dict(reference=2)):
         with pytest.raises(ValueError, match="reference"):
-            e.attentions(p.act(4, 8, 8, 640), "b", kv, 77, **{"reference": 1, **kw})
+            e.attentions(p.act(4, 8, 8, 640), "b", kv, 77, shared=kw.pop("shared", 1), variant=engine.AttnVariant(**{"reference": 1, **kw}))
 
 
 def test_every_new_launch_fits_its_buffers():
@@ -436,7 +436,7 @@ def test_every_new_launch_fits_its_buffers():
         recs.clear()
         mix, ref_latent = p.alloc(4 * 4), p.alloc(24 * 24 * 4 * 4)
         engine.emit_unet(e, LW._Tensor(), 2, 5, 24, 24, (LW._Tensor(), 0, 0, engine.temb_columns(False)), kv, 77, LW._Tensor(), None,
-                         reference=(frozenset(engine.PAG_LAYERS), ref_latent, mix))
+                         variant=engine.UNetVariant(reference=(frozenset(engine.PAG_LAYERS), ref_latent, mix)))
     finally:
         engine.Plan.rec = orig
     checked = 0

@@ -204,7 +204,7 @@ def _walk_unet(nb, h, w, R=0, rows=0, ctx_rows=None):
             wbuf = p.alloc(offs[-1] * 4)
             ra = (R, rows, {lv: wbuf.at(o * 4) for lv, o in zip(levels, offs)})
         n0 = len(out)
-        engine.emit_unet(e, T(), max(rows, 1) if R else nb, nb, h, w, temb, kv, 77, T(), None, region_attn=ra)
+        engine.emit_unet(e, T(), max(rows, 1) if R else nb, nb, h, w, temb, kv, 77, T(), None, variant=engine.UNetVariant(region_attn=ra))
     finally:
         engine.Plan.rec = orig
     return out[n0:], p
@@ -271,7 +271,7 @@ def test_attention_mode_plan_refuses_long_contexts():
     kv = engine.emit_context_kv(e, ctx, engine.UNET_ATTN_LAYERS, p)
     with pytest.raises(ValueError, match="context tokens"):
         engine.emit_unet(e, LW._Tensor(), 1, 1, 8, 8, (LW._Tensor(), 0, 0, engine.temb_columns(False)), kv, 154, LW._Tensor(), None,
-                         region_attn=(3, 1, {lv: LW._Tensor() for lv in engine.unet_levels(8, 8)}))
+                         variant=engine.UNetVariant(region_attn=(3, 1, {lv: LW._Tensor() for lv in engine.unet_levels(8, 8)})))
 
 
 # ---------------------------------------------------------------------------------------------------- argument checks

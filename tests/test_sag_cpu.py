@@ -200,7 +200,7 @@ def _sag_step(B, h, w, cfg=True, sampler=False):
         planes = p.alloc((3 if cfg else 2) * h * w * 4)
         ws = p.alloc(ops.colsum_workspace_floats(B, 8, mh * mw) * 4)
         build.first = len(p.recs)
-        engine.emit_unet(e, latent, B, NB, h, w, temb, kv, 77, eps, sag=(A, ws, 0, B))
+        engine.emit_unet(e, latent, B, NB, h, w, temb, kv, 77, eps, variant=engine.UNetVariant(sag=(A, ws, 0, B)))
         p.free(ws)
         engine.emit_sag_pass(e, latent, eps, coef, 8 if sampler else 4, 4, A, params, degraded, B, h, w, temb, kv, 77,
                              eps.at((2 if cfg else 1) * B * n * 4))
@@ -230,7 +230,7 @@ def test_sag_none_records_the_plain_plan():
         ctx = engine.Act(p.alloc(2 * 77 * 768 * 2), 2, 77, 1, 768)
         kv = engine.emit_context_kv(e, ctx, engine.UNET_ATTN_LAYERS, p)
         build.first = len(p.recs)
-        engine.emit_unet(e, T(), 2, 2, 8, 8, (T(), 0, 0, engine.temb_columns(False)), kv, 77, T(), None, sag=None)
+        engine.emit_unet(e, T(), 2, 2, 8, 8, (T(), 0, 0, engine.temb_columns(False)), kv, 77, T(), None, variant=engine.UNetVariant(sag=None))
 
     mine = _record(build)[0][build.first:]
     tail = plain[len(plain) - len(mine):]
@@ -314,7 +314,7 @@ def test_colsum_is_refused_where_it_cannot_run():
     def build(p, e, T):
         x = p.act(2, 8, 8, 320)   # head size 40
         e.attentions(x, "down_blocks.0.attentions.0", {"down_blocks.0.attentions.0.transformer_blocks.0.attn2": (T(), T(), 80)}, 77,
-                     colsum=(T(), T(), 0, 2))
+                     variant=engine.AttnVariant(colsum=(T(), T(), 0, 2)))
 
     with pytest.raises(ValueError, match="colsum"):
         _record(build)
@@ -322,7 +322,7 @@ def test_colsum_is_refused_where_it_cannot_run():
     def rows(p, e, T):
         x = p.act(2, 2, 2, 1280)
         e.attentions(x, "mid_block.attentions.0", {"mid_block.attentions.0.transformer_blocks.0.attn2": (T(), T(), 80)}, 77,
-                     colsum=(T(), T(), 1, 2))
+                     variant=engine.AttnVariant(colsum=(T(), T(), 1, 2)))
 
     with pytest.raises(ValueError, match="colsum"):
         _record(rows)

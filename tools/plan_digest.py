@@ -1,10 +1,14 @@
 """Digests of what a DenoiseEngine records, one line per job kind: the check that a change of the plumbing moved no launch.
 
-Run this same file once in a checkout of each commit (it uses only what both have: DenoiseEngine's keyword constructor, the
-engine.Plan.rec hook and the stand-ins of tests/_layer_walk.py) and compare the lines:
+Run this same file once in a checkout of each commit (it uses only what both have: DenoiseEngine's keyword constructor,
+DiffusionModel._build's signature, the engine.Plan.rec hook and the stand-ins of tests/_layer_walk.py) and compare the lines:
 
     python tools/plan_digest.py          # on the CPU: "<kind>  <recorded launches>  <sha256 over the records>"
+    python tools/plan_digest.py --unfolded   # the same with engine.LN_FOLD = engine.FF_PROJ_FOLD = False: the layer_norm routes and
+                                             # the unfused attn2 route (the stand-in weights otherwise make every fold "exist")
     python tools/plan_digest.py --run    # on the GPU: "<kind>  <seconds>  <sha256 of the result latent>"
+
+The CPU table has the job kinds first, then "model <kind>": the host loop's twin, DiffusionModel._build at batch 2 and 77 tokens.
 
 A record holds the index of its plan (in the order the plans record their first launch), the op's name, every scalar keyword,
 for Buf / BufView / Act operands the arena offset and the bytes available from there, and for operands that are engine tensors
@@ -162,6 +166,24 @@ def cpu_kinds():
             ("controlnet two passes", eng(tu=154, control=True))]
 
 
+def model_kinds():
+    """(kind, function that builds its bound plan through DiffusionModel._build), in the order of the table."""
+    from minsdtf_amd.models import DiffusionModel
+
+    def model(size=8, **kw):
+        def build():
+            m = DiffusionModel.__new__(DiffusionModel)
+            m.h = m.w = size
+            m.device, m._W, m._use_graph = torch.device("cpu"), stand_ins()[0]._W, False
+            return m._build(2, 77, kw.pop("with_controls", False), **kw)
+        return build
+
+    return [("model plain", model()), ("model with_controls", model(with_controls=True)), ("model pag mid", model(pag_layers={MID})),
+            ("model regions 2", model(regions=2)), ("model reference mid", model(reference=(MID,))),
+            ("model adain alone", model(reference=(), adain=(ADAIN_MID,))), ("model hypertile 2x2", model(size=16, window=(2, 2, 0))),
+            ("model sag", model(sag=True))]
+
+
 # ------------------------------------------------------------------------------------------------------------ the latents (GPU)
 def gpu_kinds(dev):
     """(kind, function that runs its job and returns the latent), in the order of the table."""
@@ -220,10 +242,15 @@ def gpu_kinds(dev):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--run", action="store_true", help="run the jobs on the GPU and hash the result latents")
+    ap.add_argument("--unfolded", action="store_true", help="record with engine.LN_FOLD = engine.FF_PROJ_FOLD = False")
     ap.add_argument("--save", help="--run: also keep the latents in this .npz (to compare two runs by their largest difference)")
     args = ap.parse_args()
     if not args.run:
-        for kind, build in cpu_kinds():
+        if args.unfolded:
+            from minsdtf_amd import engine
+
+            engine.LN_FOLD = engine.FF_PROJ_FOLD = False
+        for kind, build in cpu_kinds() + model_kinds():
             n, sha = record(build)
             print(f"{kind:32s} {n:6d}  {sha}", flush=True)
         return
