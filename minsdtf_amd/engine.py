@@ -913,7 +913,7 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
 
 
 def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w: int, temb, ctx_kv, ctx_len: int,
-              eps_out_f32, controls=None, control_taps=None, *, variant: UNetVariant = UNetVariant()) -> None:
+              eps_out_f32, controls=None, control_taps=None, *, variant: UNetVariant = UNetVariant(), control_units=None) -> None:
     """DiffusionModel graph (diffusion_model.py:184-279).  variant: how this forward differs from the plain one (UNetVariant).
 
     latent_f32: fp32 [latent_batch_mod][h][w][4] (sample b reads row b % latent_batch_mod);
@@ -925,14 +925,19 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
         skip as its epilogue residual and the skip's buffer as its output: skip += zero_conv(feature) in one launch, summed
         in fp32 — the 13 elementwise adds do not exist;
       controls = 13 fp32 buffers [NB][h_i][w_i][c_i] handed over the model boundary (predict_on_batch): one
-        add-and-round launch each."""
+        add-and-round launch each;
+      control_units = (scales, num_steps, rows_u, [control_taps of unit 0, of unit 1, ...]): a job with ControlNet units
+        (minsdtf_amd/control.py).  Every unit's 13 zero convs run HERE without the residual, into fp32 temporaries, with the
+        tile and split-K configuration the fused form takes (tuning.lookup reads the shape, not the output type), and ONE
+        msdc_control_combine launch adds them to the 13 skips, each scaled by row *step_ptr of `scales` (fp32
+        [num_steps][units][13][2]: column 0 for the first rows_u rows, the unconditional ones, column 1 behind them)."""
     p = e.p
     table, sstride, bstride, cols = temb
 
     def temb_of(name):
         return (table.at(cols[name] * 4), sstride, bstride)
 
-    variant.check(NB, controls, control_taps)
+    variant.check(NB, controls, control_taps if control_units is None else control_units)
     x = p.act(NB, h, w, 320)
     gen = NB - 1 if variant.reference is not None else NB   # the rows conv_in reads from latent_f32
     p.rec(ops.conv_direct, x=latent_f32, w=e.W["conv_in.w"], bias=e.W["conv_in.b"], out=x.buf, batch=gen,
@@ -953,6 +958,25 @@ def emit_unet(e: Emitter, latent_f32, latent_batch_mod: int, NB: int, h: int, w:
             assert (o.B, o.H, o.W, o.C) == (f.B, f.H, f.W, f.C)
             e_c.conv(f, f"zero_convs.{i}", o.C, ksize=1, residual=o, out=o)
             p.free(f)
+    elif control_units is not None:
+        scales, num_steps, rows_u, unit_taps = control_units
+        skips = outputs + [x]
+        assert len(skips) == 13 and 1 <= len(unit_taps) <= 3 and 0 <= rows_u <= NB
+        resid = []
+        for n, (e_c, feats) in enumerate(unit_taps):
+            assert len(feats) == 13
+            rs = []
+            for i, (o, f) in enumerate(zip(skips, feats)):
+                assert (o.B, o.H, o.W, o.C) == (f.B, f.H, f.W, f.C)
+                rs.append(e_c.conv(f, f"unit{n}.zero_convs.{i}" if n else f"zero_convs.{i}", o.C, ksize=1, out_dtype=ops.OUT_F32,
+                                   wkey=f"zero_convs.{i}"))
+                p.free(f)
+            resid.append(rs)
+        p.rec(ops.control_combine, skips=[o.buf for o in skips], resid=[[r.buf for r in rs] for rs in resid],
+              counts=[o.H * o.W * o.C for o in skips], scales=scales, step_ptr=e.step_ptr, rows=NB, rows_u=rows_u,
+              num_steps=num_steps, name="control_combine")
+        for rs in resid:
+            p.free(*rs)
     elif controls is not None:
         assert len(outputs) == 12 and len(controls) == 13
         for i, (o, c) in enumerate(zip(outputs + [x], controls)):

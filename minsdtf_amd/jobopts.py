@@ -3,7 +3,7 @@ a parsed job description means ("Where a job option lives")."""
 from dataclasses import dataclass
 from typing import FrozenSet, Optional, Tuple
 
-from . import hypertile as hypertile_mod, reference as reference_mod, regions as regions_mod, samplers as smp
+from . import control as control_mod, hypertile as hypertile_mod, reference as reference_mod, regions as regions_mod, samplers as smp
 from .engine import PAG_LAYERS
 
 # job kind -> (what it is, the arguments and then the states it cannot be combined with, in the order the error names them)
@@ -35,9 +35,11 @@ _ENGINE_SENTENCE = {
 }
 
 
-def job_options(sampler=None, regions=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None) -> dict:
-    """_engine's option keywords of a job from its parsed descriptions (None: the job has none): only what the job asks for."""
-    out = dict(sampler=sampler and sampler.name, pag=pag and pag.key, hypertile=hypertile, sag=sag and True, dynthresh=dynthresh and True)
+def job_options(sampler=None, regions=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None) -> dict:
+    """_engine's option keywords of a job from its parsed descriptions (None: the job has none): only what the job asks for.
+    `control`: the parsed units of control.parse - the engine is built for their number only."""
+    out = dict(sampler=sampler and sampler.name, pag=pag and pag.key, hypertile=hypertile, sag=sag and True, dynthresh=dynthresh and True,
+               control_units=control and len(control))
     if regions is not None:   # (the base prompt counts when it is evaluated)
         out.update(regions=regions.count, region_mode=regions.mode)
     if reference is not None:
@@ -58,6 +60,7 @@ class EngineOptions:
     hypertile: Optional[Tuple[int, ...]] = None      # (nh, nw, depth) of a HyperTile job
     sag: bool = False                                # self-attention guidance
     dynthresh: bool = False                          # dynamic thresholding
+    control_units: int = 0                           # the number of ControlNet units of a job with control= (minsdtf_amd/control.py)
 
     @classmethod
     def of(cls, **opts) -> "EngineOptions":
@@ -68,7 +71,7 @@ class EngineOptions:
                    region_mode=o.region_mode if regions or o.region_mode not in regions_mod.MODES else "latent",   # (an unknown mode stays, for check() to name)
                    pag=frozenset(o.pag) if o.pag else None, reference=frozenset(o.reference or ()) if (o.reference or adain) else None,
                    adain=adain, hypertile=tuple(int(v) for v in ht) if ht is not None and len(ht) == 3 else ht,   # (else as given, for check())
-                   sag=bool(o.sag), dynthresh=bool(o.dynthresh))
+                   sag=bool(o.sag), dynthresh=bool(o.dynthresh), control_units=int(o.control_units))
 
     def key(self) -> tuple:
         """What the options add to an engine's key behind the UNet-size part: what the plans depend on, nothing a call uploads."""
@@ -80,7 +83,8 @@ class EngineOptions:
         if self.reference is not None:   # (with reference AdaIN the site set too, behind the blocks - which may then be none)
             key += (("reference", tuple(sorted(self.reference))) + ((("adain",) + tuple(sorted(self.adain)),) if self.adain else ()),)
         key += ((("hypertile",) + self.hypertile,) if self.hypertile else ()) + ((("sag",),) if self.sag else ())
-        return key + ((("dynthresh",),) if self.dynthresh else ())
+        key += (("dynthresh",),) if self.dynthresh else ()
+        return key + ((("control", self.control_units),) if self.control_units else ())
 
     def check(self, h: int, w: int, B: int, guidance: float, control: bool, inpaint: bool, tcd: bool, streams) -> None:
         """ValueError for what an engine of batch B at h x w refuses: each kind's own checks, then its exclusions, read from REFUSED."""
@@ -126,3 +130,6 @@ class EngineOptions:
             exclusive("hypertile")
         exclusive("sag", self.sag)
         exclusive("dynamic_threshold", self.dynthresh, also=not guidance > 0.0)
+        # control units exclude nothing a ControlNet job is not already excluded from (the rows above name it): no REFUSED row
+        if self.control_units and not (1 <= self.control_units <= control_mod.MAX_UNITS and control):
+            raise ValueError(f"control: {self.control_units} unit(s) (1 .. {control_mod.MAX_UNITS}, on an engine with a ControlNet)")

@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
-from . import _lib, _lib_dynthresh, _lib_ext
+from . import _lib, _lib_control, _lib_dynthresh, _lib_ext
 from ._lib import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, OUT_BF16, OUT_F32, OUT_U8  # noqa: F401
 
 
@@ -346,6 +346,35 @@ def dynamic_threshold(*, eps, out, scales, params, batch, h, w, num_steps, step_
     a.eps, a.out, a.scales, a.step_ptr, a.params = _p(eps), _p(out), _p(scales), _p(step_ptr), _p(params)
     a.batch, a.h, a.w, a.num_steps = int(batch), int(h), int(w), int(num_steps)
     return Call(lib.msdt_dynamic_threshold, (C.byref(a),), name, keep=a, check=_lib_dynthresh.check)
+
+
+# ---- the ControlNet-units library (include/minsdtf_hip_control.h, minsdtf_amd/_lib_control.py) -------------------------------------
+def control_chunk_prefix(counts) -> list:
+    """MsdcControlCombine.chunk_prefix of the 13 per-row element counts: the workgroups of a row in front of every tap, then all."""
+    out = [0]
+    for n in counts:
+        out.append(out[-1] + (int(n) + _lib_control.CHUNK - 1) // _lib_control.CHUNK)
+    return out
+
+
+def control_combine(*, skips, resid, counts, scales, rows, rows_u, num_steps, step_ptr=None, name="control_combine") -> Call:
+    """msdc_control_combine: skip_k[b] = bf16(fp32(skip_k[b]) + sum_n s_n * resid[n][k][b]), one fmaf per unit in unit order, over the 13
+    taps of one UNet pass in ONE launch (minsdtf_amd/control.py).  skips: 13 bf16 [rows][counts[k]] (in place); resid: 1 .. 3 lists of
+    13 fp32 [rows][counts[k]]; scales fp32 [num_steps][len(resid)][13][2] (row *step_ptr; column 0 for the rows < rows_u, else 1)."""
+    lib = _lib_control.load()
+    T = _lib_control.TAPS
+    if len(skips) != T or len(counts) != T or not 1 <= len(resid) <= _lib_control.MAX_UNITS or any(len(r) != T for r in resid):
+        raise ValueError(f"control_combine: {len(skips)} skips, {len(counts)} counts, {[len(r) for r in resid]} residuals "
+                         f"({T} of each, 1 .. {_lib_control.MAX_UNITS} units)")
+    a = _lib_control.MsdcControlCombine()
+    for k in range(T):
+        a.skip[k], a.count[k] = _p(skips[k]), int(counts[k])
+        for n, r in enumerate(resid):
+            a.resid[n][k] = _p(r[k])
+    a.chunk_prefix[:] = control_chunk_prefix(counts)
+    a.scales, a.step_ptr = _p(scales), _p(step_ptr)
+    a.rows, a.rows_u, a.units, a.num_steps = int(rows), int(rows_u), len(resid), int(num_steps)
+    return Call(lib.msdc_control_combine, (C.byref(a),), name, keep=a, check=_lib_control.check)
 
 
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:

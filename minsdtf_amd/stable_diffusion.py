@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib, engine, ops
+from . import control as control_mod
 from . import hires as hires_mod
 from . import dynthresh as dynthresh_mod
 from . import hypertile as hypertile_mod
@@ -77,15 +78,23 @@ class DenoiseEngine:
 
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
-                 use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False, **options):
-        """`options`: the fields of jobopts.EngineOptions as a caller gives them; kept as `options` and each as its own attribute."""
+                 use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
+                 control_nets=(), **options):
+        """`options`: the fields of jobopts.EngineOptions as a caller gives them; kept as `options` and each as its own attribute.
+        `control_nets`: the (ControlNet, HintNet) pairs of the units behind the first of an engine built with control_units = N -
+        model objects, not options: N - 1 of them (unit 0 is `control_net` / `hint_net`)."""
         unet._require_weights()
         self.unet, self.B, self.num_steps = unet, B, num_steps
         self.h, self.w = unet.h, unet.w
         self.options = EngineOptions.of(**options)
         self.options.check(self.h, self.w, B, guidance, control_net is not None, inpaint, tcd, streams)   # (before anything is allocated)
-        # self.sampler, .tiled, .regions, .region_mode, .pag, .reference, .adain, .hypertile, .sag, .dynthresh: the fields, as they are
+        # self.sampler, .tiled, .regions, .region_mode, .pag, .reference, .adain, .hypertile, .sag, .dynthresh, .control_units: the
+        # fields, as they are
         vars(self).update(vars(self.options))
+        self.control_nets = [(control_net, hint_net)] + [tuple(pair) for pair in control_nets] if control_net is not None else []
+        if len(self.control_nets) != max(self.control_units, 1 if control_net is not None else 0):
+            raise ValueError(f"control: an engine of {self.control_units} unit(s) takes {max(self.control_units - 1, 0)} further "
+                             f"(ControlNet, HintNet) pair(s) as control_nets, got {len(tuple(control_nets))}")
         self.region_attn = self.region_mode == "attention"   # ("latent" without regions)
         if self.reference is not None and guidance > 0.0 and t_cond != t_uncond:
             raise ValueError("reference_only: the negative prompt must have the conditional context's token length "
@@ -182,6 +191,11 @@ class DenoiseEngine:
         ctx_kv_u, ctx_kv_c = {}, {}
         e_c = None
         table_c = total_c = None
+        # control units (minsdtf_amd/control.py): every unit behind the first has its own time-embedding table, context K/V and hint,
+        # recorded behind unit 0's; a unit on the ControlNet of a unit in front of it (another picture, the same weights) shares
+        # that unit's table and K/V
+        further = self.control_nets[1:]
+        e_cn, tables_cn, kv_cn = [], [], [{} for _ in further]
         if self.has_control:
             control_net._require_weights()
             hint_net._require_weights()
@@ -189,6 +203,18 @@ class DenoiseEngine:
             total_c = sum(c for _, c in engine.resblock_names(True))
             table_c = prep_t.alloc(num_steps * total_c * 4)
             engine.emit_time_embedding(engine.Emitter(prep_t, control_net._W), self.temb_in, num_steps, table_c, encoder_only=True)
+            for n, (cn, hn) in enumerate(further):
+                cn._require_weights()
+                hn._require_weights()
+                same = [m for m in range(n + 1) if self.control_nets[m][0] is cn]   # (unit m, in front of unit n + 1)
+                if same:
+                    e_cn.append(None)
+                    tables_cn.append(table_c if same[0] == 0 else tables_cn[same[0] - 1])
+                    kv_cn[n] = ctx_kv_c if same[0] == 0 else kv_cn[same[0] - 1]
+                    continue
+                e_cn.append(engine.Emitter(prep, cn._W))
+                tables_cn.append(prep_t.alloc(num_steps * total_c * 4))
+                engine.emit_time_embedding(engine.Emitter(prep_t, cn._W), self.temb_in, num_steps, tables_cn[-1], encoder_only=True)
         for (_row0, nb, t, tag) in passes:
             if self.region_attn and tag != "uncond":   # context rows, not UNet rows: the B conditional rows read R * B contexts
                 nb = nb + (self.regions - 1) * B
@@ -199,8 +225,13 @@ class DenoiseEngine:
             ctx_kv_u[tag] = engine.emit_context_kv(e_u, c16, engine.UNET_ATTN_LAYERS, prep)
             if self.has_control:
                 ctx_kv_c[tag] = engine.emit_context_kv(e_c, c16, engine.ENCODER_ATTN_LAYERS, prep)
+                for n, e_n in enumerate(e_cn):
+                    if e_n is not None:
+                        kv_cn[n][tag] = engine.emit_context_kv(e_n, c16, engine.ENCODER_ATTN_LAYERS, prep)
         self.hint_img = None
+        self.hint_imgs_further: List[torch.Tensor] = []
         hint_act = None
+        hints_cn = []
         if self.has_control:
             # hint computed once per image batch (stable_diffusion.py:427-441), tiled to both halves
             nb_max = max(nb for (_r, nb, _t, _g) in passes)
@@ -208,6 +239,13 @@ class DenoiseEngine:
             e_h = engine.Emitter(prep, hint_net._W)
             hint_act = prep.act(nb_max, h, w, 320)
             engine.emit_hintnet(e_h, self.hint_img, B, 8 * h, 8 * w, hint_act, copies=nb_max // B)
+            for _cn, hn in further:   # every further unit: its HintNet on its own hint buffer
+                img = torch.zeros(B, 8 * h, 8 * w, 3, dtype=torch.float32, device=dev)
+                self.hint_imgs_further.append(img)
+                hints_cn.append(prep.act(nb_max, h, w, 320))
+                engine.emit_hintnet(engine.Emitter(prep, hn._W), img, B, 8 * h, 8 * w, hints_cn[-1], copies=nb_max // B)
+        cols_c = engine.temb_columns(True)
+        self._units_prep = [dict(table=(t, total_c, 0, cols_c), kv=kv, hint=hi) for t, kv, hi in zip(tables_cn, kv_cn, hints_cn)]
         prep_t.finalize()
         prep.finalize()
         self.prep, self.prep_t = prep, prep_t
@@ -241,6 +279,8 @@ class DenoiseEngine:
             self.region_w = torch.zeros(offs[-1], dtype=torch.float32, device=dev)
             region_planes = {lv: _Ptr(self.region_w.data_ptr() + o * 4) for lv, o in zip(levels, offs)}
         self.pag_w = torch.zeros(2, h, w, dtype=torch.float32, device=dev) if self.pag else None
+        # control_units (N, or 0): the per-step scale table of the N units, fp32 [num_steps][N][13][2] (control.table), a per-call upload
+        self.cn_scales = torch.zeros(self.num_steps, self.control_units, 13, 2, dtype=torch.float32, device=dev) if self.control_units else None
         self.branches = []
         step = None
         # ControlNet beside the UNet's down path: its encoder reads the same latent and is independent of the UNet until the
@@ -255,7 +295,9 @@ class DenoiseEngine:
                 self.branches.append(step)
                 s_u = engine.Emitter(step, unet._W, step_ptr=self.step_ptr)
                 s_c = engine.Emitter(step, control_net._W, step_ptr=self.step_ptr) if self.has_control else None
+                s_cn = [engine.Emitter(step, cn._W, step_ptr=self.step_ptr) for cn, _hn in self.control_nets[1:]]
             taps = None
+            units = None
             if self.has_control:
                 # ControlNet encoder first; its 13 zero convs run inside the UNet plan, fused with the residual adds
                 hint_nb = engine.Act(prep["hint"].buf, nb, h, w, 320)  # first nb rows of the tiled hint
@@ -265,6 +307,17 @@ class DenoiseEngine:
                     s_cf = engine.Emitter(self.cn_plan, control_net._W, step_ptr=self.step_ptr)
                 feats = engine.emit_controlnet_features(s_cf, self.latent, B, nb, h, w, prep["table_c"], prep["kv_c"][tag], t, hint_nb)
                 taps = (s_c, feats)
+            if self.control_units:
+                # one encoder per unit, where unit 0's runs (beside the UNet's down path, or in line); their zero convs and the ONE
+                # msdc_control_combine run inside the UNet plan, the scales read from row *step_ptr of `cn_scales`
+                unit_taps = [taps]
+                for (cn, _hn), s_n, up in zip(self.control_nets[1:], s_cn, self._units_prep):
+                    s_nf = engine.Emitter(self.cn_plan, cn._W, step_ptr=self.step_ptr) if overlap else s_n
+                    feats = engine.emit_controlnet_features(s_nf, self.latent, B, nb, h, w, up["table"], up["kv"][tag], t,
+                                                            engine.Act(up["hint"].buf, nb, h, w, 320))
+                    unit_taps.append((s_n, feats))
+                rows_u = {"both": B, "uncond": nb, "cond": 0}[tag]
+                taps, units = None, (self.cn_scales, self.num_steps, rows_u, unit_taps)
             eps_view = _Ptr(self.eps.data_ptr() + row0 * n * 4)
             if self.reference is not None:   # x_r of this step first, then the forward whose last row reads it
                 step.rec(ops.reference_latent, z=self.ref_z, noise=self.ref_noise, coef=self.ref_coef, step_ptr=self.step_ptr,
@@ -273,7 +326,7 @@ class DenoiseEngine:
             if sag_here:
                 sag_ws = step.alloc(ops.colsum_workspace_floats(B, 8, mh * mw) * 4)
             engine.emit_unet(s_u, self.latent, B, nb, h, w, prep["table_u"], prep["kv_u"][tag], t, eps_view, control_taps=taps,
-                             variant=self._unet_variant(tag, region_planes, sag_ws))
+                             variant=self._unet_variant(tag, region_planes, sag_ws), **({} if units is None else dict(control_units=units)))
             if sag_here:
                 step.free(sag_ws)
                 d_rows = _Ptr(self.eps.data_ptr() + (2 if self.cfg else 1) * B * n * 4)
@@ -493,7 +546,7 @@ class DenoiseEngine:
 
     def prepare(self, contexts: Dict[str, np.ndarray], noise: np.ndarray, scheduler: Scheduler, timesteps,
                 start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None,
-                regions=None, pag_scale=None, reference=None, sag=None, dynamic_threshold=None) -> None:
+                regions=None, pag_scale=None, reference=None, sag=None, dynamic_threshold=None, control=None) -> None:
         """Upload the per-call inputs and run the preparation plan.  Every array may be a host array or a (device) tensor.
         noise = None: the start latent is already in `self.latent` (written there by stream-ordered device work queued before
         this call: the hand-off of a hires job), nothing is uploaded for it.
@@ -512,7 +565,24 @@ class DenoiseEngine:
         planes of the combine (sag.weights, k from the scale and the engine's guidance in float64) are per-call uploads too.
         dynamic_threshold = the dynthresh.Resolved (or DynThreshSpec / dict) of an engine built with dynthresh=True: the scale table
         of the executed steps (dynthresh.scales over num_steps - start_index steps from the engine's guidance, rounded once to fp32,
-        in rows start_index ..) and the 32 bytes of dynthresh.params are per-call uploads too."""
+        in rows start_index ..) and the 32 bytes of dynthresh.params are per-call uploads too.
+        control = (table, hints) of an engine built with control_units = N: the scale table fp32 [num_steps][N][13][2] (control.table
+        over this engine's num_steps: its rows are the step counter's, whatever `start_index` is) and the N - 1 conditioning
+        pictures of the further units, each like `hint_image`, are per-call uploads too: weights, ranges and modes re-record nothing."""
+        if (control is None) != (self.cn_scales is None):
+            raise ValueError("prepare: `control` goes with an engine built with control_units=N, and only with one")
+        if self.cn_scales is not None:
+            tab, hints = control
+            tab = _f32_tensor(tab)
+            if tuple(tab.shape) != tuple(self.cn_scales.shape) or len(hints) != len(self.hint_imgs_further):
+                raise ValueError(f"prepare: control table of shape {tuple(tab.shape)} with {len(hints)} further hint(s), this engine's "
+                                 f"are {tuple(self.cn_scales.shape)} and {len(self.hint_imgs_further)}")
+            self.cn_scales.copy_(tab)
+            for dst, hi in zip(self.hint_imgs_further, hints):
+                hi = _f32_tensor(hi)
+                if hi.shape[0] != self.B:
+                    hi = hi.repeat(self.B // hi.shape[0], 1, 1, 1)
+                dst.copy_(hi)
         if (dynamic_threshold is None) != (self.dt_params is None):
             raise ValueError("prepare: `dynamic_threshold` goes with an engine built with dynthresh=True, and only with one")
         if self.dt_params is not None:
@@ -666,7 +736,9 @@ class StableDiffusionBase:
         regional prompting, `prompt` being the base prompt; ``pag``: None, or a pag.PagSpec / dict for perturbed-attention
         guidance; ``reference_only``: None, or a reference.ReferenceSpec / dict for reference-only control; ``hypertile``: None, or a
         hypertile.HypertileSpec / dict for windowed self-attention; ``sag``: None, or a sag.SagSpec / dict for self-attention guidance;
-        ``dynamic_threshold``: None, or a dynthresh.DynThreshSpec / dict for dynamic thresholding (see generate_image)."""
+        ``dynamic_threshold``: None, or a dynthresh.DynThreshSpec / dict for dynamic thresholding; ``control`` (through **kw, with
+        ``control_net_image``): None, or one control.ControlUnit / dict or a list of them - weight, start / end, mode and further
+        ControlNets (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
@@ -678,6 +750,7 @@ class StableDiffusionBase:
     def image_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
                        reference_image_strength=0.8, guidance_rescale=0.7, callback=None, **kw):
+        """Reference :111-139.  ``control`` (through **kw, with ``control_net_image``): the ControlNet units of generate_image."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
@@ -689,7 +762,7 @@ class StableDiffusionBase:
                 embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
                 reference_image_strength=0.8, inpaint_mask=None, mask_blur_strength=None, guidance_rescale=0.7,
                 callback=None, **kw):
-        """Reference :141-175."""
+        """Reference :141-175.  ``control`` (through **kw, with ``control_net_image``): the ControlNet units of generate_image."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
@@ -906,7 +979,8 @@ class StableDiffusionBase:
                        diffusion_noise=None, seed=None, negative_embedding=None, control_net_image=None, inpaint_mask=None,
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
                        callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None,
-                       tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, sag=None, dynamic_threshold=None):
+                       tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, sag=None, dynamic_threshold=None,
+                       control=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
@@ -974,7 +1048,21 @@ class StableDiffusionBase:
         as it is - so `guidance_rescale` is NOT applied to such a job.  The two scales may move over the steps (``cfg_mode``,
         ``mimic_mode``: dynthresh.MODES); a plane without spread keeps its plain prediction.  Works with every sampler, with
         ``hires`` (both passes, each schedule over its own executed steps), ``regions``, ``pag``, ``sag``, ``hypertile``,
-        ``reference_only``, shard_batch and host_loop=True; the engine is keyed by the fact only."""
+        ``reference_only``, shard_batch and host_loop=True; the engine is keyed by the fact only.
+        ``control`` (with ``control_net_image``; one control.ControlUnit or dict {"weight": 1.0, "start": 0.0, "end": 1.0, "mode":
+        "balanced"}, or a list of 1 .. control.MAX_UNITS of them): ControlNet units.  Unit 0 is the pipeline's own ControlNet on
+        ``control_net_image``; every further unit carries its own ``image`` and ``path`` (another ControlNet checkpoint, loaded once
+        and kept on the pipeline; None: the pipeline's own, on this picture) or ``models`` = (ControlNet, HintNet).  ``weight`` (one
+        float >= 0 or 13, one per residual) scales the unit's residuals, ``start`` / ``end`` bound the share of the steps it acts on
+        (diffusers' rule), ``mode`` is "balanced", "prompt" (soft injection: residual k times 0.825 ** (12 - k)) or "control" (that,
+        on the conditional half only).  Every unit's 13 zero convs write fp32 and ONE msdc_control_combine launch per UNet pass adds
+        them to the skips, the scales read from a per-step device table - so weights, ranges and modes are per-call uploads and the
+        engine is keyed by the number of units alone.  Works with whatever a ControlNet job works with: every sampler, a TCD pipeline,
+        image_to_image, inpainting, denoise_streams = 2, a negative prompt of another length, shard_batch and host_loop=True.
+        ``control`` = None is the job as it was, bit for bit."""
+        cu = control_mod.parse(control)   # (ValueError for a bad description)
+        if cu is not None and control_net_image is None:
+            raise ValueError("control: the units scale the ControlNet of `control_net_image`, which is missing")
         given = dict(tiled=tiled, hires=hires, control_net_image=control_net_image, reference_image=reference_image,
                      inpaint_mask=inpaint_mask, regions=regions, pag=pag, reference_only=reference_only, hypertile=hypertile)
         dt = dynthresh_mod.parse(dynamic_threshold)   # (ValueError for a bad description)
@@ -1035,7 +1123,7 @@ class StableDiffusionBase:
             raise ValueError(f"sampler={sampler!r} on a TCD pipeline (active_tcd=True): the TCD sampler is the only one it runs")
         # what the job's engines are built with, built here once.  A tiled or hires job takes all of it too: every option but the sampler,
         # dynthresh and (hires, second pass only) the windows is refused with those two - its REFUSED row names `tiled` / `hires`
-        engine_opts = job_options(sampler=spec, regions=reg, pag=pg, reference=ref, hypertile=ht_key, sag=sg, dynthresh=dt)
+        engine_opts = job_options(sampler=spec, regions=reg, pag=pg, reference=ref, hypertile=ht_key, sag=sg, dynthresh=dt, control=cu)
         B = batch_size
         context = self._batch_of(encoded_text, B, 2)
         unconditional_context = self._negative_context(negative_prompt, negative_embedding, B)
@@ -1080,6 +1168,13 @@ class StableDiffusionBase:
             start_latent = sched.entry_latent(start_index, encoded, noise)
         hint = self._hint_batch(control_net_image, B)
         g, phi = float(unconditional_guidance_scale), float(guidance_rescale)
+        cu_tab = cu_nets = cu_hints = None
+        if cu is not None:   # the table over the whole schedule (its rows are the step counter's), the further units' models and hints
+            cu_tab = control_mod.table(cu, num_steps)
+            cu_nets = [self._control_models(u) for u in cu[1:]]
+            cu_hints = [self._hint_batch(u.image, B) for u in cu[1:]]
+            if cu_nets:   # (model objects, not options: in front of the options on the way to the engine)
+                engine_opts = dict(engine_opts, control_nets=tuple(cu_nets))
         ref_in = None
         if ref is not None:
             if g > 0.0 and unconditional_context.shape[1] != context.shape[1]:
@@ -1110,10 +1205,12 @@ class StableDiffusionBase:
             if spec is not None:
                 latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
                                                  sampler_z, ip, region_w=region_w, pag=pg, hypertile=ht_key, sag=sg, dynthresh=dt,
+                                                 control=None if cu is None else (cu_tab, cu_nets, cu_hints),
                                                  reference=None if ref is None else (ref, ref_in, reference_mod.rates(sched, start_index)))
             else:
                 latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending, ip,
                                          region_w=region_w, pag=pg, hypertile=ht_key, sag=sg, dynthresh=dt,
+                                         control=None if cu is None else (cu_tab, cu_nets, cu_hints, start_index),
                                          reference=None if ref is None else (ref, ref_in, reference_mod.rates(self.scheduler, start_index)))
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
@@ -1138,6 +1235,10 @@ class StableDiffusionBase:
             shared["region_ctx"], shared["region_w"] = region_ctx, region_w
         if ref is not None:   # the reference latent and its draw: whole on every rank, every rank runs its own reference row
             shared["ref_z"], shared["ref_noise"] = ref_in
+        if cu is not None:   # the further units' hints per sample, the table whole on every rank (like region_w)
+            for n, hi in enumerate(cu_hints):
+                per_sample[f"control_hint{n + 1}"] = hi
+            shared["control_table"] = cu_tab
 
         def local(c, u, z, a):
             """This rank's slice of the batch: one denoise pass -> decode; returns a device tensor."""
@@ -1151,7 +1252,8 @@ class StableDiffusionBase:
                                           step_noise=a.get("tcd") if spec is None else a.get("sampler_z"), sampler=sched,
                                           regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale,
                                           reference=None if ref is None else (a["ref_z"], a["ref_noise"], ref.fidelity), sag=sg,
-                                          dynamic_threshold=dt))
+                                          dynamic_threshold=dt,
+                                          control=None if cu is None else (a["control_table"], [a[f"control_hint{n + 1}"] for n in range(len(cu) - 1)])))
             if return_latent:
                 return eng.latent
             if blend_pixels:   # pixel blend in fp32 before the uint8 cast
@@ -1178,6 +1280,23 @@ class StableDiffusionBase:
         if rows > 2 * tiled_mod.MAX_VIEW_BATCH:
             raise ValueError(f"{kind}: {batch_size} image(s){how} are {rows} UNet rows per step, more than 2 * tiled.MAX_VIEW_BATCH = "
                              f"{2 * tiled_mod.MAX_VIEW_BATCH}: {advice}")
+
+    def _control_models(self, unit):
+        """The (ControlNet, HintNet) of a control unit behind the first: its own `models`, the pipeline's own ControlNet (path None),
+        or the models of the checkpoint `path`, loaded once and kept on the pipeline by path."""
+        if unit.models is not None:
+            return tuple(unit.models)
+        if unit.path is None or unit.path == getattr(self, "controlnet_path", None):
+            return (self.control_net, self.hint_net)
+        cache = self.__dict__.setdefault("_control_models_by_path", {})
+        if unit.path not in cache:
+            dev = getattr(self, "device", None)
+            cache[unit.path] = (ControlNet(self.img_height, self.img_width, controlnet_path=unit.path, device=dev),
+                                HintNet(self.img_height, self.img_width, controlnet_path=unit.path, device=dev))
+            if self.jit_compile:
+                for m in cache[unit.path]:
+                    m.compile(jit_compile=True)
+        return cache[unit.path]
 
     def _reference_inputs(self, ref, h, w, seed):
         """(z_ref, n_ref) of a reference-only job, each (1, h, w, 4) float32: the given latent, or the picture through the VAE
@@ -1369,8 +1488,9 @@ class StableDiffusionBase:
                              + ", ".join(f"{w}: {n}" for w, n in lengths))
         return np.stack(encoded, axis=0), reg.weights()
 
-    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> tuple:
-        """`opts` as _engine takes them: one at its default (None) adds nothing to the key, an unknown name is a TypeError."""
+    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, control_nets=(), **opts) -> tuple:
+        """`opts` as _engine takes them: one at its default (None) adds nothing to the key, an unknown name is a TypeError.
+        `control_nets`: the further units' (ControlNet, HintNet) pairs - which objects they are and their weights' versions."""
         # the engine's plans (and captured hipGraphs) hold raw addresses of the packed weights: a set_weights() /
         # load_synthetic() / LoRA reload on any of the models it was built from must retire it
         base = self.diffusion_model
@@ -1378,14 +1498,15 @@ class StableDiffusionBase:
         wver = (unet.weights_version,) + ((self.control_net.weights_version, self.hint_net.weights_version) if control else ())
         key = (B, tc, tu, steps, g, phi, control, self.denoise_streams, inpaint, self.active_tcd, wver, engine.GN_EPOCH, opts.get("sampler"))
         key = key if unet is base else key + ((unet.h, unet.w),)   # (a hires job's second size: a view of the same weights)
+        key += tuple(("control_net", id(cn), cn.weights_version, id(hn), hn.weights_version) for cn, hn in control_nets)
         return key + EngineOptions.of(**opts).key()
 
-    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, **opts) -> DenoiseEngine:
+    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, control_nets=(), **opts) -> DenoiseEngine:
         """The resident engine of this shape, built if need be.  `opts`: `unet` (the UNet of another size: a hires job's second pass) and
         DenoiseEngine's options (jobopts.EngineOptions).  `job_keys`: the keys of every engine the current job uses (default: this one
         alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is built: a
         re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than the job's own engines."""
-        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, **opts)
+        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, control_nets=control_nets, **opts)
         keep = {key} | set(job_keys or ())
         if any(k not in keep for k in self._engines):
             import gc
@@ -1402,17 +1523,20 @@ class StableDiffusionBase:
                                 control_net=self.control_net if control else None,
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
                                 # (`regions` always as an int: what the residency tests read off this call for a plain job)
-                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd, **dict(opts, regions=opts.get("regions") or 0))
+                                streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd,
+                                **(dict(control_nets=control_nets) if control_nets else {}), **dict(opts, regions=opts.get("regions") or 0))
             self._engines[key] = eng
         return eng
 
     def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None,
-                   region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None):
-        """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479)."""
+                   region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None):
+        """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479).  control = (table, the further units'
+        (ControlNet, HintNet) pairs, their hint pictures, the first executed row) of a job with ControlNet units."""
         if timesteps is None:
             timesteps = self.scheduler.timesteps[::-1]
         batch_size = latent.shape[0]
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
+        cu_units = None if control is None else self._host_control_units(hint, control)
         iteration = 0
         n_sched = len(self.scheduler.timesteps)
         # (a job with dynamic thresholding: the scales of the executed steps as the device reads them, fp32)
@@ -1426,8 +1550,10 @@ class StableDiffusionBase:
             sag_step = None if sag is None else (sag, float(np.float32(self.scheduler.signal_rates[timestep])),
                                                  float(np.float32(self.scheduler.noise_rates[timestep])))
             dt_step = None if dynthresh is None else (dynthresh, float(dt_tab[iteration, 0]), float(dt_tab[iteration, 1]))
+            # (a job with ControlNet units: row control[3] + iteration of its table, the device step counter's row)
+            cu_step = None if control is None else (cu_units, control[0][control[3] + iteration])
             latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag, ref_step, hypertile,
-                                      sag_step, dt_step)
+                                      sag_step, dt_step, cu_step)
             latent = self.scheduler.step(latent, timestep, latent_prev)
             if inpaint is not None:   # reference :469-475
                 init_latent, noise, latent_mask = inpaint
@@ -1439,8 +1565,15 @@ class StableDiffusionBase:
                 callback(iteration)
         return latent
 
+    def _host_control_units(self, hint, control):
+        """[(ControlNet, its hint activation), ...] of a host-loop job with ControlNet units, unit 0 first."""
+        units = [(self.control_net, hint)]
+        for (cn, hn), img in zip(control[1], control[2]):
+            units.append((cn, hn.predict_on_batch(img)))
+        return units
+
     def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None, reference=None,
-                    hypertile=None, sag=None, dynthresh=None):
+                    hypertile=None, sag=None, dynthresh=None, control=None):
         """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
         A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
         predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host); in mode "attention"
@@ -1450,7 +1583,10 @@ class StableDiffusionBase:
         second predict_on_batch on the degraded latent, sag.combine_host - the device step's four parts in its order.
         A job with dynamic thresholding passes (its dynthresh.Resolved, the step's fp32 cfg scale, its fp32 mimic scale): behind
         whatever made u and c (the regions, PAG or SAG combine included) the result is dynthresh.dynthresh_host of the two, and no
-        rescale follows - the device step's order."""
+        rescale follows - the device step's order.
+        A job with ControlNet units passes ([(ControlNet, hint activation), ...], the step's table row fp32 [N][13][2]): the 13 arrays
+        of every unit's predict_on_batch are scaled and summed (control.scale_host) with column 0 for the unconditional and column
+        1 for the conditional prediction."""
         def guided(u, c):
             if dynthresh is not None:
                 spec_dt, g_i, m_i = dynthresh
@@ -1489,13 +1625,17 @@ class StableDiffusionBase:
                                                         adain=ref.adain)
             return guided(u, c)
 
-        def predict(ctx):
-            """The UNet's prediction for one context, through the ControlNet if there is a hint; a HyperTile job's through
-            predict_windowed ((nh, nw, depth))."""
+        def predict(ctx, half=1):
+            """The UNet's prediction for one context, through the ControlNet if there is a hint (half: 0 for the unconditional
+            prediction - the column of a control-units table); a HyperTile job's through predict_windowed ((nh, nw, depth))."""
             if hypertile is not None:
                 return self.diffusion_model.predict_windowed([latent, t_emb, ctx], hypertile[:2], hypertile[2])
             if hint is None:
                 return self.diffusion_model.predict_on_batch([latent, t_emb, ctx])
+            if control is not None:
+                units, row = control
+                controls = control_mod.scale_host([cn.predict_on_batch([latent, t_emb, ctx, hi]) for cn, hi in units], row[:, :, half])
+                return self.diffusion_model.predict_on_batch([latent, t_emb, ctx] + list(controls))
             controls = self.control_net.predict_on_batch([latent, t_emb, ctx, hint])
             return self.diffusion_model.predict_on_batch([latent, t_emb, ctx] + list(controls))
 
@@ -1504,7 +1644,7 @@ class StableDiffusionBase:
             c = self.diffusion_model.predict_regional([latent, t_emb], context, region_w)
         else:
             c = regions_mod.combine_host([predict(rc) for rc in context], region_w) if regional else None
-        u = predict(unconditional_context) if g > 0.0 else None
+        u = predict(unconditional_context, 0) if g > 0.0 else None
         c = c if regional else predict(context)
         if pag is not None:
             p = self.diffusion_model.predict_perturbed([latent, t_emb, context], pag.layers)
@@ -1514,10 +1654,12 @@ class StableDiffusionBase:
         return guided(u, c)
 
     def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
-                           inpaint=None, region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None):
-        """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`."""
+                           inpaint=None, region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None):
+        """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`.
+        control = (table, the further units' (ControlNet, HintNet) pairs, their hint pictures) of a job with ControlNet units."""
         batch_size = latent.shape[0]
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
+        cu_units = None if control is None else self._host_control_units(hint, control)
         tab = smp.rows(sched, start)
         x = np.asarray(latent, dtype=np.float64)
         prev = None
@@ -1527,7 +1669,8 @@ class StableDiffusionBase:
             e = self._guided_eps(x.astype(np.float32), t_emb, context, unconditional_context, g, phi, hint, region_w, pag,
                                  None if reference is None else reference + (i,), hypertile,
                                  None if sag is None else (sag, float(np.float32(tab[i, 0])), float(np.float32(tab[i, 1]))),
-                                 None if dynthresh is None else (dynthresh, float(dt_tab[i - start, 0]), float(dt_tab[i - start, 1])))
+                                 None if dynthresh is None else (dynthresh, float(dt_tab[i - start, 0]), float(dt_tab[i - start, 1])),
+                                 None if control is None else (cu_units, control[0][i]))
             z = step_noise[:, i] if step_noise is not None else None
             x, prev = smp.host_step(tab[i], x, e, prev, z)
             if inpaint is not None:   # the row's own alpha / sigma, as in the device kernel
