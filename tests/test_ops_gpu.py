@@ -68,7 +68,8 @@ def conv_ref(x_nhwc, w_hwio, bias=None, stride=1, pad=1, upsample=False):
     return y.permute(0, 2, 3, 1).contiguous()
 
 
-@pytest.mark.parametrize("case", [
+# The forced-form case lists are module-level names: tests/test_conv_exact_gpu.py runs the same launches on integer operands.
+CONV_GEMM_CASES = [
     dict(B=2, H=16, W=16, c0=64, N=128, ks=3),                       # basic 3x3
     dict(B=1, H=8, W=8, c0=128, N=320, ks=3),                        # M=64 < tile, N=320 (64-wide tiles)
     dict(B=2, H=12, W=20, c0=64, N=192, ks=3, tile_n=128),           # ragged M and N edges
@@ -213,7 +214,10 @@ def conv_ref(x_nhwc, w_hwio, bias=None, stride=1, pad=1, upsample=False):
     dict(B=2, H=8, W=8, c0=128, c1=64, N=256, ks=3, upsample=True, tile_m=5256, tile_n=128, stages=20, same_as=(5256, 128, 10)),   # nearest x2 in the halo staging (one 16x16 tile per sample)
     dict(B=1, H=16, W=24, c0=64, N=160, ks=3, upsample=True, tile_m=5256, tile_n=160, stages=20, same_as=(5256, 160, 11)),          # 2 x 3 tiles of the 32 x 48 image
     dict(B=2, H=16, W=16, c0=128, c1=192, N=256, ks=3, tile_m=5128, tile_n=256, stages=10, same_as=(1256, 128, 0)),     # concat boundary inside the walk
-])
+]
+
+
+@pytest.mark.parametrize("case", CONV_GEMM_CASES)
 def test_conv_gemm(gpu, case):
     from minsdtf_amd import ops, packing
 
@@ -281,7 +285,7 @@ def test_conv_gemm(gpu, case):
     g.check()
 
 
-@pytest.mark.parametrize("case", [
+CONV_GEMM_SHORTCUT_CASES = [
     dict(B=2, H=12, W=20, c=128, cx0=64, cx1=0, N=128, ks=3),                          # ResBlock conv2 + 1x1 shortcut, ragged M
     dict(B=2, H=8, W=8, c=192, cx0=128, cx1=64, N=192, ks=3, splitk=3),                # shortcut over a concat, split-K across both parts
     dict(B=1, H=16, W=16, c=64, cx0=64, cx1=0, N=320, ks=3, tile_m=64, tile_n=64),
@@ -308,7 +312,10 @@ def test_conv_gemm(gpu, case):
     dict(B=2, H=16, W=32, c=192, cx0=64, cx1=128, N=160, ks=3, tile_m=1128, tile_n=80, stages=63, other=(5256, 160, 20)),              # loader waves, lock-step loop; concat boundary between shortcut chunks
     dict(B=3, H=32, W=32, c=64, cx0=320, cx1=0, N=128, ks=3, tile_m=1128, tile_n=128, stages=6, other=(5256, 128, 20)),                # more shortcut chunks (5) than main chunks (1), deep ring
     dict(B=2, H=8, W=16, c=128, cx0=128, cx1=0, N=64, ks=3, splitk=2, tile_m=2128, tile_n=64, stages=33),                              # an 8-row image (no 16 x 16 tile): the kernel against the fp32 answer alone
-])
+]
+
+
+@pytest.mark.parametrize("case", CONV_GEMM_SHORTCUT_CASES)
 def test_conv_gemm_shortcut_operand(gpu, case):
     """conv(h) + conv1x1(x) as one contraction (diffusion_model.py:34-38,50): K = taps of h, then the channels of x."""
     from minsdtf_amd import ops
@@ -381,7 +388,7 @@ def test_conv_gemm_geglu(gpu, tile):
     g.check()
 
 
-@pytest.mark.parametrize("case", [
+CONV_GEMM_LAYER_NORM_FOLD_CASES = [
     dict(M=200, C=320, tile=(128, 128, 0), mode="dense"),      # 3 column tiles x 4 wave slabs, ragged M
     dict(M=192, C=320, tile=(128, 80, 0), mode="qkv"),         # 80-wide producer tiles, q|k|v^T epilogue
     dict(M=128, C=640, tile=(64, 64, 0), mode="geglu"),        # 10 partials per row, GEGLU consumer
@@ -419,7 +426,10 @@ def test_conv_gemm_geglu(gpu, tile):
     dict(M=600, C=320, tile=(128, 64, 0), mode="geglu", ctile=(5256, 256, 0), csame=True),
     dict(M=520, C=640, tile=(64, 64, 0), mode="qkv", ctile=(5256, 160, 0), csame=True),                   # q | k | v^T split from 5 blocks per wave
     dict(M=300, C=320, tile=(128, 80, 0), mode="dense", ctile=(5128, 256, 1), csame=True),
-])
+]
+
+
+@pytest.mark.parametrize("case", CONV_GEMM_LAYER_NORM_FOLD_CASES)
 def test_conv_gemm_layer_norm_fold(gpu, case):
     """LayerNormalization folded into the GEMMs around it (diffusion_model.py:84-88 + Dense): the producer
     (Dense + residual) writes row-moment partials, the consumer normalises through its epilogue.  Reference:
@@ -560,7 +570,7 @@ def test_conv_gemm_qkv_split(gpu, nq):
     g.check()
 
 
-@pytest.mark.parametrize("case", [
+CONV_DIRECT_CASES = [
     dict(B=2, mod=1, H=8, W=8, cin=4, cout=320, in_f32=True),                    # UNet conv_in, latent shared by both halves
     dict(B=2, mod=2, H=8, W=8, cin=320, cout=4, in_f32=False, out="f32"),        # UNet conv_out
     dict(B=1, mod=1, H=16, W=16, cin=128, cout=3, in_f32=False, out="u8"),       # VAE conv_out -> uint8
@@ -575,7 +585,10 @@ def test_conv_gemm_qkv_split(gpu, nq):
     dict(B=3, mod=3, H=24, W=48, cin=4, cout=512, in_f32=True, scale=1 / 0.18215),  # VAE decoder.conv_in: 16-pixel segments, 2 px groups
     dict(B=1, mod=1, H=5, W=8, cin=4, cout=64, in_f32=True),                     # 8-pixel segments, 16 pixel groups
     dict(B=1, mod=1, H=6, W=6, cin=4, cout=320, in_f32=True),                    # width not a multiple of 8: generic kernel
-])
+]
+
+
+@pytest.mark.parametrize("case", CONV_DIRECT_CASES)
 def test_conv_direct(gpu, case):
     from minsdtf_amd import ops
 
