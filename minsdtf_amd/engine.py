@@ -411,10 +411,22 @@ class AttnVariant:
     # live, ONE msdx_attention_colsum launch writes the attention every key of the rows row0 .. row0 + rows - 1 receives - fp32
     # [rows][H * W] to `out`, through `workspace` (ops.colsum_workspace_floats(rows, heads, H * W) floats).  Head size 160: the mid block.
     colsum: Optional[tuple] = None
+    # ip = (k_ip, vt_ip, n, np_ld, scales, num_steps, layer_index) (an IP-Adapter image prompt, minsdtf_amd/ipadapter.py): k_ip bf16
+    # [B][n][C] and vt_ip bf16 [B][C][np_ld] are this block's K / V^T of the n image tokens (emit_ip_kv), `scales` the per-step table
+    # fp32 [num_steps][16] and layer_index this block's column of it.  attn2 then takes the unfused route: q from attn2.to_q and ONE
+    # msdi_attention_decoupled launch for all rows - the text attention plus scales[*step_ptr][layer_index] times the image one.
+    ip: Optional[tuple] = None
 
     def check(self, name, x: Act, heads: int, shared: int) -> None:
         """What the fields exclude for the block `name` over the whole input x (all `shared` copies), as ValueError."""
         perturbed, regions, reference, window = self.perturbed, self.regions, self.reference, self.window
+        if self.ip is not None:
+            _k, _vt, n_ip, np_ld, _sc, num_steps, layer = self.ip
+            if regions:
+                raise ValueError(f"{name}: ip (an image prompt) does not go with regions = {regions}: both replace the attn2 launch")
+            if not 1 <= n_ip <= 16 or np_ld < n_ip or np_ld % 8 or num_steps < 1 or not 0 <= layer < 16 or x.C // heads not in (40, 80, 160):
+                raise ValueError(f"{name}: ip with {n_ip} image tokens (1 .. 16) in rows of {np_ld}, table column {layer} of {num_steps} "
+                                 f"step rows, head size {x.C // heads}")
         if self.colsum is not None:
             _cs_out, _cs_ws, cs_row0, cs_rows = self.colsum
             if x.C // heads != 160 or shared > 1 or reference or window is not None or cs_row0 < 0 or cs_rows < 1 \
@@ -683,6 +695,9 @@ class Emitter:
         if v.regions:
             if not 1 <= v.region_rows <= B or v.region_w is None or ctx_len > 96 or d not in (40, 80, 160):
                 raise ValueError(f"{name}: {v.regions} regions over {v.region_rows} of {B} rows, {ctx_len} context tokens, head size {d}")
+        elif v.ip is not None:
+            if (ctx_len + 7) // 8 * 8 + v.ip[2] > 96:
+                raise ValueError(f"{name}: {ctx_len} context tokens and {v.ip[2]} image tokens do not fit one tile of 96 keys")
         elif fold and XATTN_FUSED and heads == 8 and (d in (40, 80) or (d == 160 and XATTN_FUSED_D160)) and ctx_len <= 96:
             # norm2 -> to_q -> attention over the 77 context tokens as ONE launch (msd_cross_attention_q)
             wn = tb + ".attn2.to_q"
@@ -693,6 +708,13 @@ class Emitter:
             p.free(t1.ln[0])
             return a2
         q2 = self._ln_conv(t1, tb + ".norm2", tb + ".attn2.to_q", C, fold)
+        if v.ip is not None:   # text and image keys in ONE launch for all rows, the scale read from the table on the device
+            k_ip, vt_ip, n_ip, np_ld, scales, num_steps, layer = v.ip
+            p.rec(ops.ip_attention, q=q2.buf, k=kc, vt=vtc, k_ip=k_ip, vt_ip=vt_ip, out=a2.buf, scales=scales, step_ptr=self.step_ptr,
+                  batch=B, heads=heads, head_dim=d, s=S, t=ctx_len, n=n_ip, q_ld=C, k_ld=C, vt_ld=tp, kip_ld=C, vtip_ld=np_ld, o_ld=C,
+                  layer=layer, num_steps=num_steps, name=tb + ".attn2.ip")
+            p.free(q2)
+            return a2
         if bu:
             p.rec(ops.attention, q=q2.buf, k=kc, vt=vtc, out=a2.buf, batch=bu, heads=heads, head_dim=d, s=S, t=ctx_len, q_ld=C,
                   k_ld=C, vt_ld=tp, o_ld=C, scale=d ** -0.5, q_prescaled=True, name=tb + ".attn2")
@@ -731,6 +753,21 @@ def emit_context_kv(e: Emitter, ctx: Act, attn_names: Sequence[Tuple[str, int]],
         vb = persistent.alloc(ctx.B * C * tp * 2)
         e.conv(ctx, name + ".kv", 2 * C, bias=False, split=(0, C, None, kb, vb, tp))
         out[name] = (kb, vb, tp)
+    return out
+
+
+def emit_ip_kv(e: Emitter, tokens: Act, attn_names: Sequence[Tuple[str, int]], persistent: Plan):
+    """K and V^T of an IP-Adapter's image tokens for every cross-attention layer (constant over all steps), from the adapter's
+    to_k_ip / to_v_ip weights - `e` is an Emitter over models.IPAdapter's packed image, whose keys are <attn2 name>.kv_ip.w.
+    tokens: bf16 [NB][N][768] as an Act with H=N, W=1.  Buffers come from `persistent` (never recycled)."""
+    out = {}
+    N = tokens.H
+    np_ld = (N + 7) // 8 * 8
+    for name, C in attn_names:
+        kb = persistent.alloc(tokens.B * N * C * 2)
+        vb = persistent.alloc(tokens.B * C * np_ld * 2)
+        e.conv(tokens, name + ".kv_ip", 2 * C, bias=False, split=(0, C, None, kb, vb, np_ld))
+        out[name] = (kb, vb, np_ld)
     return out
 
 
@@ -834,6 +871,9 @@ class UNetVariant:
     # sag = mid_block.attentions.0's AttnVariant.colsum, its map fp32 [rows][mh * mw] with (mh, mw) = unet_levels(h, w)[3]; the mid
     # block is never part of the shared prefix.
     sag: Optional[tuple] = None
+    # ip = ({attn2 layer name: (k_ip, vt_ip, np_ld)} (emit_ip_kv over the NB rows), n, scales, num_steps): every block takes
+    # AttnVariant.ip with its own K / V^T of the n image tokens and its own column of the table `scales`, fp32 [num_steps][16].
+    ip: Optional[tuple] = None
 
     def _pag(self) -> frozenset:
         return frozenset(self.pag_layers or ()) if self.perturbed else frozenset()
@@ -856,6 +896,8 @@ class UNetVariant:
                 raise ValueError("emit_unet: adain goes with a reference row and not with pag, regions, a window or a ControlNet")
         if self._pag() - set(PAG_LAYERS):
             raise ValueError(f"emit_unet: unknown attention block(s) {sorted(self._pag() - set(PAG_LAYERS))}")
+        if self.ip is not None and (self.perturbed or self.region_attn or self.reference is not None or self.window is not None or self.sag is not None):
+            raise ValueError("emit_unet: ip (an image prompt) does not go with pag, regions, a reference row, a window or sag")
         if self.window is not None:
             if self.perturbed or self.region_attn or self.reference is not None:
                 raise ValueError("emit_unet: window does not go with pag, regions or a reference row")
@@ -875,7 +917,12 @@ class UNetVariant:
         R, rows, planes = self.region_attn or (0, 0, None)
         windowed = self.window is not None and ATTN_LEVEL[block] <= self.window_depth   # (such a block takes the window, not the reference)
         referenced = not windowed and self.reference is not None and block in frozenset(self.reference[0])
-        return AttnVariant(perturbed=self.perturbed if block in self._pag() else 0, regions=R, region_rows=rows,
+        ip = None
+        if self.ip is not None:
+            kv, n_ip, scales, num_steps = self.ip
+            k_ip, vt_ip, np_ld = kv[block + ".transformer_blocks.0.attn2"]
+            ip = (k_ip, vt_ip, n_ip, np_ld, scales, num_steps, PAG_LAYERS.index(block))
+        return AttnVariant(ip=ip, perturbed=self.perturbed if block in self._pag() else 0, regions=R, region_rows=rows,
                            region_w=planes[(x.H, x.W)] if self.region_attn else None,   # the weight plane of x's level
                            reference=int(referenced), mix=self.reference[2] if referenced else None,
                            window=tuple(self.window) if windowed else None, colsum=self.sag if block == "mid_block.attentions.0" else None)

@@ -3,7 +3,7 @@ a parsed job description means ("Where a job option lives")."""
 from dataclasses import dataclass
 from typing import FrozenSet, Optional, Tuple
 
-from . import control as control_mod, hypertile as hypertile_mod, reference as reference_mod, regions as regions_mod, samplers as smp
+from . import control as control_mod, hypertile as hypertile_mod, ipadapter as ipadapter_mod, reference as reference_mod, regions as regions_mod, samplers as smp
 from .engine import PAG_LAYERS
 
 # job kind -> (what it is, the arguments and then the states it cannot be combined with, in the order the error names them)
@@ -35,11 +35,13 @@ _ENGINE_SENTENCE = {
 }
 
 
-def job_options(sampler=None, regions=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None) -> dict:
+def job_options(sampler=None, regions=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None,
+                ip_tokens=None) -> dict:
     """_engine's option keywords of a job from its parsed descriptions (None: the job has none): only what the job asks for.
-    `control`: the parsed units of control.parse - the engine is built for their number only."""
+    `control`: the parsed units of control.parse - the engine is built for their number only.  `ip_tokens`: the number of image
+    tokens of a job with an IP-Adapter image prompt - the engine is built for that number only."""
     out = dict(sampler=sampler and sampler.name, pag=pag and pag.key, hypertile=hypertile, sag=sag and True, dynthresh=dynthresh and True,
-               control_units=control and len(control))
+               control_units=control and len(control), ip_tokens=ip_tokens or None)
     if regions is not None:   # (the base prompt counts when it is evaluated)
         out.update(regions=regions.count, region_mode=regions.mode)
     if reference is not None:
@@ -61,6 +63,7 @@ class EngineOptions:
     sag: bool = False                                # self-attention guidance
     dynthresh: bool = False                          # dynamic thresholding
     control_units: int = 0                           # the number of ControlNet units of a job with control= (minsdtf_amd/control.py)
+    ip_tokens: int = 0                               # the number of image tokens of a job with ip_adapter= (minsdtf_amd/ipadapter.py)
 
     @classmethod
     def of(cls, **opts) -> "EngineOptions":
@@ -71,7 +74,7 @@ class EngineOptions:
                    region_mode=o.region_mode if regions or o.region_mode not in regions_mod.MODES else "latent",   # (an unknown mode stays, for check() to name)
                    pag=frozenset(o.pag) if o.pag else None, reference=frozenset(o.reference or ()) if (o.reference or adain) else None,
                    adain=adain, hypertile=tuple(int(v) for v in ht) if ht is not None and len(ht) == 3 else ht,   # (else as given, for check())
-                   sag=bool(o.sag), dynthresh=bool(o.dynthresh), control_units=int(o.control_units))
+                   sag=bool(o.sag), dynthresh=bool(o.dynthresh), control_units=int(o.control_units), ip_tokens=int(o.ip_tokens))
 
     def key(self) -> tuple:
         """What the options add to an engine's key behind the UNet-size part: what the plans depend on, nothing a call uploads."""
@@ -84,7 +87,8 @@ class EngineOptions:
             key += (("reference", tuple(sorted(self.reference))) + ((("adain",) + tuple(sorted(self.adain)),) if self.adain else ()),)
         key += ((("hypertile",) + self.hypertile,) if self.hypertile else ()) + ((("sag",),) if self.sag else ())
         key += (("dynthresh",),) if self.dynthresh else ()
-        return key + ((("control", self.control_units),) if self.control_units else ())
+        key += (("control", self.control_units),) if self.control_units else ()
+        return key + ((("ip", self.ip_tokens),) if self.ip_tokens else ())
 
     def check(self, h: int, w: int, B: int, guidance: float, control: bool, inpaint: bool, tcd: bool, streams) -> None:
         """ValueError for what an engine of batch B at h x w refuses: each kind's own checks, then its exclusions, read from REFUSED."""
@@ -133,3 +137,9 @@ class EngineOptions:
         # control units exclude nothing a ControlNet job is not already excluded from (the rows above name it): no REFUSED row
         if self.control_units and not (1 <= self.control_units <= control_mod.MAX_UNITS and control):
             raise ValueError(f"control: {self.control_units} unit(s) (1 .. {control_mod.MAX_UNITS}, on an engine with a ControlNet)")
+        # an image prompt's exclusions live in ipadapter.py (REFUSED above is counted by its tests): no REFUSED row either
+        if self.ip_tokens:
+            if not 1 <= self.ip_tokens <= ipadapter_mod.MAX_TOKENS:
+                raise ValueError(f"ip_adapter: {self.ip_tokens} image tokens (1 .. {ipadapter_mod.MAX_TOKENS})")
+            ipadapter_mod.refuse(dict(regions=self.regions or None, pag=self.pag, sag=self.sag or None, reference_only=self.reference,
+                                      hypertile=self.hypertile, tiled=self.tiled), streams)

@@ -256,7 +256,7 @@ class DiffusionModel(HipModel):
         self._maybe_load(ckpt_path, lora_dict)
 
     def _build(self, B: int, T: int, with_controls: bool, pag_layers=None, regions: int = 0, reference=None, window=None,
-               adain=None, sag: bool = False) -> _BoundPlan:
+               adain=None, sag: bool = False, ip=None) -> _BoundPlan:
         """pag_layers: the attention blocks whose self-attention is the identity map for ALL B rows (predict_perturbed).
         regions = R: all B rows are conditional rows over R region contexts (predict_regional): the context input is
         (R * B, T, 768), region-major, and `region_w` the four levels' weight planes (regions.pack_levels).
@@ -265,7 +265,9 @@ class DiffusionModel(HipModel):
         adain = the reference AdaIN sites of such a forward (reference.ADAIN_SITES); `reference` may then be an empty set.
         window = (nh, nw, depth) of a HyperTile forward (predict_windowed): engine.UNetVariant's window / window_depth.
         sag: the mid block's self-attention also writes the attention map of all B rows (predict_sag_map): io["sag_A"], fp32
-        [B][mh * mw]."""
+        [B][mh * mw].
+        ip = a models.IPAdapter (predict_ip): every attn2 is ONE msdi_attention_decoupled launch over the text context and the
+        adapter's K / V^T of `ip_tokens` (B, N, 768), scaled by row 0 of `ip_scales`, fp32 (1, 16)."""
         h, w = self.h, self.w
         reference = frozenset(reference or ()) if (reference or adain) else None   # (an empty layer set next to AdaIN sites)
         NB = B + 1 if reference is not None else B
@@ -282,12 +284,19 @@ class DiffusionModel(HipModel):
             levels = engine.unet_levels(h, w)
             offs = regions_mod.level_offsets(regions, levels)
             shapes["region_w"] = (offs[-1],)
+        if ip is not None:
+            shapes.update(ip_tokens=(B, ip.tokens, 768), ip_scales=(1, 16))
         ins = _stage_inputs(plan, shapes)
         if regions:
             region_attn = (regions, B, {lv: ins["region_w"].at(o * 4) for lv, o in zip(levels, offs)})
         ctx16 = engine.Act(plan.alloc(CB * T * 768 * 2), CB, T, 1, 768)
         plan.rec(ops.cast_f32_to_bf16, x=ins["context"], out=ctx16.buf, n=CB * T * 768, name="context.bf16")
         ctx_kv = engine.emit_context_kv(e, ctx16, engine.UNET_ATTN_LAYERS, plan)
+        ip_variant = None
+        if ip is not None:
+            tok16 = engine.Act(plan.alloc(B * ip.tokens * 768 * 2), B, ip.tokens, 1, 768)
+            plan.rec(ops.cast_f32_to_bf16, x=ins["ip_tokens"], out=tok16.buf, n=B * ip.tokens * 768, name="ip_tokens.bf16")
+            ip_variant = (engine.emit_ip_kv(engine.Emitter(plan, ip._W), tok16, engine.UNET_ATTN_LAYERS, plan), ip.tokens, ins["ip_scales"], 1)
         cols = engine.temb_columns(False)
         total = sum(c for _, c in engine.resblock_names(False))
         table = plan.alloc(NB * total * 4)
@@ -312,7 +321,7 @@ class DiffusionModel(HipModel):
             reference=(reference, ins["ref_latent"], ins["ref_mix"]) if reference is not None else None,
             adain=frozenset(adain) if adain else None,
             window=window[:2] if window is not None else None, window_depth=window[2] if window is not None else 0,
-            sag=(sag_A, sag_ws, 0, B) if sag else None)
+            sag=(sag_A, sag_ws, 0, B) if sag else None, ip=ip_variant)
         engine.emit_unet(e, ins["latent"], B, NB, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls, variant=variant)
         plan.finalize()
         bp = _BoundPlan(plan, self._use_graph)
@@ -427,6 +436,41 @@ class DiffusionModel(HipModel):
         bp.run()
         return bp.host("eps")[:B]
 
+    def predict_ip(self, x, adapter, tokens, scales):
+        """predict_on_batch([latent, t_emb, context(, 13 controls)]) with an IP-Adapter image prompt: every attn2 also attends to the
+        image `tokens` - (N, 768) for every row, or (B, N, 768) - through `adapter` (a models.IPAdapter), its share scaled per
+        attention block by `scales`, fp32 (16,) in engine.PAG_LAYERS order (one row of ipadapter.table).  The forward of an image-prompt
+        job's host loop (minsdtf_amd/ipadapter.py); a bound plan of its own per (B, T, adapter)."""
+        from . import ipadapter as ipadapter_mod
+
+        if len(x) not in (3, 16):
+            raise ValueError("predict_ip takes [latent, t_emb, context] and, with a ControlNet, its 13 control tensors")
+        latent, t_emb, context = _np32(x[0]), _np32(x[1]), _np32(x[2])
+        controls = [_np32(c) for c in x[3:]]
+        B, T = latent.shape[0], context.shape[1]
+        if latent.shape[1:] != (self.h, self.w, 4):
+            raise ValueError(f"latent shape {latent.shape} does not match the model ({self.h},{self.w},4)")
+        adapter._require_weights()
+        tok = _np32(tokens)
+        tok = np.array(np.broadcast_to(tok, (B,) + tok.shape)) if tok.ndim == 2 else tok   # (a copy: every row its own)
+        sc = _np32(scales).reshape(-1)
+        if tok.shape != (B, adapter.tokens, 768) or sc.shape != (16,):
+            raise ValueError(f"predict_ip: tokens of shape {tok.shape} and {sc.shape[0]} scales, expected {(B, adapter.tokens, 768)} "
+                             f"(or {(adapter.tokens, 768)}) and 16")
+        ipadapter_mod.check_context(T, adapter.tokens)
+        key = (B, T, bool(controls), ("ip", adapter.tokens, id(adapter), adapter.weights_version))
+        bp = self._bound(key, lambda: self._build(B, T, bool(controls), ip=adapter))
+        bp.keep_alive = adapter   # (the plan holds raw addresses of its packed weights)
+        bp.io["latent"].copy_(torch.from_numpy(latent))
+        bp.io["t_emb"].copy_(torch.from_numpy(t_emb))
+        bp.io["context"].copy_(torch.from_numpy(context))
+        bp.io["ip_tokens"].copy_(torch.from_numpy(tok))
+        bp.io["ip_scales"].copy_(torch.from_numpy(sc.reshape(1, 16)))
+        for i, c in enumerate(controls):
+            bp.io[f"control.{i}"].copy_(torch.from_numpy(c))
+        bp.run()
+        return bp.host("eps")
+
     def _predict(self, x, pag_layers, window=None, sag=False):
         latent, t_emb, context = _np32(x[0]), _np32(x[1]), _np32(x[2])
         controls = [_np32(c) for c in x[3:]]
@@ -453,6 +497,98 @@ class DiffusionModel(HipModel):
         return bp.host("eps")
 
     __call__ = predict_on_batch
+
+
+class IPAdapter:
+    """The weights of an IP-Adapter (minsdtf_amd/ipadapter.py): a small model object of its own beside the UNet - 32 bias-free
+    matrices, to_k_ip / to_v_ip of the 16 cross-attentions, packed per attention as ONE bf16 [2 C][768] matrix
+    `<attn2 name>.kv_ip.w` (k rows, then v rows) the way layout.py describes a bias-free dense (ROWS, chunk-major as the UNet's) -
+    and, on the host in float64, the image projection Linear(1024 -> N * 768) + LayerNorm(768).  They do not enter the UNet's
+    packed image, and a LoRA switch does not touch them."""
+
+    def __init__(self, tokens: int = 4, name=None, device=None, path=None):
+        from . import ipadapter as ipadapter_mod
+
+        if not 1 <= int(tokens) <= ipadapter_mod.MAX_TOKENS:
+            raise ValueError(f"ip_adapter: {tokens} image tokens (1 .. {ipadapter_mod.MAX_TOKENS})")
+        self.name = name or "ip_adapter"
+        self.device = device if device is not None else default_device()
+        self.tokens = int(tokens)
+        self._W = None
+        self.projection: Optional[Dict[str, np.ndarray]] = None
+        self.weights_version = 0
+        if path is not None:
+            self.load(path)
+
+    def _require_weights(self):
+        if self._W is None:
+            raise RuntimeError(f"{self.name}: no weights set (pass path=, call set_state() or IPAdapter.synthetic())")
+
+    @staticmethod
+    def packed_layout() -> List["layout.Packed"]:
+        """The packed image: per cross-attention one ROWS entry over its two source layers, in engine.UNET_ATTN_LAYERS order."""
+        out = []
+        for name, C in engine.UNET_ATTN_LAYERS:
+            parts = [layout.Part(name + ".to_k_ip"), layout.Part(name + ".to_v_ip", row_off=C)]
+            out.append(layout.Packed(name + ".kv_ip.w", layout.ROWS, (2 * C, 768), parts, chunk_major=engine.W_CHUNK_MAJOR))
+        return out
+
+    def set_state(self, state) -> None:
+        """Adopt a loaded checkpoint (ipadapter.read_state's input: the nested dict of a .bin or flat prefixed keys); raises on any
+        key or shape that does not fit."""
+        from . import ipadapter as ipadapter_mod
+
+        named = ipadapter_mod.read_state(state)
+        n = named["proj.weight"].shape[0] // 768
+        named_keras = {}
+        for name, _C in engine.UNET_ATTN_LAYERS:
+            blk = name[:-len(".transformer_blocks.0.attn2")]
+            for m in ("to_k_ip", "to_v_ip"):   # torch Linear [out][in] -> the Keras Dense (in, out) the packer starts from
+                named_keras[(f"{name}.{m}", "dense_w")] = np.ascontiguousarray(named[f"{blk}.{m}"].T)
+        W, _ = packing.pack(self.packed_layout(), named_keras, self.device)
+        self._W, self.tokens = W, n
+        self.projection = {k: np.asarray(named[k], dtype=np.float64) for k in ("proj.weight", "proj.bias", "norm.weight", "norm.bias")}
+        self.weights_version += 1
+
+    def load(self, path: str) -> None:
+        if not os.path.exists(str(path)):
+            raise ValueError(f"ip_adapter: checkpoint {path!r} not found")
+        self.set_state(wtab.read_state_dict(path))
+
+    @classmethod
+    def synthetic(cls, seed: int = 0, tokens: int = 4, device=None, scale: float = 1.0) -> "IPAdapter":
+        """A seeded synthetic adapter, for tests and fixtures like the synthetic UNet: Glorot-uniform matrices (times `scale`)."""
+        m = cls(tokens, device=device)
+        m.set_state(cls.synthetic_state(seed, tokens, scale))
+        return m
+
+    @staticmethod
+    def synthetic_state(seed: int = 0, tokens: int = 4, scale: float = 1.0) -> Dict[str, np.ndarray]:
+        """The flat state dict of synthetic(): the public file layout, float32 arrays."""
+        from . import ipadapter as ipadapter_mod
+
+        rng = np.random.default_rng([int(seed), 0x1BAD])
+
+        def glorot(out_f, in_f):
+            lim = float(np.sqrt(6.0 / (in_f + out_f))) * scale
+            return rng.uniform(-lim, lim, size=(out_f, in_f)).astype(np.float32)
+
+        state = {"image_proj.proj.weight": glorot(tokens * 768, 1024),
+                 "image_proj.proj.bias": rng.uniform(-0.05, 0.05, size=(tokens * 768,)).astype(np.float32),
+                 "image_proj.norm.weight": rng.uniform(0.8, 1.2, size=(768,)).astype(np.float32),
+                 "image_proj.norm.bias": rng.uniform(-0.1, 0.1, size=(768,)).astype(np.float32)}
+        for j, width in enumerate(ipadapter_mod.CHECKPOINT_WIDTHS):
+            state[f"ip_adapter.{2 * j + 1}.to_k_ip.weight"] = glorot(width, 768)
+            state[f"ip_adapter.{2 * j + 1}.to_v_ip.weight"] = glorot(width, 768)
+        return state
+
+    def project(self, embeds) -> np.ndarray:
+        """(1024,) CLIP image embedding -> the (N, 768) fp32 image tokens (ipadapter.project)."""
+        from . import ipadapter as ipadapter_mod
+
+        self._require_weights()
+        p = self.projection
+        return ipadapter_mod.project(embeds, p["proj.weight"], p["proj.bias"], p["norm.weight"], p["norm.bias"], self.tokens)
 
 
 def _skip_hw(i: int, h: int, w: int):

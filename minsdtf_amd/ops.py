@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
-from . import _lib, _lib_control, _lib_dynthresh, _lib_ext
+from . import _lib, _lib_control, _lib_dynthresh, _lib_ext, _lib_ipadapter
 from ._lib import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, OUT_BF16, OUT_F32, OUT_U8  # noqa: F401
 
 
@@ -375,6 +375,23 @@ def control_combine(*, skips, resid, counts, scales, rows, rows_u, num_steps, st
     a.scales, a.step_ptr = _p(scales), _p(step_ptr)
     a.rows, a.rows_u, a.units, a.num_steps = int(rows), int(rows_u), len(resid), int(num_steps)
     return Call(lib.msdc_control_combine, (C.byref(a),), name, keep=a, check=_lib_control.check)
+
+
+# ---- the IP-Adapter library (include/minsdtf_hip_ipadapter.h, minsdtf_amd/_lib_ipadapter.py) ---------------------------------------
+def ip_attention(*, q, k, vt, k_ip, vt_ip, out, scales, batch, heads, head_dim, s, t, n, q_ld, k_ld, vt_ld, kip_ld, vtip_ld, o_ld, layer,
+                 num_steps, step_ptr=None, name="ip_attention") -> Call:
+    """msdi_attention_decoupled: out[b] = softmax(q[b] k[b]^T) v[b] + sc * softmax(q[b] k_ip[b]^T) v_ip[b] per query, two independent
+    softmaxes in one launch, sc = scales[*step_ptr][layer] (minsdtf_amd/ipadapter.py).  q bf16 [batch][s][q_ld] carrying scale *
+    log2(e), k bf16 [batch][t][k_ld], vt bf16 [batch][heads * head_dim][vt_ld], k_ip bf16 [batch][n][kip_ld], vt_ip bf16
+    [batch][heads * head_dim][vtip_ld], scales fp32 [num_steps][16], out bf16 [batch][s][o_ld]."""
+    lib = _lib_ipadapter.load()
+    a = _lib_ipadapter.MsdiAttentionDecoupled()
+    a.q, a.k, a.vt, a.k_ip, a.vt_ip, a.out = _p(q), _p(k), _p(vt), _p(k_ip), _p(vt_ip), _p(out)
+    a.scales, a.step_ptr = _p(scales), _p(step_ptr)
+    a.batch, a.heads, a.head_dim, a.s, a.t, a.n = int(batch), int(heads), int(head_dim), int(s), int(t), int(n)
+    a.q_ld, a.k_ld, a.vt_ld, a.kip_ld, a.vtip_ld, a.o_ld = int(q_ld), int(k_ld), int(vt_ld), int(kip_ld), int(vtip_ld), int(o_ld)
+    a.layer, a.num_steps = int(layer), int(num_steps)
+    return Call(lib.msdi_attention_decoupled, (C.byref(a),), name, keep=a, check=_lib_ipadapter.check)
 
 
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:

@@ -34,6 +34,7 @@ import torch
 
 from . import _lib, engine, ops
 from . import control as control_mod
+from . import ipadapter as ipadapter_mod
 from . import hires as hires_mod
 from . import dynthresh as dynthresh_mod
 from . import hypertile as hypertile_mod
@@ -79,8 +80,9 @@ class DenoiseEngine:
     def __init__(self, unet: DiffusionModel, B: int, t_cond: int, t_uncond: int, num_steps: int, guidance: float,
                  guidance_rescale: float, control_net: Optional[ControlNet] = None, hint_net: Optional[HintNet] = None,
                  use_graph: bool = True, streams: Optional[int] = None, inpaint: bool = False, tcd: bool = False,
-                 control_nets=(), **options):
+                 control_nets=(), ip_adapter=None, **options):
         """`options`: the fields of jobopts.EngineOptions as a caller gives them; kept as `options` and each as its own attribute.
+        `ip_adapter`: the models.IPAdapter of an engine built with ip_tokens = N - a model object, not an option.
         `control_nets`: the (ControlNet, HintNet) pairs of the units behind the first of an engine built with control_units = N -
         model objects, not options: N - 1 of them (unit 0 is `control_net` / `hint_net`)."""
         unet._require_weights()
@@ -95,6 +97,13 @@ class DenoiseEngine:
         if len(self.control_nets) != max(self.control_units, 1 if control_net is not None else 0):
             raise ValueError(f"control: an engine of {self.control_units} unit(s) takes {max(self.control_units - 1, 0)} further "
                              f"(ControlNet, HintNet) pair(s) as control_nets, got {len(tuple(control_nets))}")
+        self.ip_model = ip_adapter
+        if (ip_adapter is None) != (self.ip_tokens == 0) or (ip_adapter is not None and ip_adapter.tokens != self.ip_tokens):
+            raise ValueError(f"ip_adapter: an engine of ip_tokens = {self.ip_tokens} takes a models.IPAdapter of that many image tokens as "
+                             f"ip_adapter, got {None if ip_adapter is None else ip_adapter.tokens}")
+        if self.ip_tokens:
+            for t in (t_cond, t_uncond) if guidance > 0.0 else (t_cond,):
+                ipadapter_mod.check_context(t, self.ip_tokens)
         self.region_attn = self.region_mode == "attention"   # ("latent" without regions)
         if self.reference is not None and guidance > 0.0 and t_cond != t_uncond:
             raise ValueError("reference_only: the negative prompt must have the conditional context's token length "
@@ -189,6 +198,15 @@ class DenoiseEngine:
         engine.emit_time_embedding(e_t, self.temb_in, num_steps, table_u, encoder_only=False)
         self.ctx_in: Dict[str, torch.Tensor] = {}
         ctx_kv_u, ctx_kv_c = {}, {}
+        # ip_tokens (N, or 0): the image tokens of an IP-Adapter job, fp32 [nb][N][768] per pass (a per-call upload: the unconditional
+        # rows carry the tokens of the zero embedding, the conditional rows the picture's), their K / V^T for the 16 attn2 layers
+        # recorded here once (engine.emit_ip_kv, the adapter's weights) - constant over the steps, nothing of it runs per step
+        self.ip_in: Dict[str, torch.Tensor] = {}
+        self._ip_kv: dict = {}
+        e_ip = None
+        if self.ip_tokens:
+            self.ip_model._require_weights()
+            e_ip = engine.Emitter(prep, self.ip_model._W)
         e_c = None
         table_c = total_c = None
         # control units (minsdtf_amd/control.py): every unit behind the first has its own time-embedding table, context K/V and hint,
@@ -223,6 +241,12 @@ class DenoiseEngine:
             c16 = engine.Act(prep.alloc(nb * t * 768 * 2), nb, t, 1, 768)
             prep.rec(ops.cast_f32_to_bf16, x=st, out=c16.buf, n=nb * t * 768, name=f"context.{tag}.bf16")
             ctx_kv_u[tag] = engine.emit_context_kv(e_u, c16, engine.UNET_ATTN_LAYERS, prep)
+            if e_ip is not None:
+                N = self.ip_tokens
+                self.ip_in[tag] = torch.zeros(nb, N, 768, dtype=torch.float32, device=dev)
+                tok16 = engine.Act(prep.alloc(nb * N * 768 * 2), nb, N, 1, 768)
+                prep.rec(ops.cast_f32_to_bf16, x=self.ip_in[tag], out=tok16.buf, n=nb * N * 768, name=f"ip_tokens.{tag}.bf16")
+                self._ip_kv[tag] = engine.emit_ip_kv(e_ip, tok16, engine.UNET_ATTN_LAYERS, prep)
             if self.has_control:
                 ctx_kv_c[tag] = engine.emit_context_kv(e_c, c16, engine.ENCODER_ATTN_LAYERS, prep)
                 for n, e_n in enumerate(e_cn):
@@ -281,6 +305,8 @@ class DenoiseEngine:
         self.pag_w = torch.zeros(2, h, w, dtype=torch.float32, device=dev) if self.pag else None
         # control_units (N, or 0): the per-step scale table of the N units, fp32 [num_steps][N][13][2] (control.table), a per-call upload
         self.cn_scales = torch.zeros(self.num_steps, self.control_units, 13, 2, dtype=torch.float32, device=dev) if self.control_units else None
+        # ip_tokens: the per-step scale table of the image prompt, fp32 [num_steps][16] (ipadapter.table), a per-call upload
+        self.ip_scales = torch.zeros(self.num_steps, 16, dtype=torch.float32, device=dev) if self.ip_tokens else None
         self.branches = []
         step = None
         # ControlNet beside the UNet's down path: its encoder reads the same latent and is independent of the UNet until the
@@ -351,6 +377,10 @@ class DenoiseEngine:
             kw.update(window=self.hypertile[:2], window_depth=self.hypertile[2])
         if sag_ws is not None:   # this pass holds the u rows (the c rows without guidance) in its first B rows
             kw.update(sag=(self.sag_A, sag_ws, 0, B))
+        # ip_tokens: every attn2 of the UNet (not of a ControlNet's encoder) is ONE msdi_attention_decoupled launch over the text
+        # keys and this pass's image-token K / V^T, its scale read from row *step_ptr of `ip_scales` (minsdtf_amd/ipadapter.py)
+        if self.ip_tokens:
+            kw.update(ip=(self._ip_kv[tag], self.ip_tokens, self.ip_scales, self.num_steps))
         return engine.UNetVariant(**kw)
 
     def _build_tail(self, step, guidance, guidance_rescale, inpaint, tcd) -> "engine.Plan":
@@ -546,7 +576,7 @@ class DenoiseEngine:
 
     def prepare(self, contexts: Dict[str, np.ndarray], noise: np.ndarray, scheduler: Scheduler, timesteps,
                 start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None,
-                regions=None, pag_scale=None, reference=None, sag=None, dynamic_threshold=None, control=None) -> None:
+                regions=None, pag_scale=None, reference=None, sag=None, dynamic_threshold=None, control=None, ip_adapter=None) -> None:
         """Upload the per-call inputs and run the preparation plan.  Every array may be a host array or a (device) tensor.
         noise = None: the start latent is already in `self.latent` (written there by stream-ordered device work queued before
         this call: the hand-off of a hires job), nothing is uploaded for it.
@@ -568,7 +598,25 @@ class DenoiseEngine:
         in rows start_index ..) and the 32 bytes of dynthresh.params are per-call uploads too.
         control = (table, hints) of an engine built with control_units = N: the scale table fp32 [num_steps][N][13][2] (control.table
         over this engine's num_steps: its rows are the step counter's, whatever `start_index` is) and the N - 1 conditioning
-        pictures of the further units, each like `hint_image`, are per-call uploads too: weights, ranges and modes re-record nothing."""
+        pictures of the further units, each like `hint_image`, are per-call uploads too: weights, ranges and modes re-record nothing.
+        ip_adapter = (tokens_u, tokens_c, table) of an engine built with ip_tokens = N: the image tokens (N, 768) of the unconditional
+        and of the conditional rows and the scale table fp32 [num_steps][16] (ipadapter.table over this engine's num_steps) are
+        per-call uploads too: another picture, weight, range or weight type re-records nothing."""
+        if (ip_adapter is None) != (self.ip_scales is None):
+            raise ValueError("prepare: `ip_adapter` goes with an engine built with ip_tokens=N, and only with one")
+        if self.ip_scales is not None:
+            tok_u, tok_c, tab = (_f32_tensor(a) for a in ip_adapter)
+            want = (self.ip_tokens, 768)
+            if tuple(tab.shape) != tuple(self.ip_scales.shape) or tuple(tok_u.shape) != want or tuple(tok_c.shape) != want:
+                raise ValueError(f"prepare: image tokens of shapes {tuple(tok_u.shape)}, {tuple(tok_c.shape)} and a table of shape "
+                                 f"{tuple(tab.shape)}, this engine's are {want} and {tuple(self.ip_scales.shape)}")
+            self.ip_scales.copy_(tab)
+            for tag, dst in self.ip_in.items():
+                if tag == "both":   # the unconditional rows first
+                    dst[:self.B].copy_(tok_u.to(dst.device).expand(self.B, -1, -1))
+                    dst[self.B:].copy_(tok_c.to(dst.device).expand(dst.shape[0] - self.B, -1, -1))
+                else:
+                    dst.copy_((tok_u if tag == "uncond" else tok_c).to(dst.device).expand(dst.shape[0], -1, -1))
         if (control is None) != (self.cn_scales is None):
             raise ValueError("prepare: `control` goes with an engine built with control_units=N, and only with one")
         if self.cn_scales is not None:
@@ -718,6 +766,9 @@ class StableDiffusionBase:
         self._engines: Dict[tuple, DenoiseEngine] = {}
         self.denoise_streams = None  # None / 1: cond+uncond as one fused batch; 2: two concurrent HIP streams
         self.text_frontend = None
+        # any callable picture -> (1024,) CLIP image embedding (ViT-H/14): what ip_adapter={"image": ...} goes through, as
+        # text_frontend is for string prompts; the vision tower itself is not part of this package
+        self.image_prompt_encoder = None
         self.bpe_path = None  # local copy of CLIP's bpe_simple_vocab_16e6.txt.gz (or $MSD_BPE_PATH) for string prompts
         self.unconditional_context = None  # (77, 768) embedding of the empty prompt, supplied by the caller
         # False (default, the reference's meaning of batch_size: stable_diffusion.py:384-397 tiles one prompt to the batch THIS
@@ -738,7 +789,8 @@ class StableDiffusionBase:
         hypertile.HypertileSpec / dict for windowed self-attention; ``sag``: None, or a sag.SagSpec / dict for self-attention guidance;
         ``dynamic_threshold``: None, or a dynthresh.DynThreshSpec / dict for dynamic thresholding; ``control`` (through **kw, with
         ``control_net_image``): None, or one control.ControlUnit / dict or a list of them - weight, start / end, mode and further
-        ControlNets (see generate_image)."""
+        ControlNets (see generate_image); ``ip_adapter`` (through **kw): None, or an ipadapter.IPAdapterSpec / dict for an IP-Adapter
+        image prompt (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
@@ -750,7 +802,8 @@ class StableDiffusionBase:
     def image_to_image(self, prompt, negative_prompt=None, batch_size=1, num_steps=50, unconditional_guidance_scale=7.5,
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
                        reference_image_strength=0.8, guidance_rescale=0.7, callback=None, **kw):
-        """Reference :111-139.  ``control`` (through **kw, with ``control_net_image``): the ControlNet units of generate_image."""
+        """Reference :111-139.  ``control`` (through **kw, with ``control_net_image``): the ControlNet units of generate_image;
+        ``ip_adapter`` (through **kw): its IP-Adapter image prompt."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
@@ -762,7 +815,8 @@ class StableDiffusionBase:
                 embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
                 reference_image_strength=0.8, inpaint_mask=None, mask_blur_strength=None, guidance_rescale=0.7,
                 callback=None, **kw):
-        """Reference :141-175.  ``control`` (through **kw, with ``control_net_image``): the ControlNet units of generate_image."""
+        """Reference :141-175.  ``control`` (through **kw, with ``control_net_image``): the ControlNet units of generate_image;
+        ``ip_adapter`` (through **kw): its IP-Adapter image prompt."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
@@ -980,7 +1034,7 @@ class StableDiffusionBase:
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
                        callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None,
                        tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, sag=None, dynamic_threshold=None,
-                       control=None):
+                       control=None, ip_adapter=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
@@ -1059,7 +1113,30 @@ class StableDiffusionBase:
         them to the skips, the scales read from a per-step device table - so weights, ranges and modes are per-call uploads and the
         engine is keyed by the number of units alone.  Works with whatever a ControlNet job works with: every sampler, a TCD pipeline,
         image_to_image, inpainting, denoise_streams = 2, a negative prompt of another length, shard_batch and host_loop=True.
-        ``control`` = None is the job as it was, bit for bit."""
+        ``control`` = None is the job as it was, bit for bit.
+        ``ip_adapter`` (an ipadapter.IPAdapterSpec or a dict {"embeds": (1024,) CLIP image embedding | "tokens": (N, 768) image tokens |
+        "image": a picture, "weight": 1.0, "start": 0.0, "end": 1.0, "weight_type": "linear" | "style" | "composition" | {attention
+        block: factor}, "path": an IP-Adapter checkpoint | "model": a models.IPAdapter}): an IP-Adapter image prompt.  Every
+        cross-attention of the UNet also attends to the N image tokens through the adapter's own to_k_ip / to_v_ip, decoupled from the
+        text attention: out = softmax(q K_text^T) V_text + s softmax(q K_ip^T) V_ip as ONE msdi_attention_decoupled launch per block,
+        s read from a per-step device table (``weight`` inside [``start``, ``end``) by diffusers' rule, times the block factors of
+        ``weight_type``: "style" is up_blocks.1 only, "composition" down_blocks.2.attentions.1 only).  The tokens are the adapter's
+        projection of the embedding, made on the host once per call; the unconditional rows take the zero embedding's tokens.
+        ``image`` needs ``self.image_prompt_encoder`` (any callable picture -> (1024,) embedding); ``tokens`` bypasses the projection
+        (the entry for "plus" adapters).  Tokens and table are per-call uploads, so the engine is keyed by N and the adapter alone and
+        one engine serves every picture, weight and schedule.  Works with every sampler, a TCD pipeline, ``control_net_image`` with or
+        without ``control`` (the ControlNet's own encoder stays plain), image_to_image, inpainting, ``dynamic_threshold``,
+        shard_batch and host_loop=True; not with regions, pag, sag, reference_only, hypertile, tiled, hires or denoise_streams = 2,
+        nor with prompts of more than 77 tokens.  One adapter and one picture per job.  A spec whose table is all 0 (weight 0) is the
+        plain job on the plain engine; ``ip_adapter`` = None is the job as it was, bit for bit."""
+        ipa = ipadapter_mod.parse(ip_adapter)   # (ValueError for a bad description)
+        ipa_tab = None
+        if ipa is not None:
+            ipadapter_mod.refuse(dict(regions=regions, pag=pag, sag=sag, reference_only=reference_only, hypertile=hypertile, tiled=tiled,
+                                      hires=hires), self.denoise_streams)
+            ipa_tab = ipadapter_mod.table(ipa, num_steps)
+            if not ipa_tab.any():
+                ipa = ipa_tab = None   # (every scale 0: the plain job, on the plain engine)
         cu = control_mod.parse(control)   # (ValueError for a bad description)
         if cu is not None and control_net_image is None:
             raise ValueError("control: the units scale the ControlNet of `control_net_image`, which is missing")
@@ -1127,6 +1204,12 @@ class StableDiffusionBase:
         B = batch_size
         context = self._batch_of(encoded_text, B, 2)
         unconditional_context = self._negative_context(negative_prompt, negative_embedding, B)
+        ipa_model = ipa_tok = None
+        if ipa is not None:   # the adapter, its tokens of the picture and of the zero embedding: (N, 768) each
+            ipa_model, ipa_tok = self._ip_inputs(ipa)
+            for t in (context.shape[1], unconditional_context.shape[1]) if float(unconditional_guidance_scale) > 0.0 else (context.shape[1],):
+                ipadapter_mod.check_context(t, ipa_model.tokens)
+            engine_opts = dict(engine_opts, ip_tokens=ipa_model.tokens, ip_adapter=ipa_model)   # (a model object beside the options)
         if geo is not None:
             noise = (self._get_initial_diffusion_noise(B, seed, geo.height, geo.width) if diffusion_noise is None
                      else self._batch_of(diffusion_noise, B, 3))
@@ -1206,11 +1289,13 @@ class StableDiffusionBase:
                 latent = self._host_loop_sampler(context, unconditional_context, start_latent, g, phi, hint, callback, sched, start_index,
                                                  sampler_z, ip, region_w=region_w, pag=pg, hypertile=ht_key, sag=sg, dynthresh=dt,
                                                  control=None if cu is None else (cu_tab, cu_nets, cu_hints),
+                                                 ip=None if ipa is None else (ipa_model, ipa_tok, ipa_tab),
                                                  reference=None if ref is None else (ref, ref_in, reference_mod.rates(sched, start_index)))
             else:
                 latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending, ip,
                                          region_w=region_w, pag=pg, hypertile=ht_key, sag=sg, dynthresh=dt,
                                          control=None if cu is None else (cu_tab, cu_nets, cu_hints, start_index),
+                                         ip=None if ipa is None else (ipa_model, ipa_tok, ipa_tab, start_index),
                                          reference=None if ref is None else (ref, ref_in, reference_mod.rates(self.scheduler, start_index)))
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
@@ -1239,6 +1324,8 @@ class StableDiffusionBase:
             for n, hi in enumerate(cu_hints):
                 per_sample[f"control_hint{n + 1}"] = hi
             shared["control_table"] = cu_tab
+        if ipa is not None:   # the two token sets and the table: whole on every rank
+            shared["ip_tokens"], shared["ip_table"] = np.stack(ipa_tok, axis=0), ipa_tab
 
         def local(c, u, z, a):
             """This rank's slice of the batch: one denoise pass -> decode; returns a device tensor."""
@@ -1253,7 +1340,8 @@ class StableDiffusionBase:
                                           regions=a.get("region_w"), pag_scale=None if pg is None else pg.scale,
                                           reference=None if ref is None else (a["ref_z"], a["ref_noise"], ref.fidelity), sag=sg,
                                           dynamic_threshold=dt,
-                                          control=None if cu is None else (a["control_table"], [a[f"control_hint{n + 1}"] for n in range(len(cu) - 1)])))
+                                          control=None if cu is None else (a["control_table"], [a[f"control_hint{n + 1}"] for n in range(len(cu) - 1)]),
+                                          ip_adapter=None if ipa is None else (a["ip_tokens"][0], a["ip_tokens"][1], a["ip_table"])))
             if return_latent:
                 return eng.latent
             if blend_pixels:   # pixel blend in fp32 before the uint8 cast
@@ -1297,6 +1385,36 @@ class StableDiffusionBase:
                 for m in cache[unit.path]:
                     m.compile(jit_compile=True)
         return cache[unit.path]
+
+    def _ip_inputs(self, ipa):
+        """(the models.IPAdapter of an image-prompt job, (tokens_u, tokens_c)): its own `model`, or the checkpoint `path` loaded once
+        and kept on the pipeline by path; the (N, 768) fp32 tokens of the unconditional rows (the zero embedding's, or
+        `negative_tokens` / zeros beside `tokens`) and of the conditional rows (the picture's)."""
+        model = ipa.model
+        if model is None:
+            if ipa.path is None:
+                raise ValueError("ip_adapter: one of `path` (an IP-Adapter checkpoint) and `model` (a models.IPAdapter) is needed")
+            from .models import IPAdapter
+
+            cache = self.__dict__.setdefault("_ip_adapters_by_path", {})
+            if ipa.path not in cache:
+                cache[ipa.path] = IPAdapter(path=ipa.path, device=getattr(self, "device", None))
+            model = cache[ipa.path]
+        model._require_weights()
+        if ipa.tokens is not None:
+            if ipa.tokens.shape[0] != model.tokens:
+                raise ValueError(f"ip_adapter: {ipa.tokens.shape[0]} `tokens`, the adapter takes {model.tokens}")
+            neg = np.zeros_like(ipa.tokens) if ipa.negative_tokens is None else ipa.negative_tokens
+            return model, (np.asarray(neg, dtype=np.float32), np.asarray(ipa.tokens, dtype=np.float32))
+        embeds = ipa.embeds
+        if embeds is None:
+            if self.image_prompt_encoder is None:
+                raise ValueError("ip_adapter: `image` needs StableDiffusion.image_prompt_encoder (a callable picture -> (1024,) CLIP image "
+                                 "embedding), which is not set: pass `embeds` (the embedding) or `tokens` (the image tokens) instead")
+            embeds = np.asarray(self.image_prompt_encoder(ipa.image), dtype=np.float64).reshape(-1)
+            if embeds.shape != (ipadapter_mod.EMBED_DIM,) or not np.isfinite(embeds).all():
+                raise ValueError(f"ip_adapter: image_prompt_encoder returned shape {embeds.shape}, expected a finite ({ipadapter_mod.EMBED_DIM},)")
+        return model, (model.project(np.zeros(ipadapter_mod.EMBED_DIM)), model.project(embeds))
 
     def _reference_inputs(self, ref, h, w, seed):
         """(z_ref, n_ref) of a reference-only job, each (1, h, w, 4) float32: the given latent, or the picture through the VAE
@@ -1488,9 +1606,10 @@ class StableDiffusionBase:
                              + ", ".join(f"{w}: {n}" for w, n in lengths))
         return np.stack(encoded, axis=0), reg.weights()
 
-    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, control_nets=(), **opts) -> tuple:
+    def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, control_nets=(), ip_adapter=None, **opts) -> tuple:
         """`opts` as _engine takes them: one at its default (None) adds nothing to the key, an unknown name is a TypeError.
-        `control_nets`: the further units' (ControlNet, HintNet) pairs - which objects they are and their weights' versions."""
+        `control_nets`: the further units' (ControlNet, HintNet) pairs - which objects they are and their weights' versions.
+        `ip_adapter`: the models.IPAdapter of an image-prompt job - which object it is and its weights' version."""
         # the engine's plans (and captured hipGraphs) hold raw addresses of the packed weights: a set_weights() /
         # load_synthetic() / LoRA reload on any of the models it was built from must retire it
         base = self.diffusion_model
@@ -1499,14 +1618,15 @@ class StableDiffusionBase:
         key = (B, tc, tu, steps, g, phi, control, self.denoise_streams, inpaint, self.active_tcd, wver, engine.GN_EPOCH, opts.get("sampler"))
         key = key if unet is base else key + ((unet.h, unet.w),)   # (a hires job's second size: a view of the same weights)
         key += tuple(("control_net", id(cn), cn.weights_version, id(hn), hn.weights_version) for cn, hn in control_nets)
+        key += (("ip_adapter", id(ip_adapter), ip_adapter.weights_version),) if ip_adapter is not None else ()
         return key + EngineOptions.of(**opts).key()
 
-    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, control_nets=(), **opts) -> DenoiseEngine:
+    def _engine(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, control_nets=(), ip_adapter=None, **opts) -> DenoiseEngine:
         """The resident engine of this shape, built if need be.  `opts`: `unet` (the UNet of another size: a hires job's second pass) and
         DenoiseEngine's options (jobopts.EngineOptions).  `job_keys`: the keys of every engine the current job uses (default: this one
         alone).  The engines' arenas are the big allocations, so whatever the current job does not need goes BEFORE anything is built: a
         re-recording (another shape, new weights, a cluster-GroupNorm give-up: GN_EPOCH) never needs room for more than the job's own engines."""
-        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, control_nets=control_nets, **opts)
+        key = self._engine_key(B, tc, tu, steps, g, phi, control, inpaint, control_nets=control_nets, ip_adapter=ip_adapter, **opts)
         keep = {key} | set(job_keys or ())
         if any(k not in keep for k in self._engines):
             import gc
@@ -1524,14 +1644,16 @@ class StableDiffusionBase:
                                 hint_net=self.hint_net if control else None, use_graph=self.jit_compile,
                                 # (`regions` always as an int: what the residency tests read off this call for a plain job)
                                 streams=self.denoise_streams, inpaint=inpaint, tcd=self.active_tcd,
-                                **(dict(control_nets=control_nets) if control_nets else {}), **dict(opts, regions=opts.get("regions") or 0))
+                                **(dict(control_nets=control_nets) if control_nets else {}),
+                                **(dict(ip_adapter=ip_adapter) if ip_adapter is not None else {}), **dict(opts, regions=opts.get("regions") or 0))
             self._engines[key] = eng
         return eng
 
     def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None,
-                   region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None):
+                   region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None, ip=None):
         """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479).  control = (table, the further units'
-        (ControlNet, HintNet) pairs, their hint pictures, the first executed row) of a job with ControlNet units."""
+        (ControlNet, HintNet) pairs, their hint pictures, the first executed row) of a job with ControlNet units.
+        ip = (the models.IPAdapter, (tokens_u, tokens_c), table, the first executed row) of a job with an image prompt."""
         if timesteps is None:
             timesteps = self.scheduler.timesteps[::-1]
         batch_size = latent.shape[0]
@@ -1552,8 +1674,10 @@ class StableDiffusionBase:
             dt_step = None if dynthresh is None else (dynthresh, float(dt_tab[iteration, 0]), float(dt_tab[iteration, 1]))
             # (a job with ControlNet units: row control[3] + iteration of its table, the device step counter's row)
             cu_step = None if control is None else (cu_units, control[0][control[3] + iteration])
+            # (a job with an image prompt: row ip[3] + iteration of its table, the device step counter's row)
+            ip_step = None if ip is None else (ip[0], ip[1], ip[2][ip[3] + iteration])
             latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag, ref_step, hypertile,
-                                      sag_step, dt_step, cu_step)
+                                      sag_step, dt_step, cu_step, ip_step)
             latent = self.scheduler.step(latent, timestep, latent_prev)
             if inpaint is not None:   # reference :469-475
                 init_latent, noise, latent_mask = inpaint
@@ -1573,7 +1697,7 @@ class StableDiffusionBase:
         return units
 
     def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None, reference=None,
-                    hypertile=None, sag=None, dynthresh=None, control=None):
+                    hypertile=None, sag=None, dynthresh=None, control=None, ip=None):
         """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
         A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
         predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host); in mode "attention"
@@ -1586,7 +1710,15 @@ class StableDiffusionBase:
         rescale follows - the device step's order.
         A job with ControlNet units passes ([(ControlNet, hint activation), ...], the step's table row fp32 [N][13][2]): the 13 arrays
         of every unit's predict_on_batch are scaled and summed (control.scale_host) with column 0 for the unconditional and column
-        1 for the conditional prediction."""
+        1 for the conditional prediction.
+        A job with an image prompt passes (the models.IPAdapter, (tokens_u, tokens_c), the step's table row fp32 [16]): every UNet
+        forward is predict_ip, with the zero embedding's tokens for the unconditional and the picture's for the conditional one."""
+        def unet(x, half):
+            """The UNet's forward of one half (0: unconditional) over [latent, t_emb, context(, 13 controls)]."""
+            if ip is not None:
+                return self.diffusion_model.predict_ip(x, ip[0], ip[1][half], ip[2])
+            return self.diffusion_model.predict_on_batch(x)
+
         def guided(u, c):
             if dynthresh is not None:
                 spec_dt, g_i, m_i = dynthresh
@@ -1631,13 +1763,13 @@ class StableDiffusionBase:
             if hypertile is not None:
                 return self.diffusion_model.predict_windowed([latent, t_emb, ctx], hypertile[:2], hypertile[2])
             if hint is None:
-                return self.diffusion_model.predict_on_batch([latent, t_emb, ctx])
+                return unet([latent, t_emb, ctx], half)
             if control is not None:
                 units, row = control
                 controls = control_mod.scale_host([cn.predict_on_batch([latent, t_emb, ctx, hi]) for cn, hi in units], row[:, :, half])
-                return self.diffusion_model.predict_on_batch([latent, t_emb, ctx] + list(controls))
+                return unet([latent, t_emb, ctx] + list(controls), half)
             controls = self.control_net.predict_on_batch([latent, t_emb, ctx, hint])
-            return self.diffusion_model.predict_on_batch([latent, t_emb, ctx] + list(controls))
+            return unet([latent, t_emb, ctx] + list(controls), half)
 
         regional = isinstance(context, (list, tuple))   # (its region prompts run in front of the unconditional one)
         if regional and isinstance(region_w, (list, tuple)):   # mode "attention": the level planes, one forward for all regions
@@ -1654,9 +1786,11 @@ class StableDiffusionBase:
         return guided(u, c)
 
     def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
-                           inpaint=None, region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None):
+                           inpaint=None, region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None,
+                           ip=None):
         """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`.
-        control = (table, the further units' (ControlNet, HintNet) pairs, their hint pictures) of a job with ControlNet units."""
+        control = (table, the further units' (ControlNet, HintNet) pairs, their hint pictures) of a job with ControlNet units.
+        ip = (the models.IPAdapter, (tokens_u, tokens_c), table) of a job with an image prompt."""
         batch_size = latent.shape[0]
         hint = self.hint_net.predict_on_batch(hint_image) if hint_image is not None else None
         cu_units = None if control is None else self._host_control_units(hint, control)
@@ -1670,7 +1804,8 @@ class StableDiffusionBase:
                                  None if reference is None else reference + (i,), hypertile,
                                  None if sag is None else (sag, float(np.float32(tab[i, 0])), float(np.float32(tab[i, 1]))),
                                  None if dynthresh is None else (dynthresh, float(dt_tab[i - start, 0]), float(dt_tab[i - start, 1])),
-                                 None if control is None else (cu_units, control[0][i]))
+                                 None if control is None else (cu_units, control[0][i]),
+                                 None if ip is None else (ip[0], ip[1], ip[2][i]))
             z = step_noise[:, i] if step_noise is not None else None
             x, prev = smp.host_step(tab[i], x, e, prev, z)
             if inpaint is not None:   # the row's own alpha / sigma, as in the device kernel
