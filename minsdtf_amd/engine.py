@@ -1285,3 +1285,52 @@ def emit_text_encoder(e: Emitter, x: Act, n_layers: int, heads: int = 12) -> Act
     out = e.layer_norm(x, "text_model.final_layer_norm")
     p.free(x)
     return out
+
+
+def emit_clip_vision(e: Emitter, pixels, layers: int, penultimate: bool = False, B: int = 1, embeds=None, heads: int = wtab.VIT_HEADS):
+    """CLIP ViT-H/14 vision tower with its projection (transformers' CLIPVisionModelWithProjection): pixels fp32 [B][224][224][3] on
+    the 0 .. 255 scale -> msdv_patch_embed (normalisation, patch conv, class token, position embedding, pre-LayerNorm), then
+    `layers` x [LN -> self-attention over the 257 tokens (q/k/v/out Dense with bias, 16 heads of 80, not causal) -> +x -> LN -> fc1
+    (fp32 out) -> msdv_gelu (erf GELU, the one rounding) -> fc2 -> +x], then msdv_pool_project (post-LayerNorm of the class token,
+    the 1280 -> 1024 projection) into `embeds`, fp32 [B][1024]: 2 + 8 * layers launches.  penultimate: the last layer and the pooled
+    head are not built and the returned Act is the last layer's INPUT (diffusers' hidden_states[-2]).
+    Returns the bf16 [B][257][1280] Act of the last hidden state built."""
+    from . import vision
+
+    p = e.p
+    T, C = wtab.VIT_TOKENS, wtab.VIT_DIM
+    d = C // heads
+    Tp = (T + 7) // 8 * 8
+    emb = "vision_model.embeddings."
+    scale, shift = vision.pixel_affine()
+    x = p.act(B, T, 1, C)
+    p.rec(ops.patch_embed, pixels=pixels, w=e.W[emb + "patch_embedding.w"], cls=e.W[emb + "class_embedding"],
+          pos=e.W[emb + "position_embedding"], gamma=e.W["vision_model.pre_layrnorm.g"], beta=e.W["vision_model.pre_layrnorm.b"],
+          out=x.buf, batch=B, scale=scale, shift=shift, w_ld=(wtab.VIT_PATCH ** 2 * 3 + 7) // 8 * 8, o_ld=C, eps=EPS,
+          name="vision_model.embeddings")
+    for i in range(layers - 1 if penultimate else layers):
+        ln = f"vision_model.encoder.layers.{i}"
+        h = e.layer_norm(x, ln + ".layer_norm1")
+        q, k = p.act(B, T, 1, C), p.act(B, T, 1, C)
+        vt = p.alloc(B * C * Tp * 2)
+        e.conv(h, ln + ".self_attn.qkv", 3 * C, split=(C, C, q.buf, k.buf, vt, Tp))
+        p.free(h)
+        o = p.act(B, T, 1, C)
+        p.rec(ops.attention, q=q.buf, k=k.buf, vt=vt, out=o.buf, batch=B, heads=heads, head_dim=d, s=T, t=T, q_ld=C, k_ld=C,
+              vt_ld=Tp, o_ld=C, scale=float(d) ** -0.5, causal=False, name=ln + ".self_attn")
+        p.free(q, k, vt)
+        x2 = e.conv(o, ln + ".self_attn.out_proj", C, residual=x)
+        p.free(o, x)
+        h = e.layer_norm(x2, ln + ".layer_norm2")
+        f32 = e.conv(h, ln + ".mlp.fc1", wtab.VIT_MLP, out_dtype=ops.OUT_F32)   # bias inside, no rounding: msdv_gelu's input
+        p.free(h)
+        f = p.act(B, T, 1, wtab.VIT_MLP)
+        p.rec(ops.gelu, x=f32.buf, out=f.buf, rows=B * T, cols=wtab.VIT_MLP, name=ln + ".mlp.gelu")
+        p.free(f32)
+        x = e.conv(f, ln + ".mlp.fc2", C, residual=x2)
+        p.free(f, x2)
+    if not penultimate and embeds is not None:   # (embeds None: the caller wants the last hidden state alone)
+        p.rec(ops.pool_project, x=x.buf, gamma=e.W["vision_model.post_layernorm.g"], beta=e.W["vision_model.post_layernorm.b"],
+              w=e.W["visual_projection.w"], out=embeds, batch=B, x_stride=T * C, w_layout=e.w_layout("visual_projection.w"), eps=EPS,
+              name="visual_projection")
+    return x

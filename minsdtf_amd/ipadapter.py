@@ -54,7 +54,8 @@ CHECKPOINT_WIDTHS = (320, 320, 640, 640, 1280, 1280) + (1280,) * 3 + (640,) * 3 
 @dataclass
 class IPAdapterSpec:
     """Exactly one of ``embeds`` (the (1024,) CLIP image embedding), ``tokens`` ((N, 768) image tokens, past the projection: the
-    entry for "plus" adapters) and ``image`` (a picture, through StableDiffusion.image_prompt_encoder); ``weight``: a finite float;
+    entry for "plus" adapters) and ``image`` (a picture, through StableDiffusion.image_prompt_encoder or the pipeline's own
+    clip_vision tower); ``weight``: a finite float;
     ``start`` / ``end``: the share of the steps the adapter acts on, 0 <= start <= end <= 1; ``weight_type``: one of WEIGHT_TYPES or
     a dict {attention block name: factor}; at most one of ``path`` (an IP-Adapter checkpoint) and ``model`` (a models.IPAdapter).
     ``negative_tokens``: with ``tokens``, the (N, 768) tokens of the unconditional rows (default: zeros)."""

@@ -85,6 +85,7 @@ class Packed:
     norm: Optional[str] = None            # (.lnw) the LayerNorm folded in: its gamma is the parts' colscale
     colsum: Optional[str] = None          # (.lnw) the .lncs key: float64 row sums of this matrix's ROUNDED rows
     lnb: Optional[Tuple[str, str]] = None  # (.lnw) (the .lnb key, packed key of the LayerNorm beta)
+    pad_k: Optional[int] = None           # (ROWS) stored row length when K is no multiple of 8: the columns K .. pad_k - 1 are zeros
 
     @property
     def dtype(self) -> str:
@@ -92,6 +93,8 @@ class Packed:
 
     @property
     def stored_shape(self) -> Tuple[int, ...]:
+        if self.pad_k is not None:
+            return (self.shape[0], self.pad_k)
         return (self.shape[1] // 64, self.shape[0], 64) if self.chunk_major else self.shape
 
     @property
@@ -146,6 +149,11 @@ def layout(specs, flags: Flags = Flags()) -> List[Packed]:
         elif has("gamma"):
             vec(n + ".g", "gamma", [Part(n)])
             vec(n + ".b", "beta", [Part(n)])
+        elif n.endswith(".patch_embedding"):
+            # the CLIP vision tower's 14 x 14 / stride-14 patch conv (no bias): K = 588 is no multiple of 8, and msdv_patch_embed
+            # reads 16-byte fragments of a row: rows of 592, the four last columns zeros (the kernel ignores them anyway)
+            e = rows(n + ".w", [Part(n)])
+            e.pad_k = (e.shape[1] + 7) // 8 * 8
         elif n.endswith(".time_emb_proj"):
             # every ResBlock's projection of the time embedding as ONE matrix, in table order (engine.emit_time_embedding):
             # bf16 rows for the MFMA kernel, or the fp32 (1, 1, 1280, sum C_out) of the vector-FMA one

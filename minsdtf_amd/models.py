@@ -13,6 +13,7 @@ DiffusionModel     diffusion_model.py:163-296                     [latent, t_emb
 ImageDecoder       image_decoder.py:22-66                         latent -> (B,8h,8w,3)
 ControlNet         control_net.py:45-118                          [latent, t_emb, context, hint] -> 13 arrays
 HintNet            control_net.py:10-42                           (B,H,W,3) -> (B,H/8,W/8,320)
+ClipVisionEncoder  (transformers CLIPVisionModelWithProjection)    (B,224,224,3) 0..255 -> (B,1024) image_embeds
 =================  =============================================  ==========================
 
 Inputs / outputs at this boundary are host numpy arrays like the reference's; the fused,
@@ -854,5 +855,79 @@ class TextEncoder(HipModel):
         bp.io["emb"].copy_(torch.from_numpy(emb))
         bp.run()
         return bp.host("context")
+
+    __call__ = predict_on_batch
+
+
+class ClipVisionEncoder(HipModel):
+    """CLIP ViT-H/14 vision tower with its projection (transformers' CLIPVisionModelWithProjection; the `image_encoder` that ships with
+    the SD 1.5 IP-Adapters): pixels (B, 224, 224, 3) on the 0 .. 255 scale (vision.preprocess) -> the (B, 1024) float32 image
+    embedding an IP-Adapter projects.  `layers`: how many of the 32 encoder layers are built (tests build 2-layer towers)."""
+    kind = "clip_vision"
+    OUTPUTS = ("image_embeds", "penultimate", "last_hidden_state")
+
+    def __init__(self, layers=wtab.VIT_LAYERS, name=None, path=None, device=None):
+        self.layers = int(layers)
+        super().__init__(name or "clip_vision", device)
+        if path is not None:
+            self.load(path)
+
+    def _table_kw(self):
+        return {"layers": self.layers}
+
+    def count_params(self) -> int:
+        return int(sum(int(np.prod(s.shape)) for s in self._specs))
+
+    def set_state(self, state) -> None:
+        """Adopt a loaded checkpoint (key -> tensor / array under CLIPVisionModelWithProjection's key names; fp16 files load); raises on
+        a missing key or a wrong shape, naming it."""
+        self.set_weights(wtab.clip_vision_arrays(state, self.layers))
+
+    def load(self, path: str) -> None:
+        if not os.path.exists(str(path)):
+            raise ValueError(f"clip_vision: checkpoint {path!r} not found")
+        self.set_state(wtab.read_state_dict(path))
+
+    def load_synthetic(self, seed=0, bias_scale=0.0):
+        """Fill with the seeded synthetic tower (wtab.clip_vision_synthetic_state; `bias_scale` is not used: its biases are always
+        drawn); returns that state - what vision.forward_host takes."""
+        state = wtab.clip_vision_synthetic_state(seed, self.layers)
+        self.set_state(state)
+        return state
+
+    def _build(self, B: int, output: str) -> _BoundPlan:
+        plan = engine.Plan(self.device)
+        e = engine.Emitter(plan, self._W)
+        T, C = wtab.VIT_TOKENS, wtab.VIT_DIM
+        px = plan.alloc(B * wtab.VIT_IMAGE * wtab.VIT_IMAGE * 3 * 4)
+        emb = plan.alloc(B * wtab.VIT_PROJ * 4) if output == "image_embeds" else None
+        x = engine.emit_clip_vision(e, px, self.layers, penultimate=output == "penultimate", B=B, embeds=emb)
+        h32 = None
+        if output != "image_embeds":   # the hidden state leaves as fp32 (the slot of the pooled head: the launch count stays 2 + 8 L)
+            h32 = plan.alloc(B * T * C * 4)
+            plan.rec(ops.cast_bf16_to_f32, x=x.buf, out=h32, n=B * T * C, name=output + ".f32")
+        plan.finalize()
+        bp = _BoundPlan(plan, self._use_graph)
+        bp.io["pixels"] = px.tensor(torch.float32, (B, wtab.VIT_IMAGE, wtab.VIT_IMAGE, 3))
+        bp.io["out"] = emb.tensor(torch.float32, (B, wtab.VIT_PROJ)) if h32 is None else h32.tensor(torch.float32, (B, T, C))
+        return bp
+
+    def predict_on_batch(self, pixels, output="image_embeds"):
+        """pixels (B, 224, 224, 3) or (224, 224, 3), 0 .. 255 -> `image_embeds` (B, 1024) float32; output="penultimate": the
+        (B, 257, 1280) float32 input of the last layer (diffusers' hidden_states[-2], what a "plus" resampler consumes);
+        output="last_hidden_state": the output of the last layer, before the post-LayerNorm."""
+        px = _np32(pixels)
+        px = px[None] if px.ndim == 3 else px
+        if output not in self.OUTPUTS:
+            raise ValueError(f"clip_vision: output {output!r} (one of {self.OUTPUTS})")
+        if px.ndim != 4 or px.shape[1:] != (wtab.VIT_IMAGE, wtab.VIT_IMAGE, 3) or not 1 <= px.shape[0] <= 8:
+            raise ValueError(f"clip_vision: pixels of shape {px.shape} ((B, 224, 224, 3), B = 1 .. 8; vision.preprocess makes them)")
+        if output == "penultimate" and self.layers < 2:
+            raise ValueError("clip_vision: output='penultimate' needs at least 2 layers")
+        B = px.shape[0]
+        bp = self._bound((B, output), lambda: self._build(B, output))
+        bp.io["pixels"].copy_(torch.from_numpy(px))
+        bp.run()
+        return bp.host("out")
 
     __call__ = predict_on_batch

@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
-from . import _lib, _lib_control, _lib_dynthresh, _lib_ext, _lib_ipadapter
+from . import _lib, _lib_control, _lib_dynthresh, _lib_ext, _lib_ipadapter, _lib_vision
 from ._lib import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, OUT_BF16, OUT_F32, OUT_U8  # noqa: F401
 
 
@@ -392,6 +392,41 @@ def ip_attention(*, q, k, vt, k_ip, vt_ip, out, scales, batch, heads, head_dim, 
     a.q_ld, a.k_ld, a.vt_ld, a.kip_ld, a.vtip_ld, a.o_ld = int(q_ld), int(k_ld), int(vt_ld), int(kip_ld), int(vtip_ld), int(o_ld)
     a.layer, a.num_steps = int(layer), int(num_steps)
     return Call(lib.msdi_attention_decoupled, (C.byref(a),), name, keep=a, check=_lib_ipadapter.check)
+
+
+# ---- the vision library (include/minsdtf_hip_vision.h, minsdtf_amd/_lib_vision.py) -------------------------------------------------
+def patch_embed(*, pixels, w, cls, pos, gamma, beta, out, batch, scale, shift, w_ld, o_ld=_lib_vision.WIDTH, eps=1e-5,
+                image=_lib_vision.IMAGE, patch=_lib_vision.PATCH, width=_lib_vision.WIDTH, name="patch_embed") -> Call:
+    """msdv_patch_embed: pixels fp32 [batch][224][224][3] (0 .. 255) -> out bf16 [batch][257][o_ld], the input of layer 0 of the CLIP
+    ViT-H/14 vision tower: x = bf16(fma(pixel, scale[c], shift[c])), the 14 x 14 / stride-14 patch product with w bf16 [1280][w_ld]
+    (k = (ky * 14 + kx) * 3 + c, the columns >= 588 ignored), + pos fp32 [257][1280] (token 0: cls + pos[0]), LayerNorm(gamma, beta).
+    scale / shift: three floats each (vision.pixel_affine)."""
+    lib = _lib_vision.load()
+    a = _lib_vision.MsdvPatchEmbed()
+    a.pixels, a.w, a.cls, a.pos, a.gamma, a.beta, a.out = _p(pixels), _p(w), _p(cls), _p(pos), _p(gamma), _p(beta), _p(out)
+    a.scale[:], a.shift[:] = [float(v) for v in scale], [float(v) for v in shift]
+    a.eps = float(eps)
+    a.batch, a.image, a.patch, a.width, a.w_ld, a.o_ld = int(batch), int(image), int(patch), int(width), int(w_ld), int(o_ld)
+    return Call(lib.msdv_patch_embed, (C.byref(a),), name, keep=a, check=_lib_vision.check)
+
+
+def gelu(*, x, out, rows, cols, ld_in=None, ld_out=None, name="gelu") -> Call:
+    """msdv_gelu: out[r][:cols] = bf16(0.5 x (1 + erf(x / sqrt 2))), x fp32 [rows][ld_in], out bf16 [rows][ld_out]."""
+    lib = _lib_vision.load()
+    return Call(lib.msdv_gelu, (_p(x), _p(out), int(rows), int(cols), int(cols if ld_in is None else ld_in),
+                                int(cols if ld_out is None else ld_out)), name, check=_lib_vision.check)
+
+
+def pool_project(*, x, gamma, beta, w, out, batch, x_stride, w_layout=0, eps=1e-5, width=_lib_vision.WIDTH, proj=_lib_vision.PROJ,
+                 name="pool_project") -> Call:
+    """msdv_pool_project: out fp32 [batch][1024] = LayerNorm(x[b]) w^T, x bf16 rows of 1280 at a stride of x_stride elements (the
+    class token of the last layer), w bf16 [1024][1280] rows (w_layout 0) or their chunk-major image (1); no bias."""
+    lib = _lib_vision.load()
+    a = _lib_vision.MsdvPoolProject()
+    a.x, a.gamma, a.beta, a.w, a.out = _p(x), _p(gamma), _p(beta), _p(w), _p(out)
+    a.x_stride, a.eps = int(x_stride), float(eps)
+    a.batch, a.width, a.proj, a.w_layout = int(batch), int(width), int(proj), int(w_layout)
+    return Call(lib.msdv_pool_project, (C.byref(a),), name, keep=a, check=_lib_vision.check)
 
 
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:

@@ -226,6 +226,8 @@ def pack(layout: List[Packed], named, device, keep=None) -> Tuple[PackedWeights,
             W[e.key] = dev_f32(_keras(e, named), device)
             continue
         m = _matrix(e, named)
+        if e.pad_k is not None:
+            m = torch.nn.functional.pad(m, (0, e.pad_k - m.shape[1]))
         if e.parts[0].ffproj_top and kept(e):
             masters.top[e.parts[0].layer] = m[:, : e.parts[1].col_off].contiguous().to(device)
         if e.norm is None:

@@ -766,9 +766,14 @@ class StableDiffusionBase:
         self._engines: Dict[tuple, DenoiseEngine] = {}
         self.denoise_streams = None  # None / 1: cond+uncond as one fused batch; 2: two concurrent HIP streams
         self.text_frontend = None
-        # any callable picture -> (1024,) CLIP image embedding (ViT-H/14): what ip_adapter={"image": ...} goes through, as
-        # text_frontend is for string prompts; the vision tower itself is not part of this package
+        # any callable picture -> (1024,) CLIP image embedding (ViT-H/14): what ip_adapter={"image": ...} goes through when it is
+        # set, as text_frontend is for string prompts; without one the package's own tower encodes the picture (clip_vision below)
         self.image_prompt_encoder = None
+        # the CLIP ViT-H/14 vision tower (models.ClipVisionEncoder): set one, or give the path of the `image_encoder/model.safetensors`
+        # that ships with the SD 1.5 IP-Adapters and it is built on first use
+        self.clip_vision_path = None
+        self._clip_vision = None
+        self._image_prompt_cache = None   # ((pixel digest, tower, its weights_version), embedding) of the last picture encoded
         self.bpe_path = None  # local copy of CLIP's bpe_simple_vocab_16e6.txt.gz (or $MSD_BPE_PATH) for string prompts
         self.unconditional_context = None  # (77, 768) embedding of the empty prompt, supplied by the caller
         # False (default, the reference's meaning of batch_size: stable_diffusion.py:384-397 tiles one prompt to the batch THIS
@@ -1122,7 +1127,8 @@ class StableDiffusionBase:
         s read from a per-step device table (``weight`` inside [``start``, ``end``) by diffusers' rule, times the block factors of
         ``weight_type``: "style" is up_blocks.1 only, "composition" down_blocks.2.attentions.1 only).  The tokens are the adapter's
         projection of the embedding, made on the host once per call; the unconditional rows take the zero embedding's tokens.
-        ``image`` needs ``self.image_prompt_encoder`` (any callable picture -> (1024,) embedding); ``tokens`` bypasses the projection
+        ``image`` goes through ``self.image_prompt_encoder`` (any callable picture -> (1024,) embedding) when one is set, else through
+        the package's CLIP ViT-H/14 tower (``self.clip_vision`` / ``clip_vision_path=``); ``tokens`` bypasses the projection
         (the entry for "plus" adapters).  Tokens and table are per-call uploads, so the engine is keyed by N and the adapter alone and
         one engine serves every picture, weight and schedule.  Works with every sampler, a TCD pipeline, ``control_net_image`` with or
         without ``control`` (the ControlNet's own encoder stays plain), image_to_image, inpainting, ``dynamic_threshold``,
@@ -1386,6 +1392,42 @@ class StableDiffusionBase:
                     m.compile(jit_compile=True)
         return cache[unit.path]
 
+    @property
+    def clip_vision(self):
+        """The CLIP ViT-H/14 vision tower of image prompts (models.ClipVisionEncoder), or None: the one that was set, or the checkpoint
+        `clip_vision_path` loaded on first use."""
+        if self._clip_vision is None and self.clip_vision_path is not None:
+            from .models import ClipVisionEncoder
+
+            tower = ClipVisionEncoder(path=self.clip_vision_path, device=getattr(self, "device", None))
+            if self.jit_compile:
+                tower.compile(jit_compile=True)
+            self._clip_vision = tower
+        return self._clip_vision
+
+    @clip_vision.setter
+    def clip_vision(self, tower):
+        self._clip_vision = tower
+
+    def encode_image_prompt(self, picture) -> np.ndarray:
+        """A picture (anything vision.preprocess takes: uint8 / float HxWx3 on the 0 .. 255 scale, or a path) -> its (1024,) float64 CLIP
+        image embedding through `clip_vision`: what ip_adapter={"embeds": ...} takes.  The last picture's embedding is kept, keyed
+        by a digest of the preprocessed pixels and the tower's weights_version: encoding it again does not run the tower."""
+        from . import vision
+
+        tower = self.clip_vision
+        if tower is None:
+            raise ValueError("encode_image_prompt: no vision tower: set StableDiffusion.clip_vision (a models.ClipVisionEncoder) or pass "
+                             "clip_vision_path= (the IP-Adapter's image_encoder/model.safetensors)")
+        px = vision.preprocess(picture)
+        key = (vision.digest(px), id(tower), tower.weights_version)
+        if self._image_prompt_cache is None or self._image_prompt_cache[0] != key:
+            embeds = np.asarray(tower.predict_on_batch(px[None]), dtype=np.float64).reshape(-1)
+            if embeds.shape != (ipadapter_mod.EMBED_DIM,) or not np.isfinite(embeds).all():
+                raise ValueError(f"clip_vision returned shape {embeds.shape}, expected a finite ({ipadapter_mod.EMBED_DIM},)")
+            self._image_prompt_cache = (key, embeds)
+        return self._image_prompt_cache[1].copy()
+
     def _ip_inputs(self, ipa):
         """(the models.IPAdapter of an image-prompt job, (tokens_u, tokens_c)): its own `model`, or the checkpoint `path` loaded once
         and kept on the pipeline by path; the (N, 768) fp32 tokens of the unconditional rows (the zero embedding's, or
@@ -1407,13 +1449,19 @@ class StableDiffusionBase:
             neg = np.zeros_like(ipa.tokens) if ipa.negative_tokens is None else ipa.negative_tokens
             return model, (np.asarray(neg, dtype=np.float32), np.asarray(ipa.tokens, dtype=np.float32))
         embeds = ipa.embeds
-        if embeds is None:
-            if self.image_prompt_encoder is None:
-                raise ValueError("ip_adapter: `image` needs StableDiffusion.image_prompt_encoder (a callable picture -> (1024,) CLIP image "
-                                 "embedding), which is not set: pass `embeds` (the embedding) or `tokens` (the image tokens) instead")
+        if embeds is None and self.image_prompt_encoder is not None:   # (a callable that was set wins over the package's tower)
             embeds = np.asarray(self.image_prompt_encoder(ipa.image), dtype=np.float64).reshape(-1)
             if embeds.shape != (ipadapter_mod.EMBED_DIM,) or not np.isfinite(embeds).all():
                 raise ValueError(f"ip_adapter: image_prompt_encoder returned shape {embeds.shape}, expected a finite ({ipadapter_mod.EMBED_DIM},)")
+        elif embeds is None:
+            if self.clip_vision is None:
+                raise ValueError("ip_adapter: `image` needs StableDiffusion.image_prompt_encoder (a callable picture -> (1024,) CLIP image "
+                                 "embedding), which is not set: pass `embeds` (the embedding) or `tokens` (the image tokens) instead, or give "
+                                 "the pipeline its own tower (StableDiffusion.clip_vision / clip_vision_path=)")
+            if model.tokens > 4:
+                raise ValueError(f"ip_adapter: `image` with a \"plus\" adapter ({model.tokens} image tokens): its resampler over the tower's hidden "
+                                 "states is not part of the package: pass tokens= (the resampler's output) instead")
+            embeds = self.encode_image_prompt(ipa.image)
         return model, (model.project(np.zeros(ipadapter_mod.EMBED_DIM)), model.project(embeds))
 
     def _reference_inputs(self, ref, h, w, seed):
@@ -1823,8 +1871,10 @@ class StableDiffusion(StableDiffusionBase):
     initialised torch.distributed process group ("More than one GPU")."""
 
     def __init__(self, img_height=512, img_width=512, jit_compile=False, clip_skip=-1, unet_ckpt=None, text_encoder_ckpt=None,
-                 vae_ckpt=None, lora_path=None, controlnet_path=None, active_tcd=False, device=None, lora_switch=False):
+                 vae_ckpt=None, lora_path=None, controlnet_path=None, active_tcd=False, device=None, lora_switch=False,
+                 clip_vision_path=None):
         super().__init__(img_height, img_width, jit_compile, active_tcd)
+        self.clip_vision_path = clip_vision_path   # the CLIP ViT-H/14 tower of image prompts, loaded on first use (clip_vision)
         # lora_switch (opt in: fp32 masters of the targetable weights stay on the device, ~3.4 GB for the UNet): LoRAs are merged
         # into the packed weights in place by set_loras() instead of at load time (minsdtf_amd/lora.py)
         self.lora_switch = bool(lora_switch)

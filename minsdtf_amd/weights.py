@@ -284,6 +284,79 @@ TABLES["text_encoder"] = text_encoder_table
 TABLES["text_clip_embedding"] = text_clip_embedding_table
 
 
+# --------------------------------------------------------------------------------------
+# CLIP ViT-H/14 vision tower with its projection: the `image_encoder/model.safetensors` that ships with the SD 1.5 IP-Adapters,
+# under the key names of transformers' CLIPVisionModelWithProjection.  `layers`: how many encoder layers are built (32 in the
+# checkpoint; tests build 2-layer towers, as clip_skip cuts the text encoder).
+# --------------------------------------------------------------------------------------
+VIT_DIM, VIT_HEADS, VIT_LAYERS, VIT_MLP, VIT_IMAGE, VIT_PATCH, VIT_PROJ = 1280, 16, 32, 5120, 224, 14, 1024
+VIT_TOKENS = (VIT_IMAGE // VIT_PATCH) ** 2 + 1
+
+
+def clip_vision_table(layers: int = VIT_LAYERS) -> List[WeightSpec]:
+    if not 1 <= int(layers) <= VIT_LAYERS:
+        raise ValueError(f"clip_vision: {layers} layers (1 .. {VIT_LAYERS})")
+    emb = "vision_model.embeddings."
+    rows = [WeightSpec(emb + "class_embedding", None, emb + "class_embedding", "embedding", None, (VIT_DIM,)),
+            WeightSpec(emb + "patch_embedding.weight", None, emb + "patch_embedding", "conv_w", CONV_PERM, (VIT_PATCH, VIT_PATCH, 3, VIT_DIM)),
+            WeightSpec(emb + "position_embedding.weight", None, emb + "position_embedding", "embedding", None, (VIT_TOKENS, VIT_DIM))]
+    t = _Table("", use_alt=False)
+    t.norm("vision_model.pre_layrnorm", "vision_model.pre_layrnorm", VIT_DIM)   # (the checkpoint spells it so)
+    for idx in range(int(layers)):
+        ln = f"vision_model.encoder.layers.{idx}"
+        t.norm(ln + ".layer_norm1", ln + ".layer_norm1", VIT_DIM)
+        for proj in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            t.dense(f"{ln}.self_attn.{proj}", f"{ln}.self_attn.{proj}", VIT_DIM, VIT_DIM)
+        t.norm(ln + ".layer_norm2", ln + ".layer_norm2", VIT_DIM)
+        t.dense(ln + ".mlp.fc1", ln + ".mlp.fc1", VIT_DIM, VIT_MLP)
+        t.dense(ln + ".mlp.fc2", ln + ".mlp.fc2", VIT_MLP, VIT_DIM)
+    t.norm("vision_model.post_layernorm", "vision_model.post_layernorm", VIT_DIM)
+    t.dense("visual_projection", "visual_projection", VIT_DIM, VIT_PROJ, bias=False)
+    return rows + t.rows
+
+
+TABLES["clip_vision"] = clip_vision_table
+
+
+def clip_vision_arrays(state, layers: int = VIT_LAYERS) -> List[np.ndarray]:
+    """A loaded vision-tower checkpoint (key -> tensor / array, PyTorch layout; fp16 and bf16 files load) -> the ordered fp32
+    Keras-layout list ``set_weights`` takes.  Keys the table does not name (a `position_ids` buffer, the layers past `layers`)
+    are ignored; a missing key raises KeyError and a wrong shape ValueError, each naming the key."""
+    out = []
+    for spec in clip_vision_table(layers):
+        if spec.key not in state:
+            raise KeyError(f"clip_vision: the checkpoint has no {spec.key!r}")
+        w = state[spec.key]
+        if hasattr(w, "detach"):
+            w = w.detach().float().cpu().numpy()
+        w = np.asarray(w, dtype=np.float32)
+        if tuple(w.shape) != spec.torch_shape:
+            raise ValueError(f"clip_vision: {spec.key!r} has shape {tuple(w.shape)}, expected {spec.torch_shape}")
+        out.append(to_keras_layout(spec, w))
+    return out
+
+
+def clip_vision_synthetic_state(seed: int = 0, layers: int = VIT_LAYERS) -> Dict[str, np.ndarray]:
+    """A seeded synthetic tower in the checkpoint's layout, float32: Glorot-uniform matrices (the patch matrix by its (588, 1280)
+    fans), gammas in [0.8, 1.2], biases and betas in [-0.1, 0.1], class token and position embedding 0.5 N(0, 1)."""
+    rng = np.random.Generator(np.random.PCG64([int(seed), 7]))
+    state = {}
+    for spec in clip_vision_table(layers):
+        shape = spec.torch_shape
+        if spec.kind == "embedding":
+            w = 0.5 * rng.standard_normal(size=shape)
+        elif spec.kind in ("conv_w", "dense_w"):
+            fan_out, fan_in = shape[0], int(np.prod(shape[1:]))
+            lim = np.sqrt(6.0 / (fan_in + fan_out))
+            w = rng.uniform(-lim, lim, size=shape)
+        elif spec.kind == "gamma":
+            w = rng.uniform(0.8, 1.2, size=shape)
+        else:
+            w = rng.uniform(-0.1, 0.1, size=shape)
+        state[spec.key] = w.astype(np.float32)
+    return state
+
+
 def table(kind: str, **kw) -> List[WeightSpec]:
     return TABLES[kind](**kw)
 
@@ -322,7 +395,7 @@ def synth_tensors(kind: str, seed: int = 0, bias_scale: float = 0.0, **table_kw)
     parity tests so that bias / beta paths are not vacuous); 0 gives the Keras default init.
     """
     salt = {"civitai_model": 0, "decoder": 1, "controlnet": 2, "hintnet": 3, "encoder": 4, "text_encoder": 5,
-            "text_clip_embedding": 6}[kind]
+            "text_clip_embedding": 6, "clip_vision": 7}[kind]
     rng = np.random.Generator(np.random.PCG64([seed, salt]))
     for spec in table(kind, **table_kw):
         if spec.kind == "embedding":   # Keras Embedding default: uniform(-0.05, 0.05)
