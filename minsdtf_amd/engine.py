@@ -1334,3 +1334,71 @@ def emit_clip_vision(e: Emitter, pixels, layers: int, penultimate: bool = False,
               w=e.W["visual_projection.w"], out=embeds, batch=B, x_stride=T * C, w_layout=e.w_layout("visual_projection.w"), eps=EPS,
               name="visual_projection")
     return x
+
+
+RESAMPLER_LAYER_LAUNCHES = 10
+
+
+def ip_resampler_launches(depth: int, B: int = 1) -> int:
+    """The launch count of emit_ip_resampler plus models.IPResampler's two boundary casts: 6 + 10 * depth, and one more (the replica
+    of the latents) when B > 1."""
+    return 6 + RESAMPLER_LAYER_LAUNCHES * int(depth) + (1 if int(B) > 1 else 0)
+
+
+def emit_ip_resampler(e: Emitter, hidden: Act, depth: int, tokens: int = wtab.RS_TOKENS, heads: int = wtab.RS_HEADS) -> Act:
+    """The Resampler of an IP-Adapter "plus" checkpoint (minsdtf_amd/resampler.py): hidden bf16 [B][257][1280], the tower's
+    penultimate hidden states -> x = proj_in(hidden) (bias inside); the latents, a packed fp32 constant, rounded to bf16 once and
+    replicated over the B samples; then `depth` x [LayerNorm1(x) -> to_kv with K as rows and V transposed (split_mode) | LayerNorm2
+    (latents) -> the stacked q | k | v GEMM of the 16 latent rows (split_mode) | ONE msdr_perceiver_attention over both key segments
+    where those two GEMMs left them | to_out with the residual epilogue | LayerNorm -> fc1 (fp32 out) -> msdv_gelu (erf GELU, the
+    one rounding) -> fc2 with the residual epilogue]; then proj_out (bias inside) and LayerNorm_out.
+
+    The attention scale sits on the SCORES: the launch's `scale` is 64**-0.5 * log2(e) in one fp32 multiplication (the product of
+    the formula's two 64**-0.25 factors, and the kernel's softmax is base 2); to_q is packed as it is in the file.
+    Launches: 4 + 10 * depth here, + 1 when B > 1 (the replica of the latents); with models.IPResampler's two boundary casts
+    6 + 10 * depth (+ 1): ip_resampler_launches.  The LayerNorms are msd_layer_norm launches: LayerNorm1 differs per layer, so the
+    x-side K / V of the layers are not one GEMM.  Every GEMM row and every attention workgroup belongs to one sample and the tile
+    forms are chosen per sample, so a sample's tokens do not depend on its batch.
+    Returns the bf16 [B][tokens][768] Act of the image tokens."""
+    p = e.p
+    B, T, C = hidden.B, hidden.H, wtab.RS_DIM
+    N = int(tokens)
+    d = C // heads
+    Tp, Np = (T + 7) // 8 * 8, (N + 7) // 8 * 8
+    x = e.conv(hidden, "proj_in", C)
+    lat = p.act(B, N, 1, C)
+    p.rec(ops.cast_f32_to_bf16, x=e.W["latents"], out=lat.buf, n=N * C, name="latents.bf16")
+    if B > 1:
+        p.rec(ops.replicate, src=lat.buf, dst=lat.buf, nbytes=N * C * 2, copies=B, name="latents.replicate")
+    for i in range(int(depth)):
+        ln = f"layers.{i}"
+        xn = e.layer_norm(x, ln + ".attn.norm1")
+        kx, vtx = p.act(B, T, 1, C), p.alloc(B * C * Tp * 2)
+        e.conv(xn, ln + ".attn.to_kv", 2 * C, bias=False, split=(0, C, None, kx.buf, vtx, Tp))
+        p.free(xn)
+        h = e.layer_norm(lat, ln + ".attn.norm2")
+        q, kl = p.act(B, N, 1, C), p.act(B, N, 1, C)
+        vtl = p.alloc(B * C * Np * 2)
+        e.conv(h, ln + ".attn.qkv", 3 * C, bias=False, split=(C, C, q.buf, kl.buf, vtl, Np))
+        p.free(h)
+        o = p.act(B, N, 1, C)
+        p.rec(ops.perceiver_attention, q=q.buf, k_x=kx.buf, vt_x=vtx, k_l=kl.buf, vt_l=vtl, out=o.buf, batch=B, heads=heads, head_dim=d,
+              n=N, t_x=T, q_ld=C, kx_ld=C, vtx_ld=Tp, kl_ld=C, vtl_ld=Np, o_ld=C, scale=float(d) ** -0.5 * 1.4426950408889634,
+              name=ln + ".attn")
+        p.free(q, kx, vtx, kl, vtl)
+        lat2 = e.conv(o, ln + ".attn.to_out", C, bias=False, residual=lat)
+        p.free(o, lat)
+        h = e.layer_norm(lat2, ln + ".ff.norm")
+        f32 = e.conv(h, ln + ".ff.fc1", wtab.RS_FF, bias=False, out_dtype=ops.OUT_F32)   # no rounding: msdv_gelu's input
+        p.free(h)
+        f = p.act(B, N, 1, wtab.RS_FF)
+        p.rec(ops.gelu, x=f32.buf, out=f.buf, rows=B * N, cols=wtab.RS_FF, name=ln + ".ff.gelu")
+        p.free(f32)
+        lat = e.conv(f, ln + ".ff.fc2", C, bias=False, residual=lat2)
+        p.free(f, lat2)
+    p.free(x)
+    y = e.conv(lat, "proj_out", C)
+    p.free(lat)
+    out = e.layer_norm(y, "norm_out")
+    p.free(y)
+    return out

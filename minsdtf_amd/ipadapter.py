@@ -184,7 +184,9 @@ def read_state(state) -> Dict[str, np.ndarray]:
     """A loaded IP-Adapter checkpoint - the nested dict {"image_proj": {...}, "ip_adapter": {...}} of a .bin or flat prefixed keys
     ("image_proj.proj.weight", "ip_adapter.1.to_k_ip.weight", ...) - as {"proj.weight", "proj.bias", "norm.weight", "norm.bias",
     "<attention block>.to_k_ip", "<attention block>.to_v_ip"} float32 arrays, the block names engine.PAG_LAYERS'.  The map from the
-    checkpoint's odd indices 1 .. 31 (diffusers' attn_processors order) is verified by shape; any mismatch raises."""
+    checkpoint's odd indices 1 .. 31 (diffusers' attn_processors order) is verified by shape; any mismatch raises.
+    A "plus" checkpoint - one with `image_proj.latents` - has a Resampler in place of the projection: its keys come back as
+    "resampler.<key>" (resampler.read_state's, verified there) and there is no "proj.*" / "norm.*" entry."""
     flat = {}
     for k, v in dict(state).items():
         if isinstance(v, dict):
@@ -201,6 +203,12 @@ def read_state(state) -> Dict[str, np.ndarray]:
         return np.ascontiguousarray(v, dtype=np.float32)
 
     out = {}
+    if "image_proj.latents" in flat:   # a "plus" checkpoint: its image_proj is a Resampler (resampler.read_state verifies it)
+        from . import resampler as resampler_mod
+
+        for key, a in resampler_mod.read_state(flat).items():
+            out["resampler." + key] = a
+        return _read_kv(flat, arr, out)
     pw = arr("image_proj.proj.weight")
     if pw.ndim != 2 or pw.shape[1] != EMBED_DIM or pw.shape[0] % CONTEXT_DIM or not 1 <= pw.shape[0] // CONTEXT_DIM <= MAX_TOKENS:
         raise ValueError(f"ip_adapter: image_proj.proj.weight has shape {pw.shape}, expected (N * {CONTEXT_DIM}, {EMBED_DIM}) with "
@@ -210,6 +218,11 @@ def read_state(state) -> Dict[str, np.ndarray]:
         out[key] = arr("image_proj." + key)
         if out[key].shape != shape:
             raise ValueError(f"ip_adapter: image_proj.{key} has shape {out[key].shape}, expected {shape}")
+    return _read_kv(flat, arr, out)
+
+
+def _read_kv(flat, arr, out) -> Dict[str, np.ndarray]:
+    """The 32 to_k_ip / to_v_ip matrices of a checkpoint's `ip_adapter` part into `out` (read_state: both layouts share them)."""
     names = layer_names()
     for j, (layer, width) in enumerate(zip(CHECKPOINT_ORDER, CHECKPOINT_WIDTHS)):
         for m in ("to_k_ip", "to_v_ip"):

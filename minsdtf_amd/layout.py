@@ -201,6 +201,11 @@ def layout(specs, flags: Flags = Flags()) -> List[Packed]:
                 fold(base + stacked + ".w", parts, n[: -len(first)] + ".norm1")
         elif n.endswith(_STACKED):
             pass   # stacked above
+        elif n.endswith(".attn.to_q") and (n[: -len("to_q")] + "to_kv", "dense_w") in shape:
+            # the Resampler's PerceiverAttention (resampler.py): the latents' q | k | v as ONE GEMM, to_q stacked over to_kv; to_kv
+            # keeps its own matrix below, which the x side reads
+            kvn = n[: -len("to_q")] + "to_kv"
+            rows(n[: -len("to_q")] + "qkv.w", [Part(n), Part(kvn, row_off=nk(n)[0])])
         else:
             rows(n + ".w", [Part(n)])
             if has("bias"):

@@ -14,6 +14,7 @@ ImageDecoder       image_decoder.py:22-66                         latent -> (B,8
 ControlNet         control_net.py:45-118                          [latent, t_emb, context, hint] -> 13 arrays
 HintNet            control_net.py:10-42                           (B,H,W,3) -> (B,H/8,W/8,320)
 ClipVisionEncoder  (transformers CLIPVisionModelWithProjection)    (B,224,224,3) 0..255 -> (B,1024) image_embeds
+IPResampler        (IP-Adapter resampler.py Resampler)             (B,257,1280) hidden states -> (B,16,768) image tokens
 =================  =============================================  ==========================
 
 Inputs / outputs at this boundary are host numpy arrays like the reference's; the fused,
@@ -517,6 +518,9 @@ class IPAdapter:
         self.tokens = int(tokens)
         self._W = None
         self.projection: Optional[Dict[str, np.ndarray]] = None
+        # a models.IPResampler when the adapter came from a "plus" checkpoint (or synthetic_plus); settable.  Then the image tokens are
+        # its output on the vision tower's penultimate hidden states, there is no projection, and `tokens` is its query count
+        self.resampler = None
         self.weights_version = 0
         if path is not None:
             self.load(path)
@@ -540,7 +544,8 @@ class IPAdapter:
         from . import ipadapter as ipadapter_mod
 
         named = ipadapter_mod.read_state(state)
-        n = named["proj.weight"].shape[0] // 768
+        plus = {k[len("resampler."):]: v for k, v in named.items() if k.startswith("resampler.")}
+        n = plus["latents"].shape[1] if plus else named["proj.weight"].shape[0] // 768
         named_keras = {}
         for name, _C in engine.UNET_ATTN_LAYERS:
             blk = name[:-len(".transformer_blocks.0.attn2")]
@@ -548,7 +553,13 @@ class IPAdapter:
                 named_keras[(f"{name}.{m}", "dense_w")] = np.ascontiguousarray(named[f"{blk}.{m}"].T)
         W, _ = packing.pack(self.packed_layout(), named_keras, self.device)
         self._W, self.tokens = W, n
-        self.projection = {k: np.asarray(named[k], dtype=np.float64) for k in ("proj.weight", "proj.bias", "norm.weight", "norm.bias")}
+        if plus:
+            rs = IPResampler(name=self.name + ".resampler", device=self.device)
+            rs.set_state(plus)
+            self.projection, self.resampler = None, rs
+        else:
+            self.projection = {k: np.asarray(named[k], dtype=np.float64) for k in ("proj.weight", "proj.bias", "norm.weight", "norm.bias")}
+            self.resampler = None
         self.weights_version += 1
 
     def load(self, path: str) -> None:
@@ -561,6 +572,18 @@ class IPAdapter:
         """A seeded synthetic adapter, for tests and fixtures like the synthetic UNet: Glorot-uniform matrices (times `scale`)."""
         m = cls(tokens, device=device)
         m.set_state(cls.synthetic_state(seed, tokens, scale))
+        return m
+
+    @classmethod
+    def synthetic_plus(cls, seed: int = 0, depth: int = wtab.RS_DEPTH, device=None, scale: float = 1.0) -> "IPAdapter":
+        """A seeded synthetic "plus" adapter: synthetic()'s 32 to_k_ip / to_v_ip matrices at 16 tokens and, in place of the projection,
+        a `depth`-layer synthetic Resampler (resampler.synthetic_state) as `resampler`."""
+        from . import resampler as resampler_mod
+
+        state = {k: v for k, v in cls.synthetic_state(seed, wtab.RS_TOKENS, scale).items() if not k.startswith("image_proj.")}
+        state.update(resampler_mod.synthetic_state(seed, depth, wtab.RS_TOKENS))
+        m = cls(wtab.RS_TOKENS, device=device)
+        m.set_state(state)
         return m
 
     @staticmethod
@@ -588,6 +611,9 @@ class IPAdapter:
         from . import ipadapter as ipadapter_mod
 
         self._require_weights()
+        if self.resampler is not None:
+            raise ValueError("ip_adapter: a \"plus\" adapter has no projection of the pooled embedding - its Resampler reads the vision "
+                             "tower's hidden states: pass `image` (with StableDiffusion(clip_vision_path=...)) or the image `tokens`")
         p = self.projection
         return ipadapter_mod.project(embeds, p["proj.weight"], p["proj.bias"], p["norm.weight"], p["norm.bias"], self.tokens)
 
@@ -927,6 +953,93 @@ class ClipVisionEncoder(HipModel):
         B = px.shape[0]
         bp = self._bound((B, output), lambda: self._build(B, output))
         bp.io["pixels"].copy_(torch.from_numpy(px))
+        bp.run()
+        return bp.host("out")
+
+    __call__ = predict_on_batch
+
+
+class IPResampler(HipModel):
+    """The Resampler of an IP-Adapter "plus" checkpoint (minsdtf_amd/resampler.py; diffusers' IPAdapterPlusImageProjection): the CLIP
+    ViT-H/14 tower's penultimate hidden states (B, 257, 1280) -> the (B, N, 768) float32 image tokens of the decoupled
+    cross-attention.  `depth`: the number of layers (4 in the SD 1.5 plus adapters; tests build 1- and 2-layer resamplers);
+    `tokens`: the learned queries N (16).  set_state adopts both from the checkpoint.  engine.emit_ip_resampler is the launch plan:
+    6 + 10 * depth launches (+ 1 when B > 1) with the two boundary casts; the attention scale sits on the scores."""
+    kind = "ip_resampler"
+
+    def __init__(self, depth=wtab.RS_DEPTH, tokens=wtab.RS_TOKENS, name=None, device=None):
+        self.depth, self.tokens = int(depth), int(tokens)
+        if device is not None and torch.device(device).type != "cuda":
+            # a host-side object (a reader's result, the tests' stand-in devices): it holds and packs weights, it cannot run
+            self.name, self.device = name or "ip_resampler", torch.device(device)
+            self._retable()
+            self._W, self._plans, self._use_graph = None, {}, False
+            self.weights_version, self.lora_switch, self._lora = 0, False, None
+        else:
+            super().__init__(name or "ip_resampler", device)
+        self.state: Optional[Dict[str, np.ndarray]] = None   # resampler.read_state's result: what resampler.forward_host takes
+
+    def _table_kw(self):
+        return {"depth": self.depth, "tokens": self.tokens}
+
+    def _retable(self) -> None:
+        """The weight table and the Keras-like `weights` list of the current depth and token count."""
+        self._specs = wtab.table(self.kind, **self._table_kw())
+        self.weights = [WeightVar(s.name + (".kernel" if s.kind.endswith("_w") else "." + s.kind), s.shape) for s in self._specs]
+
+    def count_params(self) -> int:
+        return int(sum(int(np.prod(s.shape)) for s in self._specs))
+
+    def set_state(self, state) -> None:
+        """Adopt a loaded plus checkpoint (resampler.read_state's input: nested or flat `image_proj.` keys, fp16 files load) or
+        read_state's own result; `depth` and `tokens` follow the state.  Raises on a missing key or a wrong shape, naming it."""
+        from . import resampler as resampler_mod
+
+        state = dict(state)
+        named = state if "latents" in state and "proj_in.weight" in state else resampler_mod.read_state(state)
+        depth, tokens = resampler_mod.depth_of(named), int(np.asarray(named["latents"]).shape[-2])
+        if (depth, tokens) != (self.depth, self.tokens):
+            self.depth, self.tokens = depth, tokens
+            self._retable()
+        self.set_weights(wtab.ip_resampler_arrays(named, depth, tokens))
+        self.state = {k: np.asarray(v, dtype=np.float32) for k, v in named.items()}
+
+    def load_synthetic(self, seed=0, bias_scale=0.0):
+        """Fill with the seeded synthetic resampler (resampler.synthetic_state at this depth and token count; `bias_scale` is not
+        used: its biases are always drawn); returns that state, under the checkpoint's flat keys."""
+        from . import resampler as resampler_mod
+
+        state = resampler_mod.synthetic_state(seed, self.depth, self.tokens)
+        self.set_state(state)
+        return state
+
+    def _build(self, B: int) -> _BoundPlan:
+        plan = engine.Plan(self.device)
+        e = engine.Emitter(plan, self._W)
+        T, C = wtab.VIT_TOKENS, wtab.VIT_DIM
+        h32 = plan.alloc(B * T * C * 4)
+        h16 = engine.Act(plan.alloc(B * T * C * 2), B, T, 1, C)
+        plan.rec(ops.cast_f32_to_bf16, x=h32, out=h16.buf, n=B * T * C, name="hidden.bf16")
+        y = engine.emit_ip_resampler(e, h16, self.depth, self.tokens)
+        o32 = plan.alloc(B * self.tokens * wtab.RS_DIM * 4)
+        plan.rec(ops.cast_bf16_to_f32, x=y.buf, out=o32, n=B * self.tokens * wtab.RS_DIM, name="tokens.f32")
+        plan.finalize()
+        bp = _BoundPlan(plan, self._use_graph)
+        bp.io["hidden"] = h32.tensor(torch.float32, (B, T, C))
+        bp.io["out"] = o32.tensor(torch.float32, (B, self.tokens, wtab.RS_DIM))
+        return bp
+
+    def predict_on_batch(self, hidden):
+        """hidden (B, 257, 1280) or (257, 1280) float32, B = 1 .. 8: ClipVisionEncoder.predict_on_batch(..., output="penultimate")
+        -> the (B, N, 768) float32 image tokens."""
+        h = _np32(hidden)
+        h = h[None] if h.ndim == 2 else h
+        if h.ndim != 3 or h.shape[1:] != (wtab.VIT_TOKENS, wtab.VIT_DIM) or not 1 <= h.shape[0] <= 8:
+            raise ValueError(f"ip_resampler: hidden states of shape {h.shape} ((B, {wtab.VIT_TOKENS}, {wtab.VIT_DIM}), B = 1 .. 8: "
+                             "the tower's output='penultimate')")
+        B = h.shape[0]
+        bp = self._bound((B,), lambda: self._build(B))
+        bp.io["hidden"].copy_(torch.from_numpy(h))
         bp.run()
         return bp.host("out")
 

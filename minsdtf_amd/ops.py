@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
-from . import _lib, _lib_control, _lib_dynthresh, _lib_ext, _lib_ipadapter, _lib_vision
+from . import _lib, _lib_control, _lib_dynthresh, _lib_ext, _lib_ipadapter, _lib_resampler, _lib_vision
 from ._lib import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, OUT_BF16, OUT_F32, OUT_U8  # noqa: F401
 
 
@@ -427,6 +427,21 @@ def pool_project(*, x, gamma, beta, w, out, batch, x_stride, w_layout=0, eps=1e-
     a.x_stride, a.eps = int(x_stride), float(eps)
     a.batch, a.width, a.proj, a.w_layout = int(batch), int(width), int(proj), int(w_layout)
     return Call(lib.msdv_pool_project, (C.byref(a),), name, keep=a, check=_lib_vision.check)
+
+
+# ---- the resampler library (include/minsdtf_hip_resampler.h, minsdtf_amd/_lib_resampler.py) ----------------------------------------
+def perceiver_attention(*, q, k_x, vt_x, k_l, vt_l, out, batch, heads, n, t_x, q_ld, kx_ld, vtx_ld, kl_ld, vtl_ld, o_ld, scale,
+                        head_dim=_lib_resampler.HEAD_DIM, name="perceiver_attention") -> Call:
+    """msdr_perceiver_attention: out bf16 [batch][n][o_ld] = softmax2(scale * q [k_x ; k_l]^T) [v_x ; v_l] per head of 64, one softmax
+    over the t_x + n keys of both segments (x keys first), the V operands transposed ([batch][heads * 64][ld], keys contiguous).
+    `scale` carries log2(e): the kernel takes exp2."""
+    lib = _lib_resampler.load()
+    a = _lib_resampler.MsdrPerceiverAttention()
+    a.q, a.k_x, a.vt_x, a.k_l, a.vt_l, a.out = _p(q), _p(k_x), _p(vt_x), _p(k_l), _p(vt_l), _p(out)
+    a.scale = float(scale)
+    a.batch, a.heads, a.head_dim, a.n, a.t_x = int(batch), int(heads), int(head_dim), int(n), int(t_x)
+    a.q_ld, a.kx_ld, a.vtx_ld, a.kl_ld, a.vtl_ld, a.o_ld = int(q_ld), int(kx_ld), int(vtx_ld), int(kl_ld), int(vtl_ld), int(o_ld)
+    return Call(lib.msdr_perceiver_attention, (C.byref(a),), name, keep=a, check=_lib_resampler.check)
 
 
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:

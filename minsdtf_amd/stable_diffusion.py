@@ -774,6 +774,10 @@ class StableDiffusionBase:
         self.clip_vision_path = None
         self._clip_vision = None
         self._image_prompt_cache = None   # ((pixel digest, tower, its weights_version), embedding) of the last picture encoded
+        # a "plus" adapter's image tokens (image_prompt_tokens): ((pixel digest, tower / adapter / resampler ids and versions), tokens_c)
+        # of the last picture, and ((the same ids and versions), tokens_u) of the zero-normalised picture
+        self._image_tokens_cache = None
+        self._image_tokens_negative = None
         self.bpe_path = None  # local copy of CLIP's bpe_simple_vocab_16e6.txt.gz (or $MSD_BPE_PATH) for string prompts
         self.unconditional_context = None  # (77, 768) embedding of the empty prompt, supplied by the caller
         # False (default, the reference's meaning of batch_size: stable_diffusion.py:384-397 tiles one prompt to the batch THIS
@@ -1129,8 +1133,12 @@ class StableDiffusionBase:
         projection of the embedding, made on the host once per call; the unconditional rows take the zero embedding's tokens.
         ``image`` goes through ``self.image_prompt_encoder`` (any callable picture -> (1024,) embedding) when one is set, else through
         the package's CLIP ViT-H/14 tower (``self.clip_vision`` / ``clip_vision_path=``); ``tokens`` bypasses the projection
-        (the entry for "plus" adapters).  Tokens and table are per-call uploads, so the engine is keyed by N and the adapter alone and
-        one engine serves every picture, weight and schedule.  Works with every sampler, a TCD pipeline, ``control_net_image`` with or
+        (the entry for "plus" adapters without a picture).  A "plus" checkpoint (``ip-adapter-plus_sd15``, 16 tokens: its
+        ``image_proj`` is a Resampler, recognised by ``image_proj.latents``) takes ``image`` too: the tokens are the adapter's
+        ``resampler`` (models.IPResampler) on the tower's penultimate hidden states, the unconditional rows take the resampler's tokens
+        of the zero-normalised picture (``self.image_prompt_tokens``; both are kept, a repeated job runs neither network); it needs
+        the package's own tower - a callable returns the pooled embedding, which it cannot use - and refuses ``embeds``.
+        Tokens and table are per-call uploads, so the engine is keyed by N and the adapter alone and one engine serves every picture, weight and schedule.  Works with every sampler, a TCD pipeline, ``control_net_image`` with or
         without ``control`` (the ControlNet's own encoder stays plain), image_to_image, inpainting, ``dynamic_threshold``,
         shard_batch and host_loop=True; not with regions, pag, sag, reference_only, hypertile, tiled, hires or denoise_streams = 2,
         nor with prompts of more than 77 tokens.  One adapter and one picture per job.  A spec whose table is all 0 (weight 0) is the
@@ -1428,10 +1436,47 @@ class StableDiffusionBase:
             self._image_prompt_cache = (key, embeds)
         return self._image_prompt_cache[1].copy()
 
+    def image_prompt_tokens(self, picture, adapter):
+        """A picture (anything vision.preprocess takes) -> (tokens_u, tokens_c), each (N, 768) float32: the image tokens of a "plus"
+        `adapter` (a models.IPAdapter with a `resampler`).  tokens_c = the resampler on the tower's `penultimate` hidden states of
+        preprocess(picture); tokens_u = the same route on the picture whose NORMALISED pixels are zero (IP-Adapter's
+        IPAdapterPlus.get_image_embeds; built from vision.pixel_affine, zero to fp32 rounding) - not the zero embedding's projection.
+        tokens_c is kept for the last picture, keyed by the pixel digest, the tower's id and weights_version and the adapter's and
+        resampler's weights_version; tokens_u per (tower, adapter, resampler) versions: a repeated job runs neither network, a new
+        picture runs each once."""
+        from . import vision
+
+        rs = getattr(adapter, "resampler", None)
+        if rs is None:
+            raise ValueError("image_prompt_tokens: the adapter has no resampler (a base adapter projects the pooled embedding: "
+                             "encode_image_prompt and IPAdapter.project)")
+        tower = self.clip_vision
+        if tower is None:
+            raise ValueError("ip_adapter: `image` with a \"plus\" adapter needs the pipeline's own vision tower, whose hidden states its "
+                             "resampler reads: set StableDiffusion.clip_vision (a models.ClipVisionEncoder) or pass clip_vision_path= (an "
+                             "image_prompt_encoder callable returns the pooled embedding, which a plus adapter cannot use), or pass `tokens`")
+
+        def run(px):
+            hidden = np.asarray(tower.predict_on_batch(px[None], output="penultimate"), dtype=np.float32)
+            tok = np.asarray(rs.predict_on_batch(hidden), dtype=np.float32)
+            if tok.shape != (1, adapter.tokens, ipadapter_mod.CONTEXT_DIM) or not np.isfinite(tok).all():
+                raise ValueError(f"ip_resampler returned shape {tok.shape}, expected a finite {(1, adapter.tokens, ipadapter_mod.CONTEXT_DIM)}")
+            return np.ascontiguousarray(tok[0])
+
+        versions = (id(tower), tower.weights_version, id(adapter), adapter.weights_version, id(rs), rs.weights_version)
+        px = vision.preprocess(picture)
+        key = (vision.digest(px),) + versions
+        if self._image_tokens_cache is None or self._image_tokens_cache[0] != key:
+            self._image_tokens_cache = (key, run(px))
+        if self._image_tokens_negative is None or self._image_tokens_negative[0] != versions:
+            self._image_tokens_negative = (versions, run(vision.zero_normalised_pixels()))
+        return self._image_tokens_negative[1].copy(), self._image_tokens_cache[1].copy()
+
     def _ip_inputs(self, ipa):
         """(the models.IPAdapter of an image-prompt job, (tokens_u, tokens_c)): its own `model`, or the checkpoint `path` loaded once
         and kept on the pipeline by path; the (N, 768) fp32 tokens of the unconditional rows (the zero embedding's, or
-        `negative_tokens` / zeros beside `tokens`) and of the conditional rows (the picture's)."""
+        `negative_tokens` / zeros beside `tokens`) and of the conditional rows (the picture's).  A "plus" adapter (one with a
+        `resampler`) takes `image` through image_prompt_tokens, or `tokens`."""
         model = ipa.model
         if model is None:
             if ipa.path is None:
@@ -1441,6 +1486,8 @@ class StableDiffusionBase:
             cache = self.__dict__.setdefault("_ip_adapters_by_path", {})
             if ipa.path not in cache:
                 cache[ipa.path] = IPAdapter(path=ipa.path, device=getattr(self, "device", None))
+                if self.jit_compile and cache[ipa.path].resampler is not None:
+                    cache[ipa.path].resampler.compile(jit_compile=True)
             model = cache[ipa.path]
         model._require_weights()
         if ipa.tokens is not None:
@@ -1448,6 +1495,11 @@ class StableDiffusionBase:
                 raise ValueError(f"ip_adapter: {ipa.tokens.shape[0]} `tokens`, the adapter takes {model.tokens}")
             neg = np.zeros_like(ipa.tokens) if ipa.negative_tokens is None else ipa.negative_tokens
             return model, (np.asarray(neg, dtype=np.float32), np.asarray(ipa.tokens, dtype=np.float32))
+        if getattr(model, "resampler", None) is not None:   # a "plus" adapter: the resampler over the tower's hidden states
+            if ipa.embeds is not None:
+                raise ValueError("ip_adapter: `embeds` with a \"plus\" adapter: its resampler reads the vision tower's hidden states, not the "
+                                 "pooled embedding: pass `image` (the picture) or `tokens` (the resampler's output) instead")
+            return model, self.image_prompt_tokens(ipa.image, model)
         embeds = ipa.embeds
         if embeds is None and self.image_prompt_encoder is not None:   # (a callable that was set wins over the package's tower)
             embeds = np.asarray(self.image_prompt_encoder(ipa.image), dtype=np.float64).reshape(-1)

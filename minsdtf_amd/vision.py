@@ -31,6 +31,14 @@ def pixel_affine() -> Tuple[Tuple[float, float, float], Tuple[float, float, floa
     return tuple(1.0 / (255.0 * s) for s in STD), tuple(-m / s for m, s in zip(MEAN, STD))
 
 
+def zero_normalised_pixels() -> np.ndarray:
+    """The (224, 224, 3) float32 picture, on the 0 .. 255 scale, whose normalised pixels are zero: pixel = -shift / scale = 255 * mean
+    per channel, rounded once to fp32 (so pixel * scale + shift is zero to fp32 rounding).  The negative of a "plus" IP-Adapter."""
+    scale, shift = pixel_affine()
+    row = np.asarray([-b / a for a, b in zip(scale, shift)], dtype=np.float64)
+    return np.ascontiguousarray(np.broadcast_to(row.astype(np.float32), (SIZE, SIZE, 3)))
+
+
 def resize_size(h: int, w: int) -> Tuple[int, int]:
     """(rows, columns) after the resize: the shortest edge becomes 224, the long edge int(long * 224 / short)."""
     short, long = (w, h) if w <= h else (h, w)

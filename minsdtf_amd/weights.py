@@ -357,6 +357,47 @@ def clip_vision_synthetic_state(seed: int = 0, layers: int = VIT_LAYERS) -> Dict
     return state
 
 
+# --------------------------------------------------------------------------------------
+# The Resampler of an IP-Adapter "plus" checkpoint (minsdtf_amd/resampler.py), under the keys of its `image_proj.` part.  `depth`:
+# the number of layers (4 in the SD 1.5 plus adapters; tests build 1- and 2-layer resamplers); `tokens`: the learned queries.
+# --------------------------------------------------------------------------------------
+RS_DIM, RS_HEADS, RS_DEPTH, RS_TOKENS, RS_FF = 768, 12, 4, 16, 3072
+
+
+def ip_resampler_table(depth: int = RS_DEPTH, tokens: int = RS_TOKENS) -> List[WeightSpec]:
+    if not 1 <= int(depth) <= 16 or not 1 <= int(tokens) <= RS_TOKENS:
+        raise ValueError(f"ip_resampler: {depth} layers (1 .. 16) of {tokens} queries (1 .. {RS_TOKENS})")
+    rows = [WeightSpec("latents", None, "latents", "embedding", None, (int(tokens), RS_DIM))]   # (the file's leading 1 is dropped)
+    t = _Table("", use_alt=False)
+    t.dense("proj_in", "proj_in", VIT_DIM, RS_DIM)
+    for i in range(int(depth)):
+        k = f"layers.{i}"   # (the table's names: <layer>.attn.* for the file's <layer>.0.*, <layer>.ff.* for <layer>.1.*)
+        t.norm(k + ".0.norm1", k + ".attn.norm1", RS_DIM)
+        t.norm(k + ".0.norm2", k + ".attn.norm2", RS_DIM)
+        t.dense(k + ".0.to_q", k + ".attn.to_q", RS_DIM, RS_DIM, bias=False)
+        t.dense(k + ".0.to_kv", k + ".attn.to_kv", RS_DIM, 2 * RS_DIM, bias=False)
+        t.dense(k + ".0.to_out", k + ".attn.to_out", RS_DIM, RS_DIM, bias=False)
+        t.norm(k + ".1.0", k + ".ff.norm", RS_DIM)
+        t.dense(k + ".1.1", k + ".ff.fc1", RS_DIM, RS_FF, bias=False)
+        t.dense(k + ".1.3", k + ".ff.fc2", RS_FF, RS_DIM, bias=False)
+    t.dense("proj_out", "proj_out", RS_DIM, RS_DIM)
+    t.norm("norm_out", "norm_out", RS_DIM)
+    return rows + t.rows
+
+
+TABLES["ip_resampler"] = ip_resampler_table
+
+
+def ip_resampler_arrays(named, depth: int, tokens: int) -> List[np.ndarray]:
+    """resampler.read_state's result (verified float32 arrays under the `image_proj.` keys) -> the ordered fp32 Keras-layout list
+    ``set_weights`` takes."""
+    out = []
+    for spec in ip_resampler_table(depth, tokens):
+        w = np.asarray(named[spec.key], dtype=np.float32)
+        out.append(to_keras_layout(spec, w.reshape(spec.torch_shape)))
+    return out
+
+
 def table(kind: str, **kw) -> List[WeightSpec]:
     return TABLES[kind](**kw)
 
