@@ -633,7 +633,7 @@ def test_conv_direct(gpu, case):
         close(out, ref, what=str(case))
 
 
-@pytest.mark.parametrize("case", [
+GROUP_NORM_CASES = [
     dict(B=2, hw=64, c0=320, silu=True),
     dict(B=2, hw=256, c0=1280, c1=640, silu=True),     # concat, groups straddle the two tensors
     dict(B=1, hw=64, c0=1280, c1=1280, silu=True),     # C=2560: two channel vectors per thread
@@ -650,7 +650,10 @@ def test_conv_direct(gpu, case):
     dict(B=1, hw=4100, c0=320, c1=320, silu=False),    # same path, concat, ragged last chunk
     dict(B=2, hw=256, c0=1280, c1=640, silu=True, impl=0),   # three-launch path forced on a small tensor
     dict(B=2, hw=64, c0=320, silu=True, impl=0),
-])
+]
+
+
+@pytest.mark.parametrize("case", GROUP_NORM_CASES)
 def test_group_norm(gpu, case):
     from minsdtf_amd import _lib, ops
 
@@ -692,7 +695,7 @@ def test_group_norm(gpu, case):
     g.check()
 
 
-@pytest.mark.parametrize("case", [
+GROUP_NORM_CLUSTER_CASES = [
     dict(B=2, hw=4096, c0=320, silu=True),               # the UNet's 64x64 level: 4 parts, 4-byte units
     dict(B=1, hw=4096, c0=640, c1=320, silu=True),       # C = 960: 16 units per thread, a group straddles x0 | x1
     dict(B=1, hw=4100, c0=320, c1=320, silu=False),      # ragged last part, 8-byte units
@@ -701,7 +704,10 @@ def test_group_norm(gpu, case):
     dict(B=3, hw=2048, c0=1280, silu=False),             # 2 parts
     dict(B=2, hw=1024, c0=640, silu=True, opt=256),      # the 32x32 level on 4 parts (gn_cluster = 256 pixels per part)
     dict(B=2, hw=256, c0=1280, silu=True, opt=128),      # ... and the 16x16 level on 2
-])
+]
+
+
+@pytest.mark.parametrize("case", GROUP_NORM_CLUSTER_CASES)
 @pytest.mark.parametrize("form", ["groups", "rows"])
 def test_group_norm_cluster(gpu, case, form):
     """GroupNorm as ONE launch in which 2 / 4 / 8 workgroups share a (sample, group) slab and exchange partial moments through the
