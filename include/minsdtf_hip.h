@@ -381,6 +381,9 @@ MSD_API int msd_memset_zero(void* ptr, int64_t bytes, msd_stream_t stream);
  *   The row used is coef[*step_ptr]; after the update *step_ptr is incremented when advance != 0:
  *   advance = 1 by a second one-thread launch; advance = 2 inside the launch, by the workgroup that finishes last — then
  *   step_ptr points at TWO ints {step, ticket}, ticket zero when first used and touched by nothing else.
+ *   step_ptr == NULL (advance 0 only) uses row 0.  A counter outside 0 .. steps - 1 is clamped into that range for the
+ *   coefficient row, noise_coef and the step_noise row, but what advance stores is the counter AS READ plus one (-3 -> -2,
+ *   steps + 2 -> steps + 3): a counter that left the range stays outside it until the caller resets it.
  *   Inpainting (stable_diffusion.py:469-475), when inpaint_mask != NULL: after the sampler step
  *   latent = origin * (1 - mask) + latent * mask with origin = signal_rate[t] * inpaint_init +
  *   noise_rate[t] * inpaint_noise at the CURRENT timestep t (the reference re-noises the encoded
