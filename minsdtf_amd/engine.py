@@ -843,6 +843,10 @@ def unet_levels(h: int, w: int) -> List[Tuple[int, int]]:
     return out
 
 
+# the calls whose output takes a T2I-Adapter's feature l (minsdtf_amd/t2iadapter.py SITE_NAMES): the second pair of every level
+T2I_SITES: Tuple[str, ...] = ("down_blocks.0.attentions.1", "down_blocks.1.attentions.1", "down_blocks.2.attentions.1", "down_blocks.3.resnets.1")
+
+
 @dataclass(frozen=True)
 class UNetVariant:
     """How one UNet forward (emit_unet) differs from the plain one: which attention blocks take which AttnVariant field (at()), and
@@ -874,6 +878,11 @@ class UNetVariant:
     # ip = ({attn2 layer name: (k_ip, vt_ip, np_ld)} (emit_ip_kv over the NB rows), n, scales, num_steps): every block takes
     # AttnVariant.ip with its own K / V^T of the n image tokens and its own column of the table `scales`, fp32 [num_steps][16].
     ip: Optional[tuple] = None
+    # t2i = (features, scales, num_steps) (T2I-Adapters, minsdtf_amd/t2iadapter.py): features[u][l] is unit u's bf16 feature of site
+    # l, [h_l * w_l * ch_l], and `scales` the per-step table fp32 [num_steps][U][4].  Right behind the call that produces site l
+    # (T2I_SITES), before it is pushed as a skip and before the downsampler reads it, ONE msda_feature_add launch adds the units'
+    # scaled features to every row, in place: four launches per forward.
+    t2i: Optional[tuple] = None
 
     def _pag(self) -> frozenset:
         return frozenset(self.pag_layers or ()) if self.perturbed else frozenset()
@@ -898,6 +907,14 @@ class UNetVariant:
             raise ValueError(f"emit_unet: unknown attention block(s) {sorted(self._pag() - set(PAG_LAYERS))}")
         if self.ip is not None and (self.perturbed or self.region_attn or self.reference is not None or self.window is not None or self.sag is not None):
             raise ValueError("emit_unet: ip (an image prompt) does not go with pag, regions, a reference row, a window or sag")
+        if self.t2i is not None:
+            feats, _scales, num_steps = self.t2i
+            if self.perturbed or self.region_attn or self.reference is not None or self.window is not None or self.sag is not None \
+                    or controls is not None or control_taps is not None:
+                raise ValueError("emit_unet: t2i (adapter features) does not go with pag, regions, a reference row, a window, sag or a ControlNet")
+            if not 1 <= len(feats) <= 3 or any(len(f) != len(T2I_SITES) for f in feats) or num_steps < 1:
+                raise ValueError(f"emit_unet: t2i with {len(feats)} unit(s) (1 .. 3) of {[len(f) for f in feats]} features ({len(T2I_SITES)} "
+                                 f"each) and {num_steps} step rows")
         if self.window is not None:
             if self.perturbed or self.region_attn or self.reference is not None:
                 raise ValueError("emit_unet: window does not go with pag, regions or a reference row")
@@ -934,10 +951,21 @@ class UNetVariant:
                   hw=x.H * x.W, c=x.C, eps=1e-6, name=name + ".adain")
 
 
+    def t2i_site(self, e: "Emitter", x: Act, name: str) -> None:
+        """The T2I-Adapter features behind the call `name` that produced x, when that output is one of the four sites: every row of x
+        takes the same feature, its scale read from row *step_ptr of the table."""
+        if self.t2i is not None and name in T2I_SITES:
+            feats, scales, num_steps = self.t2i
+            site = T2I_SITES.index(name)
+            e.p.rec(ops.feature_add, x=x.buf, feats=[f[site] for f in feats], scales=scales, step_ptr=e.step_ptr, rows=x.B,
+                    n=x.H * x.W * x.C, site=site, num_steps=num_steps, name=name + ".t2i")
+
+
 def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Act], shared: int = 1, variant=UNetVariant(), NB: int = 0) -> Act:
     """Down path + mid block shared by the UNet (diffusion_model.py:193-229) and the ControlNet.  shared > 1: `x` (conv_in's output) is
     `shared` identical copies of x.B / shared samples - the first ResBlock and the front of the first transformer block run on one.
-    variant / NB: emit_unet's, for what its attention blocks and its reference AdaIN sites take; the ControlNet passes neither."""
+    variant / NB: emit_unet's, for what its attention blocks, its T2I-Adapter sites and its reference AdaIN sites take; the ControlNet
+    passes neither."""
     p = e.p
     for lvl, ch in enumerate(wtab.UNET_CH):
         for r in range(2):
@@ -947,6 +975,7 @@ def _emit_encoder(e: Emitter, x: Act, temb_of, ctx_kv, ctx_len, outputs: List[Ac
             x = e.res_block(one, name, ch, temb=temb_of(name), out_copies=copies)
             if lvl < 3:
                 x = e.attentions(x, blk, ctx_kv, ctx_len, free_input=True, shared=copies, variant=variant.at(blk, x))
+            variant.t2i_site(e, x, blk if lvl < 3 else name)
             variant.adain_site(p, x, blk if lvl < 3 else name, NB)
             outputs.append(x)
         if lvl < 3:
@@ -1402,3 +1431,43 @@ def emit_ip_resampler(e: Emitter, hidden: Act, depth: int, tokens: int = wtab.RS
     out = e.layer_norm(y, "norm_out")
     p.free(y)
     return out
+
+
+T2I_ADAPTER_LAUNCHES = 31
+
+
+def emit_t2i_adapter(e: Emitter, picture_f32, B: int, H: int, W: int, cin: int) -> List[Act]:
+    """The network of a T2I-Adapter (minsdtf_amd/t2iadapter.py; diffusers' FullAdapter): picture fp32 [B][H][W][cin] in [0, 1], H and W
+    multiples of 64 -> msda_unshuffle (PixelUnshuffle(8), the one rounding of the picture) -> conv_in (3x3, K = 9 * 64 cin) -> per
+    level l = 0 .. 3 at (320, 640, 1280, 1280) channels [msda_avgpool2 (l > 0) | the 1x1 in_conv (l = 1, 2) | twice: block1 (3x3) ->
+    msda_relu in place -> block2 (1x1) with the residual epilogue]: 1 + 1 + 3 + 2 + 8 * 3 = 31 launches.  `e` is an Emitter over
+    models.T2IAdapter's packed image (keys adapter.<layer>.w / .b).  Returns the four feature Acts, bf16 [B][H / 8 / 2^l][W / 8 / 2^l]
+    [ch_l]: each is the buffer the next level's pool reads - nothing is copied to make them - and none is freed.  Every conv row and
+    every pooled pixel belongs to one sample and the tile forms are chosen per sample, so a sample's features do not depend on its
+    batch."""
+    from .t2iadapter import BLOCKS, CHANNELS
+
+    p = e.p
+    x0 = p.act(B, H // 8, W // 8, 64 * cin)
+    p.rec(ops.unshuffle, x=picture_f32, out=x0.buf, batch=B, h=H, w=W, cin=cin, name="adapter.unshuffle")
+    x = e.conv(x0, "adapter.conv_in", CHANNELS[0], ksize=3)
+    p.free(x0)
+    feats: List[Act] = []
+    for l, ch in enumerate(CHANNELS):
+        if l > 0:   # (x is feature l - 1: read, never freed)
+            y = p.act(B, x.H // 2, x.W // 2, x.C)
+            p.rec(ops.avgpool2, x=x.buf, out=y.buf, batch=B, h=x.H, w=x.W, c=x.C, name=f"adapter.body.{l}.downsample")
+            x = y
+            if ch != CHANNELS[l - 1]:
+                y = e.conv(x, f"adapter.body.{l}.in_conv", ch)
+                p.free(x)
+                x = y
+        for j in range(BLOCKS):
+            n = f"adapter.body.{l}.resnets.{j}"
+            h = e.conv(x, n + ".block1", ch, ksize=3)
+            p.rec(ops.relu, x=h.buf, n=h.M * h.C, name=n + ".act")
+            y = e.conv(h, n + ".block2", ch, residual=x)
+            p.free(h, x)
+            x = y
+        feats.append(x)
+    return feats

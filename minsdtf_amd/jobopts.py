@@ -4,6 +4,7 @@ from dataclasses import dataclass
 from typing import FrozenSet, Optional, Tuple
 
 from . import control as control_mod, hypertile as hypertile_mod, ipadapter as ipadapter_mod, reference as reference_mod, regions as regions_mod, samplers as smp
+from . import t2iadapter as t2i_mod
 from .engine import PAG_LAYERS
 
 # job kind -> (what it is, the arguments and then the states it cannot be combined with, in the order the error names them)
@@ -36,12 +37,13 @@ _ENGINE_SENTENCE = {
 
 
 def job_options(sampler=None, regions=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None,
-                ip_tokens=None) -> dict:
+                ip_tokens=None, t2i_units=None) -> dict:
     """_engine's option keywords of a job from its parsed descriptions (None: the job has none): only what the job asks for.
     `control`: the parsed units of control.parse - the engine is built for their number only.  `ip_tokens`: the number of image
-    tokens of a job with an IP-Adapter image prompt - the engine is built for that number only."""
+    tokens of a job with an IP-Adapter image prompt - the engine is built for that number only.  `t2i_units`: the number of
+    T2I-Adapters of a job with t2i_adapter= - the engine is built for that number only."""
     out = dict(sampler=sampler and sampler.name, pag=pag and pag.key, hypertile=hypertile, sag=sag and True, dynthresh=dynthresh and True,
-               control_units=control and len(control), ip_tokens=ip_tokens or None)
+               control_units=control and len(control), ip_tokens=ip_tokens or None, t2i_units=t2i_units or None)
     if regions is not None:   # (the base prompt counts when it is evaluated)
         out.update(regions=regions.count, region_mode=regions.mode)
     if reference is not None:
@@ -64,6 +66,7 @@ class EngineOptions:
     dynthresh: bool = False                          # dynamic thresholding
     control_units: int = 0                           # the number of ControlNet units of a job with control= (minsdtf_amd/control.py)
     ip_tokens: int = 0                               # the number of image tokens of a job with ip_adapter= (minsdtf_amd/ipadapter.py)
+    t2i_units: int = 0                               # the number of adapters of a job with t2i_adapter= (minsdtf_amd/t2iadapter.py)
 
     @classmethod
     def of(cls, **opts) -> "EngineOptions":
@@ -74,7 +77,8 @@ class EngineOptions:
                    region_mode=o.region_mode if regions or o.region_mode not in regions_mod.MODES else "latent",   # (an unknown mode stays, for check() to name)
                    pag=frozenset(o.pag) if o.pag else None, reference=frozenset(o.reference or ()) if (o.reference or adain) else None,
                    adain=adain, hypertile=tuple(int(v) for v in ht) if ht is not None and len(ht) == 3 else ht,   # (else as given, for check())
-                   sag=bool(o.sag), dynthresh=bool(o.dynthresh), control_units=int(o.control_units), ip_tokens=int(o.ip_tokens))
+                   sag=bool(o.sag), dynthresh=bool(o.dynthresh), control_units=int(o.control_units), ip_tokens=int(o.ip_tokens),
+                   t2i_units=int(o.t2i_units))
 
     def key(self) -> tuple:
         """What the options add to an engine's key behind the UNet-size part: what the plans depend on, nothing a call uploads."""
@@ -88,7 +92,8 @@ class EngineOptions:
         key += ((("hypertile",) + self.hypertile,) if self.hypertile else ()) + ((("sag",),) if self.sag else ())
         key += (("dynthresh",),) if self.dynthresh else ()
         key += (("control", self.control_units),) if self.control_units else ()
-        return key + ((("ip", self.ip_tokens),) if self.ip_tokens else ())
+        key += (("ip", self.ip_tokens),) if self.ip_tokens else ()
+        return key + ((("t2i", self.t2i_units),) if self.t2i_units else ())
 
     def check(self, h: int, w: int, B: int, guidance: float, control: bool, inpaint: bool, tcd: bool, streams) -> None:
         """ValueError for what an engine of batch B at h x w refuses: each kind's own checks, then its exclusions, read from REFUSED."""
@@ -143,3 +148,10 @@ class EngineOptions:
                 raise ValueError(f"ip_adapter: {self.ip_tokens} image tokens (1 .. {ipadapter_mod.MAX_TOKENS})")
             ipadapter_mod.refuse(dict(regions=self.regions or None, pag=self.pag, sag=self.sag or None, reference_only=self.reference,
                                       hypertile=self.hypertile, tiled=self.tiled), streams)
+        # a T2I-Adapter's exclusions live in t2iadapter.py, like the image prompt's: no REFUSED row
+        if self.t2i_units:
+            if not 1 <= self.t2i_units <= t2i_mod.MAX_UNITS:
+                raise ValueError(f"t2i_adapter: {self.t2i_units} units (1 .. {t2i_mod.MAX_UNITS})")
+            t2i_mod.check_size(8 * h, 8 * w)
+            t2i_mod.refuse(dict(control_net_image=control or None, regions=self.regions or None, pag=self.pag, sag=self.sag or None,
+                                reference_only=self.reference, hypertile=self.hypertile, tiled=self.tiled), streams)

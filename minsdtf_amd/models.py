@@ -258,7 +258,7 @@ class DiffusionModel(HipModel):
         self._maybe_load(ckpt_path, lora_dict)
 
     def _build(self, B: int, T: int, with_controls: bool, pag_layers=None, regions: int = 0, reference=None, window=None,
-               adain=None, sag: bool = False, ip=None) -> _BoundPlan:
+               adain=None, sag: bool = False, ip=None, t2i: int = 0) -> _BoundPlan:
         """pag_layers: the attention blocks whose self-attention is the identity map for ALL B rows (predict_perturbed).
         regions = R: all B rows are conditional rows over R region contexts (predict_regional): the context input is
         (R * B, T, 768), region-major, and `region_w` the four levels' weight planes (regions.pack_levels).
@@ -269,7 +269,9 @@ class DiffusionModel(HipModel):
         sag: the mid block's self-attention also writes the attention map of all B rows (predict_sag_map): io["sag_A"], fp32
         [B][mh * mw].
         ip = a models.IPAdapter (predict_ip): every attn2 is ONE msdi_attention_decoupled launch over the text context and the
-        adapter's K / V^T of `ip_tokens` (B, N, 768), scaled by row 0 of `ip_scales`, fp32 (1, 16)."""
+        adapter's K / V^T of `ip_tokens` (B, N, 768), scaled by row 0 of `ip_scales`, fp32 (1, 16).
+        t2i = U (predict_t2i): the four sites of the down path take U T2I-Adapters' features, io["t2i_feat.{u}.{l}"] (bf16, flat), scaled
+        by row 0 of `t2i_scales`, fp32 (1, U, 4)."""
         h, w = self.h, self.w
         reference = frozenset(reference or ()) if (reference or adain) else None   # (an empty layer set next to AdaIN sites)
         NB = B + 1 if reference is not None else B
@@ -288,7 +290,10 @@ class DiffusionModel(HipModel):
             shapes["region_w"] = (offs[-1],)
         if ip is not None:
             shapes.update(ip_tokens=(B, ip.tokens, 768), ip_scales=(1, 16))
+        if t2i:
+            shapes["t2i_scales"] = (1, t2i, 4)
         ins = _stage_inputs(plan, shapes)
+        t2i_feats = [[plan.alloc(hl * wl * ch * 2) for (hl, wl), ch in zip(engine.unet_levels(h, w), wtab.UNET_CH)] for _u in range(t2i)]
         if regions:
             region_attn = (regions, B, {lv: ins["region_w"].at(o * 4) for lv, o in zip(levels, offs)})
         ctx16 = engine.Act(plan.alloc(CB * T * 768 * 2), CB, T, 1, 768)
@@ -323,12 +328,15 @@ class DiffusionModel(HipModel):
             reference=(reference, ins["ref_latent"], ins["ref_mix"]) if reference is not None else None,
             adain=frozenset(adain) if adain else None,
             window=window[:2] if window is not None else None, window_depth=window[2] if window is not None else 0,
-            sag=(sag_A, sag_ws, 0, B) if sag else None, ip=ip_variant)
+            sag=(sag_A, sag_ws, 0, B) if sag else None, ip=ip_variant, t2i=(t2i_feats, ins["t2i_scales"], 1) if t2i else None)
         engine.emit_unet(e, ins["latent"], B, NB, h, w, (table, 0, total, cols), ctx_kv, T, eps, controls, variant=variant)
         plan.finalize()
         bp = _BoundPlan(plan, self._use_graph)
         bp.io = {k: b.tensor(torch.float32, shapes[k]) for k, b in ins.items()}
         bp.io["eps"] = eps.tensor(torch.float32, (NB, h, w, 4))
+        for u, fs in enumerate(t2i_feats):
+            for l, ((hl, wl), ch) in enumerate(zip(engine.unet_levels(h, w), wtab.UNET_CH)):
+                bp.io[f"t2i_feat.{u}.{l}"] = fs[l].tensor(torch.bfloat16, (hl * wl * ch,))
         if sag_A is not None:
             bp.io["sag_A"] = sag_A.tensor(torch.float32, (B, mh * mw))
         for i, (st, shp) in enumerate(cstage):
@@ -470,6 +478,51 @@ class DiffusionModel(HipModel):
         bp.io["ip_scales"].copy_(torch.from_numpy(sc.reshape(1, 16)))
         for i, c in enumerate(controls):
             bp.io[f"control.{i}"].copy_(torch.from_numpy(c))
+        bp.run()
+        return bp.host("eps")
+
+    def predict_t2i(self, x, features, scales, ip=None):
+        """predict_on_batch([latent, t_emb, context]) with T2I-Adapter features: `features` is a list of U units, each the four bf16
+        features of models.T2IAdapter.features (device tensors, or arrays) - the same for every row - and `scales` fp32 (U, 4), one row
+        of t2iadapter.table: site l takes sum_u scales[u][l] * features[u][l] (msda_feature_add).  ip = (adapter, tokens, scales16):
+        the forward also carries predict_ip's image prompt.  The forward of a T2I-Adapter job's host loop (minsdtf_amd/t2iadapter.py); a
+        bound plan of its own per (B, T, U) and image-prompt adapter."""
+        if len(x) != 3:
+            raise ValueError("predict_t2i takes [latent, t_emb, context] (no control tensors)")
+        latent, t_emb, context = _np32(x[0]), _np32(x[1]), _np32(x[2])
+        B, T = latent.shape[0], context.shape[1]
+        if latent.shape[1:] != (self.h, self.w, 4):
+            raise ValueError(f"latent shape {latent.shape} does not match the model ({self.h},{self.w},4)")
+        U = len(features)
+        sc = _np32(scales).reshape(-1)
+        sizes = [hl * wl * ch for (hl, wl), ch in zip(engine.unet_levels(self.h, self.w), wtab.UNET_CH)]
+        if not 1 <= U <= 3 or sc.shape != (U * 4,) or any(len(f) != 4 or [int(np.prod(a.shape)) for a in f] != sizes for f in features):
+            raise ValueError(f"predict_t2i: {U} unit(s) (1 .. 3) of features {[[tuple(a.shape) for a in f] for f in features]} and "
+                             f"{sc.shape[0]} scales, expected four features of {sizes} elements per unit and {U * 4} scales")
+        key = (B, T, False, ("t2i", U))
+        adapter = None
+        if ip is not None:
+            from . import ipadapter as ipadapter_mod
+
+            adapter, tokens, ip_scales = ip
+            adapter._require_weights()
+            tok = _np32(tokens)
+            tok = np.array(np.broadcast_to(tok, (B,) + tok.shape)) if tok.ndim == 2 else tok
+            ipadapter_mod.check_context(T, adapter.tokens)
+            key += (("ip", adapter.tokens, id(adapter), adapter.weights_version),)
+        bp = self._bound(key, lambda: self._build(B, T, False, ip=adapter, t2i=U))
+        bp.io["latent"].copy_(torch.from_numpy(latent))
+        bp.io["t_emb"].copy_(torch.from_numpy(t_emb))
+        bp.io["context"].copy_(torch.from_numpy(context))
+        bp.io["t2i_scales"].copy_(torch.from_numpy(sc.reshape(1, U, 4)))
+        for u, fs in enumerate(features):
+            for l, f in enumerate(fs):
+                f = f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f, dtype=np.float32))
+                bp.io[f"t2i_feat.{u}.{l}"].copy_(f.reshape(-1))   # (bf16 -> bf16 as it is; fp32 arrays are rounded once)
+        if adapter is not None:
+            bp.keep_alive = adapter
+            bp.io["ip_tokens"].copy_(torch.from_numpy(tok))
+            bp.io["ip_scales"].copy_(torch.from_numpy(_np32(ip_scales).reshape(1, 16)))
         bp.run()
         return bp.host("eps")
 
@@ -1042,5 +1095,142 @@ class IPResampler(HipModel):
         bp.io["hidden"].copy_(torch.from_numpy(h))
         bp.run()
         return bp.host("out")
+
+    __call__ = predict_on_batch
+
+
+class T2IAdapter:
+    """A T2I-Adapter (minsdtf_amd/t2iadapter.py; diffusers' T2IAdapter "full adapter"): a small model object of its own beside the
+    UNet - 19 convs with bias, packed through layout.py under `adapter.<layer>` the way every other MFMA conv is - that turns one
+    conditioning picture into the four feature maps the UNet's down path takes.  engine.emit_t2i_adapter is the launch plan: 31
+    launches, once per job.  `in_channels`: 3 (depth, pose, seg, ...) or 1 (sketch, canny); set_state adopts it from the checkpoint.
+    The last picture's features are kept (keyed by a digest of the preprocessed pixels, the size and `weights_version`): a repeated
+    job does not run the adapter."""
+    kind = "t2i_adapter"
+
+    def __init__(self, in_channels: int = 3, name=None, device=None, path=None):
+        if int(in_channels) not in (1, 3):
+            raise ValueError(f"t2i_adapter: in_channels = {in_channels!r} (1 or 3)")
+        self.name = name or "t2i_adapter"
+        self.device = device if device is not None else default_device()
+        self.in_channels = int(in_channels)
+        self._W = None
+        self.state: Optional[Dict[str, np.ndarray]] = None   # t2iadapter.read_state's result: what t2iadapter.forward_host takes
+        self.weights_version = 0
+        self._plans: Dict[tuple, _BoundPlan] = {}
+        self._use_graph = False
+        self._last = None   # (key, the four bf16 device tensors) of the last picture
+        self.runs = 0       # how often the network ran (the cache's tests count it)
+        if path is not None:
+            self.load(path)
+
+    def _require_weights(self):
+        if self._W is None:
+            raise RuntimeError(f"{self.name}: no weights set (pass path=, call set_state() or T2IAdapter.synthetic())")
+
+    def compile(self, jit_compile=True, **_):
+        """As HipModel.compile: the plan of a picture size is replayed from a hipGraph captured on its first use.  Off by default: the
+        31 launches run once per job, and only for a new picture."""
+        self._use_graph = bool(jit_compile)
+        self._plans.clear()
+
+    @staticmethod
+    def specs(in_channels: int) -> List["wtab.WeightSpec"]:
+        """The weight table: per conv a Keras-layout kernel and a bias, under `adapter.<layer>` (t2iadapter.layer_names)."""
+        from . import t2iadapter as t2i_mod
+
+        out = []
+        for layer, (co, ci, k, _k) in t2i_mod.layer_names(in_channels):
+            out.append(wtab.WeightSpec("adapter." + layer + ".weight", None, "adapter." + layer, "conv_w", wtab.CONV_PERM, (k, k, ci, co)))
+            out.append(wtab.WeightSpec("adapter." + layer + ".bias", None, "adapter." + layer, "bias", None, (co,)))
+        return out
+
+    def set_state(self, state) -> None:
+        """Adopt a loaded checkpoint in either public layout (t2iadapter.read_state's input; fp16 files load) or read_state's own
+        result; `in_channels` follows the state.  Raises on a missing key or a wrong shape, naming it."""
+        from . import t2iadapter as t2i_mod
+
+        state = dict(state)
+        named = state if "body.0.resnets.0.block1.weight" in state else t2i_mod.read_state(state)
+        cin = t2i_mod.in_channels_of(named)
+        specs = self.specs(cin)
+        arrays = {}
+        for s in specs:   # torch (out, in, k, k) -> the Keras (k, k, in, out) the packer starts from
+            a = named[s.key[len("adapter."):]]
+            arrays[(s.name, s.kind)] = np.ascontiguousarray(np.transpose(a, s.perm)) if s.perm is not None else a
+        W, _ = packing.pack(layout.layout(specs, layout.Flags(engine.W_CHUNK_MAJOR, engine.MFMA_TEMB_PROJ)), arrays, self.device)
+        self._W, self.in_channels = W, cin
+        self.state = {k: np.asarray(v, dtype=np.float32) for k, v in named.items()}
+        self.weights_version += 1
+        self._plans.clear()
+        self._last = None
+
+    def load(self, path: str) -> None:
+        path = os.fspath(path)
+        if not os.path.exists(path):
+            raise ValueError(f"t2i_adapter: checkpoint {path!r} not found")
+        self.set_state(wtab.read_state_dict(path))
+
+    @staticmethod
+    def synthetic_state(seed: int = 0, in_channels: int = 3, scale: float = 1.0) -> Dict[str, np.ndarray]:
+        """The flat state dict of synthetic(): diffusers' file layout, float32 arrays (t2iadapter.synthetic_state)."""
+        from . import t2iadapter as t2i_mod
+
+        return t2i_mod.synthetic_state(seed, in_channels, scale)
+
+    @classmethod
+    def synthetic(cls, seed: int = 0, in_channels: int = 3, device=None, scale: float = 1.0) -> "T2IAdapter":
+        """A seeded synthetic adapter, for tests and fixtures like the synthetic UNet."""
+        m = cls(in_channels, device=device)
+        m.set_state(cls.synthetic_state(seed, in_channels, scale))
+        return m
+
+    def _build(self, H: int, W: int) -> _BoundPlan:
+        plan = engine.Plan(self.device)
+        e = engine.Emitter(plan, self._W)
+        cin = self.in_channels
+        px = plan.alloc(H * W * cin * 4)
+        feats = engine.emit_t2i_adapter(e, px, 1, H, W, cin)
+        plan.finalize()
+        bp = _BoundPlan(plan, self._use_graph)
+        bp.io["picture"] = px.tensor(torch.float32, (1, H, W, cin))
+        for l, f in enumerate(feats):
+            bp.io[f"feature.{l}"] = f.buf.tensor(torch.bfloat16, (1, f.H, f.W, f.C))
+        return bp
+
+    def _picture(self, picture) -> np.ndarray:
+        from . import t2iadapter as t2i_mod
+
+        px = _np32(picture)
+        px = px[None] if px.ndim == 3 else px
+        if px.ndim != 4 or px.shape[0] != 1 or px.shape[3] != self.in_channels:
+            raise ValueError(f"t2i_adapter: a picture of shape {px.shape} for an adapter of {self.in_channels} input channel(s): "
+                             f"(1, H, W, {self.in_channels}) in [0, 1], one picture per job")
+        t2i_mod.check_size(px.shape[1], px.shape[2])
+        return px
+
+    def features(self, picture) -> List[torch.Tensor]:
+        """picture (1, H, W, cin) or (H, W, cin) float32 in [0, 1] (t2iadapter.picture's result) -> the four bf16 feature tensors
+        (1, H / 8 / 2^l, W / 8 / 2^l, ch_l) on the device, copies the caller owns.  The last picture's are kept."""
+        import hashlib
+
+        self._require_weights()
+        px = self._picture(picture)
+        key = (hashlib.sha256(px.tobytes()).hexdigest(), px.shape, self.weights_version, engine.GN_EPOCH)
+        if self._last is None or self._last[0] != key:
+            H, W = px.shape[1], px.shape[2]
+            bp = self._plans.get((H, W))
+            if bp is None:
+                bp = self._plans[(H, W)] = self._build(H, W)
+            bp.io["picture"].copy_(torch.from_numpy(px))
+            bp.run()
+            self.runs += 1
+            self._last = (key, [bp.io[f"feature.{l}"].clone() for l in range(4)])
+        return [f.clone() for f in self._last[1]]   # (small, once per job: a caller that writes into them cannot reach the kept ones)
+
+    def predict_on_batch(self, picture) -> List[np.ndarray]:
+        """picture (1, H, W, cin) or (H, W, cin) in [0, 1], H and W multiples of 64 -> the four features as float32 NHWC arrays, the
+        plan's bf16 values widened."""
+        return [f.to(torch.float32).cpu().numpy() for f in self.features(picture)]
 
     __call__ = predict_on_batch

@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
-from . import _lib, _lib_control, _lib_dynthresh, _lib_ext, _lib_ipadapter, _lib_resampler, _lib_vision
+from . import _lib, _lib_control, _lib_dynthresh, _lib_ext, _lib_ipadapter, _lib_resampler, _lib_t2i, _lib_vision
 from ._lib import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, OUT_BF16, OUT_F32, OUT_U8  # noqa: F401
 
 
@@ -442,6 +442,42 @@ def perceiver_attention(*, q, k_x, vt_x, k_l, vt_l, out, batch, heads, n, t_x, q
     a.batch, a.heads, a.head_dim, a.n, a.t_x = int(batch), int(heads), int(head_dim), int(n), int(t_x)
     a.q_ld, a.kx_ld, a.vtx_ld, a.kl_ld, a.vtl_ld, a.o_ld = int(q_ld), int(kx_ld), int(vtx_ld), int(kl_ld), int(vtl_ld), int(o_ld)
     return Call(lib.msdr_perceiver_attention, (C.byref(a),), name, keep=a, check=_lib_resampler.check)
+
+
+# ---- the T2I-Adapter library (include/minsdtf_hip_t2i.h, minsdtf_amd/_lib_t2i.py) ---------------------------------------------------
+def feature_add(*, x, feats, scales, rows, n, site, num_steps, step_ptr=None, name="feature_add") -> Call:
+    """msda_feature_add: x[r] = bf16(fp32(x[r]) + sum_u s_u * feats[u]) for every row r, one fmaf per unit in unit order, a unit at
+    scale 0 not read, s_u = scales[*step_ptr][u][site] (minsdtf_amd/t2iadapter.py).  x bf16 [rows][n] (in place); feats: 1 .. 3 bf16
+    [n]; scales fp32 [num_steps][len(feats)][4]."""
+    lib = _lib_t2i.load()
+    if not 1 <= len(feats) <= _lib_t2i.MAX_UNITS:
+        raise ValueError(f"feature_add: {len(feats)} features (1 .. {_lib_t2i.MAX_UNITS} units)")
+    a = _lib_t2i.MsdaFeatureAdd()
+    a.x, a.scales, a.step_ptr = _p(x), _p(scales), _p(step_ptr)
+    for u, f in enumerate(feats):
+        a.feat[u] = _p(f)
+    a.rows, a.n, a.units, a.site, a.num_steps = int(rows), int(n), len(feats), int(site), int(num_steps)
+    return Call(lib.msda_feature_add, (C.byref(a),), name, keep=a, check=_lib_t2i.check)
+
+
+def unshuffle(*, x, out, batch, h, w, cin, name="unshuffle") -> Call:
+    """msda_unshuffle: PixelUnshuffle(8), x fp32 [batch][h][w][cin] -> out bf16 [batch][h / 8][w / 8][64 cin], channel
+    c * 64 + dy * 8 + dx: the one rounding of the picture."""
+    lib = _lib_t2i.load()
+    return Call(lib.msda_unshuffle, (_p(x), _p(out), int(batch), int(h), int(w), int(cin)), name, check=_lib_t2i.check)
+
+
+def relu(*, x, n, name="relu") -> Call:
+    """msda_relu: x = max(x, +0) over n bf16 elements in place (-0 becomes +0, a NaN keeps its bits)."""
+    lib = _lib_t2i.load()
+    return Call(lib.msda_relu, (_p(x), int(n)), name, check=_lib_t2i.check)
+
+
+def avgpool2(*, x, out, batch, h, w, c, name="avgpool2") -> Call:
+    """msda_avgpool2: AvgPool2d(2, 2), x bf16 [batch][h][w][c] -> out bf16 [batch][h / 2][w / 2][c], ((a00 + a01) + (a10 + a11)) *
+    0.25 in fp32, one rounding."""
+    lib = _lib_t2i.load()
+    return Call(lib.msda_avgpool2, (_p(x), _p(out), int(batch), int(h), int(w), int(c)), name, check=_lib_t2i.check)
 
 
 def add_bf16(*, a, b, out, n, name="add_bf16") -> Call:

@@ -35,6 +35,7 @@ import torch
 from . import _lib, engine, ops
 from . import control as control_mod
 from . import ipadapter as ipadapter_mod
+from . import t2iadapter as t2i_mod
 from . import hires as hires_mod
 from . import dynthresh as dynthresh_mod
 from . import hypertile as hypertile_mod
@@ -307,6 +308,13 @@ class DenoiseEngine:
         self.cn_scales = torch.zeros(self.num_steps, self.control_units, 13, 2, dtype=torch.float32, device=dev) if self.control_units else None
         # ip_tokens: the per-step scale table of the image prompt, fp32 [num_steps][16] (ipadapter.table), a per-call upload
         self.ip_scales = torch.zeros(self.num_steps, 16, dtype=torch.float32, device=dev) if self.ip_tokens else None
+        # t2i_units (U, or 0): the adapters' features, bf16 [h_l * w_l * ch_l] per unit and site, and their per-step scale table, fp32
+        # [num_steps][U][4] (t2iadapter.table): buffers the engine owns, per-call uploads - one engine serves every picture
+        self.t2i_scales = self.t2i_feat = None
+        if self.t2i_units:
+            self.t2i_scales = torch.zeros(self.num_steps, self.t2i_units, 4, dtype=torch.float32, device=dev)
+            self.t2i_feat = [[torch.zeros(hl * wl * ch, dtype=torch.bfloat16, device=dev) for (hl, wl), ch in zip(engine.unet_levels(h, w), wtab.UNET_CH)]
+                             for _u in range(self.t2i_units)]
         self.branches = []
         step = None
         # ControlNet beside the UNet's down path: its encoder reads the same latent and is independent of the UNet until the
@@ -381,6 +389,10 @@ class DenoiseEngine:
         # keys and this pass's image-token K / V^T, its scale read from row *step_ptr of `ip_scales` (minsdtf_amd/ipadapter.py)
         if self.ip_tokens:
             kw.update(ip=(self._ip_kv[tag], self.ip_tokens, self.ip_scales, self.num_steps))
+        # t2i_units: behind each of the four sites of the down path ONE msda_feature_add launch adds the units' features to every row
+        # of the pass, its scales read from row *step_ptr of `t2i_scales` (minsdtf_amd/t2iadapter.py)
+        if self.t2i_units:
+            kw.update(t2i=(self.t2i_feat, self.t2i_scales, self.num_steps))
         return engine.UNetVariant(**kw)
 
     def _build_tail(self, step, guidance, guidance_rescale, inpaint, tcd) -> "engine.Plan":
@@ -576,7 +588,8 @@ class DenoiseEngine:
 
     def prepare(self, contexts: Dict[str, np.ndarray], noise: np.ndarray, scheduler: Scheduler, timesteps,
                 start_index: int = 0, hint_image: Optional[np.ndarray] = None, inpaint=None, step_noise=None, sampler=None,
-                regions=None, pag_scale=None, reference=None, sag=None, dynamic_threshold=None, control=None, ip_adapter=None) -> None:
+                regions=None, pag_scale=None, reference=None, sag=None, dynamic_threshold=None, control=None, ip_adapter=None,
+                t2i_adapter=None) -> None:
         """Upload the per-call inputs and run the preparation plan.  Every array may be a host array or a (device) tensor.
         noise = None: the start latent is already in `self.latent` (written there by stream-ordered device work queued before
         this call: the hand-off of a hires job), nothing is uploaded for it.
@@ -601,7 +614,24 @@ class DenoiseEngine:
         pictures of the further units, each like `hint_image`, are per-call uploads too: weights, ranges and modes re-record nothing.
         ip_adapter = (tokens_u, tokens_c, table) of an engine built with ip_tokens = N: the image tokens (N, 768) of the unconditional
         and of the conditional rows and the scale table fp32 [num_steps][16] (ipadapter.table over this engine's num_steps) are
-        per-call uploads too: another picture, weight, range or weight type re-records nothing."""
+        per-call uploads too: another picture, weight, range or weight type re-records nothing.
+        t2i_adapter = (features, table) of an engine built with t2i_units = U: per unit the four bf16 features of
+        models.T2IAdapter.features and the scale table fp32 [num_steps][U][4] (t2iadapter.table over this engine's num_steps) are
+        per-call uploads too: another picture, weight or range re-records nothing."""
+        if (t2i_adapter is None) != (self.t2i_scales is None):
+            raise ValueError("prepare: `t2i_adapter` goes with an engine built with t2i_units=U, and only with one")
+        if self.t2i_scales is not None:
+            feats, tab = t2i_adapter
+            tab = _f32_tensor(tab)
+            got = [[int(f.numel()) for f in fs] for fs in feats]
+            want = [[int(f.numel()) for f in fs] for fs in self.t2i_feat]
+            if tuple(tab.shape) != tuple(self.t2i_scales.shape) or got != want:
+                raise ValueError(f"prepare: adapter features of {got} elements and a table of shape {tuple(tab.shape)}, this engine's are "
+                                 f"{want} and {tuple(self.t2i_scales.shape)}")
+            self.t2i_scales.copy_(tab)
+            for dst_u, src_u in zip(self.t2i_feat, feats):
+                for dst, src in zip(dst_u, src_u):
+                    dst.copy_(src.reshape(-1))
         if (ip_adapter is None) != (self.ip_scales is None):
             raise ValueError("prepare: `ip_adapter` goes with an engine built with ip_tokens=N, and only with one")
         if self.ip_scales is not None:
@@ -799,7 +829,8 @@ class StableDiffusionBase:
         ``dynamic_threshold``: None, or a dynthresh.DynThreshSpec / dict for dynamic thresholding; ``control`` (through **kw, with
         ``control_net_image``): None, or one control.ControlUnit / dict or a list of them - weight, start / end, mode and further
         ControlNets (see generate_image); ``ip_adapter`` (through **kw): None, or an ipadapter.IPAdapterSpec / dict for an IP-Adapter
-        image prompt (see generate_image)."""
+        image prompt (see generate_image); ``t2i_adapter`` (through **kw): None, or one t2iadapter.T2IAdapterSpec / dict or a list of
+        them for T2I-Adapter structural control (see generate_image)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
@@ -812,7 +843,7 @@ class StableDiffusionBase:
                        embedding=None, negative_embedding=None, seed=None, control_net_image=None, reference_image=None,
                        reference_image_strength=0.8, guidance_rescale=0.7, callback=None, **kw):
         """Reference :111-139.  ``control`` (through **kw, with ``control_net_image``): the ControlNet units of generate_image;
-        ``ip_adapter`` (through **kw): its IP-Adapter image prompt."""
+        ``ip_adapter`` (through **kw): its IP-Adapter image prompt; ``t2i_adapter`` (through **kw): its T2I-Adapter(s)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
@@ -825,7 +856,7 @@ class StableDiffusionBase:
                 reference_image_strength=0.8, inpaint_mask=None, mask_blur_strength=None, guidance_rescale=0.7,
                 callback=None, **kw):
         """Reference :141-175.  ``control`` (through **kw, with ``control_net_image``): the ControlNet units of generate_image;
-        ``ip_adapter`` (through **kw): its IP-Adapter image prompt."""
+        ``ip_adapter`` (through **kw): its IP-Adapter image prompt; ``t2i_adapter`` (through **kw): its T2I-Adapter(s)."""
         encoded_text = self.encode_text(prompt, embedding)
         return self.generate_image(encoded_text, negative_prompt=negative_prompt, batch_size=batch_size, num_steps=num_steps,
                                    unconditional_guidance_scale=unconditional_guidance_scale, seed=seed,
@@ -1043,7 +1074,7 @@ class StableDiffusionBase:
                        mask_blur_strength=None, reference_image=None, reference_image_strength=0.8, guidance_rescale=0.0,
                        callback=None, host_loop=False, return_latent=False, sampler=None, hires=None, hires_noise=None,
                        tiled=None, regions=None, pag=None, reference_only=None, hypertile=None, sag=None, dynamic_threshold=None,
-                       control=None, ip_adapter=None):
+                       control=None, ip_adapter=None, t2i_adapter=None):
         """Reference :317-486.  ``sampler``: None (the reference's DDIM-style step, or TCD on an active_tcd pipeline) or one of
         "dpmpp_2m", "dpmpp_2m_sde", "euler_a", each optionally with "_karras" (minsdtf_amd/samplers.py; not with active_tcd).
         With ``self.shard_batch = True`` under an initialised torch.distributed process group `batch_size` is the GLOBAL batch: every rank calls this with the same arguments, rank 0's inputs are broadcast, each
@@ -1142,7 +1173,29 @@ class StableDiffusionBase:
         without ``control`` (the ControlNet's own encoder stays plain), image_to_image, inpainting, ``dynamic_threshold``,
         shard_batch and host_loop=True; not with regions, pag, sag, reference_only, hypertile, tiled, hires or denoise_streams = 2,
         nor with prompts of more than 77 tokens.  One adapter and one picture per job.  A spec whose table is all 0 (weight 0) is the
-        plain job on the plain engine; ``ip_adapter`` = None is the job as it was, bit for bit."""
+        plain job on the plain engine; ``ip_adapter`` = None is the job as it was, bit for bit.
+        ``t2i_adapter`` (a t2iadapter.T2IAdapterSpec or a dict {"image": the conditioning picture, "path": a T2I-Adapter checkpoint |
+        "model": a models.T2IAdapter, "weight": 1.0 or four per-site weights, "start": 0.0, "end": 1.0}, or a list of 1 ..
+        t2iadapter.MAX_UNITS of them): T2I-Adapter structural control (depth, sketch, pose, ...).  The adapter's conv net runs once per
+        job on the picture alone (31 launches; the last picture's features are kept, a repeated job runs nothing) and every UNet pass
+        adds its four feature maps, in place, behind down_blocks.{0,1,2}.attentions.1 and down_blocks.3.resnets.1 - before the skip
+        and the downsampler read them - the same feature to every row: ONE msda_feature_add launch per site, its scale ``weight[site]``
+        inside [``start``, ``end``) by diffusers' rule, read from a per-step device table; several adapters add.  Features and table
+        are per-call uploads, so the engine is keyed by the number of units alone.  The picture (an array 0 .. 255 or a file; (H, W, 3),
+        or (H, W) / (H, W, 1) for a 1-channel adapter) is resized to the job's size, whose height and width are multiples of 64.
+        Works with every sampler, a TCD pipeline, image_to_image, inpainting, ``ip_adapter``, ``dynamic_threshold``, shard_batch and
+        host_loop=True; not with control_net_image, regions, pag, sag, reference_only, hypertile, tiled, hires or denoise_streams = 2.
+        A description whose table is all 0 (weight 0) is the plain job on the plain engine; ``t2i_adapter`` = None is the job as it
+        was, bit for bit."""
+        t2i = t2i_mod.parse(t2i_adapter)   # (ValueError for a bad description)
+        t2i_tab = None
+        if t2i is not None:
+            t2i_mod.refuse(dict(control_net_image=control_net_image, regions=regions, pag=pag, sag=sag, reference_only=reference_only,
+                                hypertile=hypertile, tiled=tiled, hires=hires), self.denoise_streams)
+            t2i_mod.check_size(self.img_height, self.img_width)
+            t2i_tab = t2i_mod.table(t2i, num_steps)
+            if not t2i_tab.any():
+                t2i = t2i_tab = None   # (every scale 0: the plain job, on the plain engine)
         ipa = ipadapter_mod.parse(ip_adapter)   # (ValueError for a bad description)
         ipa_tab = None
         if ipa is not None:
@@ -1224,6 +1277,10 @@ class StableDiffusionBase:
             for t in (context.shape[1], unconditional_context.shape[1]) if float(unconditional_guidance_scale) > 0.0 else (context.shape[1],):
                 ipadapter_mod.check_context(t, ipa_model.tokens)
             engine_opts = dict(engine_opts, ip_tokens=ipa_model.tokens, ip_adapter=ipa_model)   # (a model object beside the options)
+        t2i_feats = None
+        if t2i is not None:   # per unit the four bf16 features of its picture, on the device (every rank of a sharded job makes its own)
+            t2i_feats = self._t2i_inputs(t2i)
+            engine_opts = dict(engine_opts, t2i_units=len(t2i))
         if geo is not None:
             noise = (self._get_initial_diffusion_noise(B, seed, geo.height, geo.width) if diffusion_noise is None
                      else self._batch_of(diffusion_noise, B, 3))
@@ -1304,12 +1361,14 @@ class StableDiffusionBase:
                                                  sampler_z, ip, region_w=region_w, pag=pg, hypertile=ht_key, sag=sg, dynthresh=dt,
                                                  control=None if cu is None else (cu_tab, cu_nets, cu_hints),
                                                  ip=None if ipa is None else (ipa_model, ipa_tok, ipa_tab),
+                                                 t2i=None if t2i is None else (t2i_feats, t2i_tab),
                                                  reference=None if ref is None else (ref, ref_in, reference_mod.rates(sched, start_index)))
             else:
                 latent = self._host_loop(context, unconditional_context, start_latent, g, phi, hint, callback, ascending, ip,
                                          region_w=region_w, pag=pg, hypertile=ht_key, sag=sg, dynthresh=dt,
                                          control=None if cu is None else (cu_tab, cu_nets, cu_hints, start_index),
                                          ip=None if ipa is None else (ipa_model, ipa_tok, ipa_tab, start_index),
+                                         t2i=None if t2i is None else (t2i_feats, t2i_tab, start_index),
                                          reference=None if ref is None else (ref, ref_in, reference_mod.rates(self.scheduler, start_index)))
             if return_latent:
                 return np.asarray(latent, dtype=np.float32)
@@ -1340,6 +1399,8 @@ class StableDiffusionBase:
             shared["control_table"] = cu_tab
         if ipa is not None:   # the two token sets and the table: whole on every rank
             shared["ip_tokens"], shared["ip_table"] = np.stack(ipa_tok, axis=0), ipa_tab
+        if t2i is not None:   # the table: whole on every rank (the features are this rank's own, of the same picture)
+            shared["t2i_table"] = t2i_tab
 
         def local(c, u, z, a):
             """This rank's slice of the batch: one denoise pass -> decode; returns a device tensor."""
@@ -1355,7 +1416,8 @@ class StableDiffusionBase:
                                           reference=None if ref is None else (a["ref_z"], a["ref_noise"], ref.fidelity), sag=sg,
                                           dynamic_threshold=dt,
                                           control=None if cu is None else (a["control_table"], [a[f"control_hint{n + 1}"] for n in range(len(cu) - 1)]),
-                                          ip_adapter=None if ipa is None else (a["ip_tokens"][0], a["ip_tokens"][1], a["ip_table"])))
+                                          ip_adapter=None if ipa is None else (a["ip_tokens"][0], a["ip_tokens"][1], a["ip_table"]),
+                                          t2i_adapter=None if t2i is None else (t2i_feats, a["t2i_table"])))
             if return_latent:
                 return eng.latent
             if blend_pixels:   # pixel blend in fp32 before the uint8 cast
@@ -1706,6 +1768,29 @@ class StableDiffusionBase:
                              + ", ".join(f"{w}: {n}" for w, n in lengths))
         return np.stack(encoded, axis=0), reg.weights()
 
+    def _t2i_model(self, unit):
+        """The models.T2IAdapter of a unit: its `model`, or the checkpoint at its `path`, loaded once and kept on the pipeline."""
+        from .models import T2IAdapter
+
+        if unit.model is not None:
+            if not isinstance(unit.model, T2IAdapter):
+                raise ValueError(f"t2i_adapter: model is {type(unit.model).__name__}, expected a models.T2IAdapter")
+            return unit.model
+        cache = self.__dict__.setdefault("_t2i_adapters_by_path", {})
+        if unit.path not in cache:
+            cache[unit.path] = T2IAdapter(path=unit.path, device=self.diffusion_model.device)
+        return cache[unit.path]
+
+    def _t2i_inputs(self, units) -> list:
+        """Per unit the four bf16 feature tensors of its picture at the job's size (models.T2IAdapter.features: the last picture's
+        are kept, a repeated job does not run the adapter)."""
+        out = []
+        for u in units:
+            model = self._t2i_model(u)
+            px = t2i_mod.picture(u.image, model.in_channels, self.img_height, self.img_width, self.resize)
+            out.append(model.features(px))
+        return out
+
     def _engine_key(self, B, tc, tu, steps, g, phi, control, inpaint=False, job_keys=None, control_nets=(), ip_adapter=None, **opts) -> tuple:
         """`opts` as _engine takes them: one at its default (None) adds nothing to the key, an unknown name is a TypeError.
         `control_nets`: the further units' (ControlNet, HintNet) pairs - which objects they are and their weights' versions.
@@ -1750,8 +1835,9 @@ class StableDiffusionBase:
         return eng
 
     def _host_loop(self, context, unconditional_context, latent, g, phi, hint_image, callback, timesteps=None, inpaint=None,
-                   region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None, ip=None):
-        """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479).  control = (table, the further units'
+                   region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None, ip=None, t2i=None):
+        """The reference's own loop over predict_on_batch (stable_diffusion.py:442-479).  t2i = (the units' features, table, the first
+        executed row) of a job with T2I-Adapters.  control = (table, the further units'
         (ControlNet, HintNet) pairs, their hint pictures, the first executed row) of a job with ControlNet units.
         ip = (the models.IPAdapter, (tokens_u, tokens_c), table, the first executed row) of a job with an image prompt."""
         if timesteps is None:
@@ -1776,8 +1862,9 @@ class StableDiffusionBase:
             cu_step = None if control is None else (cu_units, control[0][control[3] + iteration])
             # (a job with an image prompt: row ip[3] + iteration of its table, the device step counter's row)
             ip_step = None if ip is None else (ip[0], ip[1], ip[2][ip[3] + iteration])
+            t2i_step = None if t2i is None else (t2i[0], t2i[1][t2i[2] + iteration])
             latent = self._guided_eps(latent, t_emb, context, unconditional_context, g, phi, hint, region_w, pag, ref_step, hypertile,
-                                      sag_step, dt_step, cu_step, ip_step)
+                                      sag_step, dt_step, cu_step, ip_step, t2i_step)
             latent = self.scheduler.step(latent, timestep, latent_prev)
             if inpaint is not None:   # reference :469-475
                 init_latent, noise, latent_mask = inpaint
@@ -1797,7 +1884,7 @@ class StableDiffusionBase:
         return units
 
     def _guided_eps(self, latent, t_emb, context, unconditional_context, g, phi, hint, region_w=None, pag=None, reference=None,
-                    hypertile=None, sag=None, dynthresh=None, control=None, ip=None):
+                    hypertile=None, sag=None, dynthresh=None, control=None, ip=None, t2i=None):
         """The UNet's noise prediction with classifier-free guidance and rescale over predict_on_batch (reference :442-467).
         A regional job passes `context` as the list of its region contexts and the normalised weights as `region_w`: one
         predict_on_batch per region, combined in fp32 in msd_region_combine's order (regions.combine_host); in mode "attention"
@@ -1812,9 +1899,13 @@ class StableDiffusionBase:
         of every unit's predict_on_batch are scaled and summed (control.scale_host) with column 0 for the unconditional and column
         1 for the conditional prediction.
         A job with an image prompt passes (the models.IPAdapter, (tokens_u, tokens_c), the step's table row fp32 [16]): every UNet
-        forward is predict_ip, with the zero embedding's tokens for the unconditional and the picture's for the conditional one."""
+        forward is predict_ip, with the zero embedding's tokens for the unconditional and the picture's for the conditional one.
+        A job with T2I-Adapters passes (the units' features, the step's table row fp32 [U][4]): every UNet forward is predict_t2i -
+        the same features for both halves - which also carries the image prompt when there is one."""
         def unet(x, half):
             """The UNet's forward of one half (0: unconditional) over [latent, t_emb, context(, 13 controls)]."""
+            if t2i is not None:
+                return self.diffusion_model.predict_t2i(x, t2i[0], t2i[1], ip=None if ip is None else (ip[0], ip[1][half], ip[2]))
             if ip is not None:
                 return self.diffusion_model.predict_ip(x, ip[0], ip[1][half], ip[2])
             return self.diffusion_model.predict_on_batch(x)
@@ -1887,8 +1978,9 @@ class StableDiffusionBase:
 
     def _host_loop_sampler(self, context, unconditional_context, latent, g, phi, hint_image, callback, sched, start, step_noise=None,
                            inpaint=None, region_w=None, pag=None, reference=None, hypertile=None, sag=None, dynthresh=None, control=None,
-                           ip=None):
+                           ip=None, t2i=None):
         """A samplers.py sampler over predict_on_batch, its step in float64 (samplers.host_step), from evaluation `start`.
+        t2i = (the units' features, table) of a job with T2I-Adapters.
         control = (table, the further units' (ControlNet, HintNet) pairs, their hint pictures) of a job with ControlNet units.
         ip = (the models.IPAdapter, (tokens_u, tokens_c), table) of a job with an image prompt."""
         batch_size = latent.shape[0]
@@ -1905,7 +1997,8 @@ class StableDiffusionBase:
                                  None if sag is None else (sag, float(np.float32(tab[i, 0])), float(np.float32(tab[i, 1]))),
                                  None if dynthresh is None else (dynthresh, float(dt_tab[i - start, 0]), float(dt_tab[i - start, 1])),
                                  None if control is None else (cu_units, control[0][i]),
-                                 None if ip is None else (ip[0], ip[1], ip[2][i]))
+                                 None if ip is None else (ip[0], ip[1], ip[2][i]),
+                                 None if t2i is None else (t2i[0], t2i[1][i]))
             z = step_noise[:, i] if step_noise is not None else None
             x, prev = smp.host_step(tab[i], x, e, prev, z)
             if inpaint is not None:   # the row's own alpha / sigma, as in the device kernel
