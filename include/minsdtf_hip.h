@@ -450,8 +450,11 @@ MSD_API int msd_sampler_step(const MsdSamplerStep* p, msd_stream_t stream);
  *   layout 2: transposed rows out[c * out_rows + r] (fp32 only: the direct-conv form of a Dense);
  * and, when out_frag != NULL, into the fragment-major copy of the same bf16 matrix (MsdConvGemm.w_layout = 2, packing.fragment_major;
  * out_rows % 16 == 0, out_cols % 64 == 0); when colsum != NULL (bf16, the job spans whole destination rows) colsum[r] = fp32 of the
- * fp64 sum of the row's ROUNDED values (the .lncs vector of a LayerNorm fold).  Rows whose rowmap entry falls outside
- * [0, out_rows) are not written.  Deterministic: every element and every row sum has one fixed evaluation order.
+ * fp64 sum of the row's ROUNDED values (the .lncs vector of a LayerNorm fold).  Rows whose destination row r falls outside
+ * [0, out_rows) are not written: neither their elements of out and out_frag nor colsum[r].  A job writes nothing else: the other
+ * rows and columns of the destination, the gap columns of a wide ld and every input keep their bits.  master, down and colscale may
+ * start on any 4-byte boundary and master_ld, k, ld, col_off need not be multiples of 4 or 8 (the vector forms are taken only where
+ * they apply; the result is the same).  Deterministic: every element and every row sum has one fixed evaluation order.
  * `jobs` is the host array (validated here: argument errors return MSD_E_ARG before anything is launched); `jobs_dev` is a device
  * copy of the same entries, which the kernel reads.  first_block = sum over the earlier jobs of ceil(n / 8).  rank <= 512.
  */
